@@ -18,11 +18,19 @@ bf16 activations / weights, fp32 softmax, LayerNorm statistics and gradient aren
 launch's rates (0.4 / 0.3 / 0.3; --dropout 0 ... turns it off).  Weak scaling: every rank processes its own trees
 (assigned by token cost, ddp.balance_trees), no data-path collective except the gradient all-reduce.
 
+A plain run sets up, warms up, times the --steps steps, writes the last timed step's outputs (--dump-outputs DIR) and
+prints the line.  Everything else it can measure or check runs only with --full (each leg still switched off by its
+--no-... option): the numerics self-checks before the warm-up; after the timed region the host-issue step, the roofline
+pass, the N > 1 gradient-exchange self-check and the CPU baseline.
+
 Rank 0 prints ONE JSON line (contract in the task description) carrying
   value / ms_per_step   all comments of the timed steps / wall time between the two barrier + synchronize brackets
   ms_per_step_median    median over the timed steps of the per-step time (HIP events at the step boundaries)
   packer_h2d_ms         [median, max] copy-stream time per batch (pack + H2D + index build) over the timed steps —
                         overlapped with the previous step; packer_host_ms the same for the host side alone
+and with --full also
+  host_issue_ms_per_step  host time to enqueue one step, taken on an idle GPU after the timed region
+  selfcheck     the numerics self-checks' results
   roofline      the dominant kernel (bf16 MFMA tile GEMM): algorithmic FLOPs of its launches / their summed duration,
                 measured live with HIP events on the launch stream in a pass of the same steps on ONE stream right
                 after the timed region (the timed region overlaps the text and image branches on two HIP streams,
@@ -31,6 +39,9 @@ Rank 0 prints ONE JSON line (contract in the task description) carrying
   cpu_baseline  the oracle (CPU restatement of the reference math, fp32, torch CPU) timed on this box's host cores on
                 a bounded sample of the same workload (2 trees of the workload's own size) and, for --config base, on
                 BASELINE.json configs[0] in full (rank 0, N = 1).
+
+--dump-outputs DIR: see dump_outputs().  The trees, the weights and the dropout seeds follow fixed seeds, so two runs
+with the same arguments feed the timed steps the same inputs and two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -473,6 +484,41 @@ def selfcheck_model(model, pb, build_fp32, crit=None, fp32_tol=0.08):
     return out
 
 
+DUMP_SAMPLE = 1 << 22        # elements per sampled array: 16 MB of float32
+
+
+def dump_outputs(out_dir, model, scalars, grad_scale, with_params=False):
+    """--dump-outputs: what a step hands its caller, as float32 / float64 ``<out_dir>/<name>.npy`` (about 32 MB at most):
+      scalars      loss, sample size, ncorrect, num_positive_correct, total_positive, num_pred_positive (summed over ranks)
+      grad_scale   1 / sample size, the factor the optimiser applies to the gradient arena (which holds the sums)
+      grad_norms   L2 norm of every trainable parameter's gradient, in named_parameters() order
+      grad_sample  a fixed sample (seed 0) of the gradient elements of those parameters, concatenated in that order — the
+                   arena's own layout (padding, data-parallel bucket order) does not enter
+      param_norms, param_sample   the same for the parameters after the optimiser's update (``with_params``)"""
+    ts = [p for _, p in model.named_parameters() if hasattr(p, "main_grad")]
+    sizes = [t.numel() for t in ts]
+    idx = np.sort(np.random.default_rng(0).choice(sum(sizes), min(DUMP_SAMPLE, sum(sizes)), replace=False))
+    bounds = np.cumsum([0] + sizes)
+
+    def norms_and_sample(xs):
+        parts = []
+        for x, lo, hi in zip(xs, bounds[:-1], bounds[1:]):
+            sel = idx[np.searchsorted(idx, lo):np.searchsorted(idx, hi)] - lo
+            parts.append(x.detach().reshape(-1)[torch.from_numpy(sel).to(x.device)].float())
+        norms = torch.stack([x.detach().double().norm() for x in xs])
+        return norms.cpu().numpy(), torch.cat(parts).cpu().numpy()
+
+    arrays = {"scalars": scalars.detach().double().cpu().numpy(),
+              "grad_scale": grad_scale.detach().double().reshape(1).cpu().numpy()}
+    arrays["grad_norms"], arrays["grad_sample"] = norms_and_sample([t.main_grad for t in ts])
+    if with_params:
+        arrays["param_norms"], arrays["param_sample"] = norms_and_sample(ts)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     if os.environ.get("MDT_BENCH_WATCHDOG"):      # diagnostics: dump every thread's Python stack and exit if the run takes longer
         import faulthandler
@@ -506,7 +552,13 @@ def main():
     ap.add_argument("--no-verify-exchange", action="store_true", help="N > 1: skip the gradient-exchange self-check after the timed region")
     ap.add_argument("--with-optimizer", action="store_true",
                     help="also run the fused Adam update inside every timed step (the headline metric is fwd+bwd only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the self-checks, the host-issue and roofline passes, the N > 1 exchange check and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     for var in ("MDT_GEMM_DIAG", "MDT_GEMM_STAMP"):
         if os.environ.get(var):
             raise SystemExit(f"bench.py refuses to run with {var} set: it changes what the GEMM kernels do (diagnostics only)")
@@ -563,10 +615,11 @@ def main():
     from multimodaldiscussiontransformer_amd.models import GraphormerModel
 
     low = args.dtype in ("bf16", "fp8")
-    if low and not args.no_selfcheck:
+    run_selfcheck = args.full and low and not args.no_selfcheck
+    if run_selfcheck:
         selfcheck()
     timer = GemmTimer()
-    if not args.no_gemm_timer:
+    if args.full and not args.no_gemm_timer:
         timer.install()
     dtype = torch.bfloat16 if low else torch.float32
     torch.manual_seed(1234)                      # same random-init weights on every rank
@@ -609,7 +662,7 @@ def main():
     torch.cuda.synchronize()
     check_batch = pack_batch(host_trees[0], spatial_pos_max=5)
     model_check = None
-    if low and not args.no_selfcheck:
+    if run_selfcheck:
         model_check = selfcheck_model(model, check_batch, lambda: GraphormerModel.build_model(base_args(args), task=None).cuda().float(), crit,
                                       fp32_tol=0.2 if fp8_state is not None else 0.08)
     tok_lens = check_batch.text_mask.sum(1).tolist()
@@ -620,7 +673,8 @@ def main():
         del check_batch
 
     def step(pb, marks=None):
-        """one step = ``uf`` micro-batches (a list when uf > 1) accumulated into the gradient arena, then the exchange (+ Adam)"""
+        """one step = ``uf`` micro-batches (a list when uf > 1) accumulated into the gradient arena, then the exchange (+ Adam);
+        returns the device scalar 1 / (global sample size) that the arena's gradient sums are to be multiplied by"""
         mark = (lambda name: marks.append((name, time.perf_counter()))) if marks is not None else (lambda name: None)
         mark("start")
         dp.zero_grad()
@@ -654,7 +708,7 @@ def main():
         if opt is not None:
             opt.step(grad_scale=gscale)
         mark("finish")
-        return loss
+        return gscale
 
     def fence():
         if dist.is_initialized():
@@ -685,21 +739,28 @@ def main():
     for i in range(args.steps):
         pb = next(batches)
         comments.append(n_comments(pb))
-        step(pb)
+        gscale = step(pb)
         ev[i + 1].record()
     fence()
     dt = time.perf_counter() - t0
     dist_diag = dp.diagnostics() if dp.bucketer.active else None        # of the LAST TIMED step (before the check runs below change it)
     step_ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
     ms_median = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
-    # host time to ENQUEUE one step (no sync inside a step), taken on an idle GPU: inside the back-to-back timed region
-    # the HIP runtime holds the host back once its queues are full, so the loop's host time there just mirrors the GPU's
-    last = next(batches)
-    t1 = time.perf_counter()
-    step(last, host_marks)
-    t_issue = time.perf_counter() - t1
-    fence()
-    host_phases = {b[0]: round((b[1] - a[1]) * 1e3, 2) for a, b in zip(host_marks, host_marks[1:])}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, scal, gscale, with_params=opt is not None)
+    t_issue, host_phases = None, None
+    if args.full:
+        # host time to ENQUEUE one step (no sync inside a step), taken on an idle GPU: inside the back-to-back timed region
+        # the HIP runtime holds the host back once its queues are full, so the loop's host time there just mirrors the GPU's
+        last = next(batches)
+        t1 = time.perf_counter()
+        step(last, host_marks)
+        t_issue = time.perf_counter() - t1
+        fence()
+        host_phases = {b[0]: round((b[1] - a[1]) * 1e3, 2) for a, b in zip(host_marks, host_marks[1:])}
+    elif pf is not None:
+        for _ in pf:        # the batch generated for --full's host-issue step: the prefetch thread finishes it before the process ends
+            pass
     # per-batch cost of the feed (steady state: the warm-up batches pay the one-off pinned-memory allocations)
     packer_ms = [round(x, 2) for x in pf.copy_ms_per_batch(skip=args.warmup)] if pf is not None else None
     packer_host_ms = [round(x, 2) for x in pf.host_ms_per_batch(skip=args.warmup)] if pf is not None else None
@@ -707,7 +768,7 @@ def main():
     # every GEMM launch.  In the timed region the text and image branches run on two streams and their kernels overlap,
     # so a bracket there times "this kernel plus its wait for compute units held by the other branch", not the kernel.
     dt_single = None
-    if not args.no_gemm_timer:
+    if args.full and not args.no_gemm_timer:
         two = ge_.two_streams
         ge_.two_streams = False
         roof = [last, pack_batch(host_trees[0], spatial_pos_max=5) if uf == 1 else [pack_batch(host_trees[k], spatial_pos_max=5) for k in range(uf)]]
@@ -726,7 +787,7 @@ def main():
     # bucketed, overlapped step; that step against the same step with every bucket held back until backward has ended,
     # and against ONE flat all-reduce of the arena (same batch, same dropout seeds: ddp.DataParallel.verify_exchange)
     exchange_check = None
-    if dp.bucketer.active and not args.no_verify_exchange:
+    if args.full and dp.bucketer.active and not args.no_verify_exchange:
         vb = last
 
         # the check repeats ONE step three times and compares the gradients: the step must leave nothing behind that the
@@ -746,8 +807,8 @@ def main():
         opt = opt_keep
         if not exchange_check["ok"]:
             raise SystemExit(f"gradient exchange self-check failed on rank {rank}: {exchange_check}")
-    tot = torch.tensor([dt, float(sum(comments)), packer_host_ms[1] if packer_host_ms else 0.0, packer_ms[1] if packer_ms else 0.0, t_issue * 1e3],
-                       dtype=torch.float64, device="cuda")
+    tot = torch.tensor([dt, float(sum(comments)), packer_host_ms[1] if packer_host_ms else 0.0, packer_ms[1] if packer_ms else 0.0,
+                        t_issue * 1e3 if t_issue is not None else 0.0], dtype=torch.float64, device="cuda")
     per_rank_host = None
     if dist.is_initialized():
         both = [torch.zeros_like(tot) for _ in range(world)]
@@ -757,7 +818,8 @@ def main():
         per_rank_comments = [int(b[1]) for b in both]
         # host-side contention between the ranks of one node (each packs, uploads and enqueues on its own cores): worst batch per rank
         per_rank_host = dict(packer_host_ms_max=[round(float(b[2]), 2) for b in both], packer_h2d_ms_max=[round(float(b[3]), 2) for b in both],
-                             host_issue_ms=[round(float(b[4]), 2) for b in both], torch_cpu_threads_per_rank=torch.get_num_threads())
+                             host_issue_ms=[round(float(b[4]), 2) for b in both] if t_issue is not None else None,
+                             torch_cpu_threads_per_rank=torch.get_num_threads())
     else:
         total_comments = float(sum(comments))
         per_rank_comments = [int(total_comments)]
@@ -833,10 +895,13 @@ def main():
             "padded_equivalent_tflops": round(value * fpc3_padded / 1e12, 1),
             "text_layout": "ragged" if ragged else "padded",
             "compute_streams": 2 if ge_.two_streams else 1,     # image branch beside the text branch
-            "host_issue_ms_per_step": round(t_issue * 1e3, 2), "host_issue_phases_ms": host_phases,
-            "roofline": roofline,
-            "selfcheck": "skipped" if (args.no_selfcheck or not low) else dict(kernels="passed", **(model_check or {})),
         }
+        if args.full:
+            out.update({
+                "host_issue_ms_per_step": round(t_issue * 1e3, 2), "host_issue_phases_ms": host_phases,
+                "roofline": roofline,
+                "selfcheck": "skipped" if (args.no_selfcheck or not low) else dict(kernels="passed", **(model_check or {})),
+            })
         if FOREIGN_LIBRARY:
             out["foreign_library"] = True
         if fp8_state is not None:
@@ -847,7 +912,7 @@ def main():
         if dist_diag is not None:
             out["distributed"] = dict(world=world, backend=backend, comments_per_rank=per_rank_comments, variable_trees=bool(args.variable_trees),
                                       exchange_check=exchange_check, per_rank_host=per_rank_host, **dist_diag)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

@@ -41,7 +41,7 @@ def test_bench_gpus_2_as_typed_on_one_card(extra):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(MDT_SINGLE_DEVICE="1", MDT_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", GPU_MAX_HW_QUEUES="4")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--trees", "2", "--nodes", "16",
-           "--no-gemm-timer", "--no-selfcheck"] + extra
+           "--full", "--no-gemm-timer", "--no-selfcheck"] + extra
     proc = subprocess.Popen(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
     try:
         out, err = proc.communicate(timeout=420)

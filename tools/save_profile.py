@@ -1,4 +1,5 @@
-"""Copy a measurement set produced by tools/run_profile.sh <tag> from gpurun_out/ into profiles/ (named per round)."""
+"""Copy a measurement set produced by tools/run_profile.sh <tag> from its output directory ($MDT_OUT, default out/) into
+profiles/ (named per round)."""
 import collections
 import csv
 import glob
@@ -10,7 +11,7 @@ import sys
 tag = sys.argv[1]
 rnd = sys.argv[2] if len(sys.argv) > 2 else "round1"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-base = os.path.join(root, "gpurun_out", "")
+base = os.path.join(root, os.environ.get("MDT_OUT", "out"), "")
 dst = os.path.join(root, "profiles", f"{rnd}_{tag}")
 shutil.copy(glob.glob(base + f"{tag}_prof/*/*kernel_stats.csv")[0], dst + "_kernel_stats.csv")
 def steps_in(stats_csv):
