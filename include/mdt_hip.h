@@ -47,12 +47,14 @@ enum {
   MDT_EPI_ACCUM = 16,    /* C += result (plain read-modify-write, fp32 or T) */
   MDT_EPI_ATOMIC = 32,   /* C (fp32) += result with float atomics (split-K weight gradients) */
   MDT_EPI_COLSUM = 128,  /* colsum[n] += sum_m C[m, n] (fp32 atomics) — the bias gradient of the layer whose
-                            output gradient this GEMM produces, fused instead of a separate pass */
+                            output gradient this GEMM produces, fused instead of a separate pass.  Summed is the fp32
+                            epilogue result r[m, n] of THIS call, before it is rounded to C's type: with MDT_EPI_ACCUM
+                            (C = C_old + r) the old contents of C are not part of the sum — colsum[n] += sum_m r[m, n] */
   MDT_EPI_AUX_GRAD = 256, /* with MDT_EPI_GELU and aux != NULL: aux receives d out / d pre-activation
                             (GELU'(u), times the dropout scale of the element when MDT_EPI_DROPOUT is set)
                             instead of u — the backward pass is then a plain MDT_EPI_MULAUX */
   MDT_EPI_MULAUX = 512,  /* * aux[m, n] (backward of an epilogue that saved its derivative) */
-  MDT_EPI_ASUM = 1024,   /* colsum[m] += sum_k op(A)[m, k] (fp32 atomics): with trans_a = 1 the column sums of the STORED
+  MDT_EPI_ASUM = 1024,   /* colsum[m] += sum_k op(A)[m, k] (fp32 atomics, NOT scaled by alpha): with trans_a = 1 the column sums of the STORED
                             A — the bias gradient db = colsum(dY) riding on the weight-gradient GEMM dW = dY^T X that
                             streams dY anyway (one extra MFMA against a vector of ones per A fragment, in the workgroups
                             of the first tile column only).  Needs trans_a = 1, MDT_EPI_ATOMIC and a colsum buffer of M

@@ -419,12 +419,12 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp256(GemmParams p) {
     direct_epilogue<2>(p, acc, lane, m0 + wr * 128, n0 + wc * 64);
     return;
   }
-  if (asum && (lane & 15) == 0) {      // every column of the ones product holds the row sum: column 0 reports it
+  if (asum && (lane & 15) == 0) {      // every column of the ones product holds the row sum: column 0 reports it (unscaled by alpha)
     const int64_t mr = m0 + wr * 128 + wc * 32 + 4 * (lane >> 4);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      if (mr + r < p.M) atomicAdd(p.colsum + mr + r, p.alpha * accb0[r]);
-      if (mr + 16 + r < p.M) atomicAdd(p.colsum + mr + 16 + r, p.alpha * accb1[r]);
+      if (mr + r < p.M) atomicAdd(p.colsum + mr + r, accb0[r]);
+      if (mr + 16 + r < p.M) atomicAdd(p.colsum + mr + 16 + r, accb1[r]);
     }
   }
 #pragma unroll

@@ -211,13 +211,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #undef W4S_MF
 #undef W4S_MB
 #undef W4S_PIN
-  if (asum_on && (lane & 15) == 0) {   // every column of the ones product holds the row sum: column 0 reports it
+  if (asum_on && (lane & 15) == 0) {   // every column of the ones product holds the row sum: column 0 reports it (unscaled by alpha)
     const int64_t mr = m0 + wr * 128 + wc * 64 + 4 * (lane >> 4);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (mr + 16 * q + r < p.M) atomicAdd(p.colsum + mr + 16 * q + r, p.alpha * accb[q][r]);
+        if (mr + 16 * q + r < p.M) atomicAdd(p.colsum + mr + 16 * q + r, accb[q][r]);
   }
   // four 64 x 64 blocks per wave through its 16-KiB LDS slot (the first 64 KiB of the ring; every request has landed)
 #pragma unroll

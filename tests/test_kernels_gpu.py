@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from multimodaldiscussiontransformer_amd import _lib as L
+from tests import gemm_reference as GR
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +85,9 @@ def test_gemm_bf16_tile128(ops, ta, tb, M, N, K):
     torch.testing.assert_close(out32.cpu(), ref, atol=1e-3, rtol=1e-4)
     out16 = ops.gemm(dev(a), dev(b), trans_a=bool(ta), trans_b=bool(tb))
     torch.testing.assert_close(out16.float().cpu(), ref, atol=0.06, rtol=1e-2)   # bf16 rounding of |x| <~ 8
+    v, d = GR.reference(a, b, trans_a=bool(ta), trans_b=bool(tb))["out"]       # per element: ½ ulp of bf16 + the fp32 sum's bound
+    GR.assert_within(out16.cpu(), v, GR.bound(v, d, torch.bfloat16), what="tile128 bf16 out")
+    GR.assert_within(out32.cpu(), v, GR.bound(v, d, torch.float32), what="tile128 fp32 out")
 
 
 def test_gemm_bf16_wgrad_splitk_and_epilogues(ops):
@@ -326,7 +330,10 @@ def test_gemm_training_epilogues_persistent(ops):
     torch.testing.assert_close(y.float(), u * mask + res.float(), **tol)
     dy = dev(rnd(M, N, seed=5, scale=0.1).to(bf))
     dref = dy.float() @ w.float()
-    torch.testing.assert_close(ops.gemm(dy, w, trans_b=True).float(), dref, **tol)                            # 0
+    dg = ops.gemm(dy, w, trans_b=True)                                                                       # 0
+    torch.testing.assert_close(dg.float(), dref, **tol)
+    v, d = GR.reference(dy, w, trans_b=True)["out"]
+    GR.assert_within(dg, v, GR.bound(v, d, bf), what="dgrad dy @ w")
     resk = dev(rnd(M, K, seed=6, scale=0.5).to(bf))
     torch.testing.assert_close(ops.gemm(dy, w, trans_b=True, residual=resk).float(), dref + resk.float(), **tol)   # 4
     w2 = dev(rnd(K, N, seed=7, scale=0.05).to(bf))
@@ -336,6 +343,8 @@ def test_gemm_training_epilogues_persistent(ops):
     du_ref = (dz.float() @ w2.float()) * aux.float()
     torch.testing.assert_close(du.float(), du_ref, **tol)
     torch.testing.assert_close(cs, du_ref.sum(0), atol=1.0, rtol=3e-2)
+    r = GR.reference(dz, w2, trans_b=True, epilogue=GR.EPI_MULAUX, aux=aux)   # (exact column sums: tests/test_gemm_routes_gpu.py)
+    GR.check({"out": du}, r, {"out": bf}, what="d fc1 saved-derivative product")
 
 
 def test_colsum_cast_transpose(ops):
