@@ -44,6 +44,7 @@ class AttnBwdArgs(C.Structure):
 _SIGS = {
     "mdt_abi_version": ([], _i),
     "mdt_last_error_string": ([], C.c_char_p),
+    "mdt_last_route": ([], C.c_char_p),
     "mdt_source_hash": ([], C.c_char_p),
     "mdt_gemm": ([_vp, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _f, _vp, _vp, _i64,
                   _vp, _i64, _i, _f, C.c_uint64, _vp], _i),
@@ -141,6 +142,11 @@ lib = _load()
 def reload_env():
     """The library reads its MDT_* environment switches once; call this after changing them (tests, A/B tools)."""
     lib.mdt_reload_env()
+
+
+def last_route() -> str:
+    """The route of this thread's last successful GEMM / attention launch ("w4p", "v4x", ...; include/mdt_hip.h)."""
+    return lib.mdt_last_route().decode()
 
 
 _TILE_QUEUE = None

@@ -542,17 +542,8 @@ static int launch_fwd(hipStream_t st, const AttnParams& p) {
   constexpr int s_pad32 = (NT * 16 + 31) & ~31;
   constexpr bool BF = !std::is_same<T, float>::value;
   const int sld = s_pad32 + (BF ? 8 : 1);
-  size_t lds = (size_t)4 * 16 * sld * sizeof(T) + (BF ? (size_t)2 * s_pad32 * IMG_LD * 2 : 0);
-  auto kern = attn_fwd_kernel<T, HD, NT, STRUCT, DROP>;
-  if (lds > 64 * 1024) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("attention_fwd: cannot reserve %zu bytes of LDS", lds);
-      return MDT_ERR_LAUNCH;
-    }
-  }
-  hipLaunchKernelGGL(kern, dim3(p.f.H, p.f.nseq), 256, lds, st, p);
-  return check_launch("attention_fwd");
+  const size_t lds = (size_t)4 * 16 * sld * sizeof(T) + (BF ? (size_t)2 * s_pad32 * IMG_LD * 2 : 0);
+  return launch_route<attn_fwd_kernel<T, HD, NT, STRUCT, DROP>>("v1", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
 }
 
 template <typename T, int HD, int NT, bool STRUCT, bool DROP>
@@ -561,18 +552,9 @@ static int launch_bwd(hipStream_t st, const AttnParams& p) {
   constexpr bool BF = !std::is_same<T, float>::value;
   const int sld = s_pad32 + (BF ? 8 : 1);
   const int nhist = STRUCT ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
-  size_t lds = (size_t)(2 * s_pad32 + nhist) * 4 + (size_t)4 * 16 * sld * sizeof(T) +
+  const size_t lds = (size_t)(2 * s_pad32 + nhist) * 4 + (size_t)4 * 16 * sld * sizeof(T) +
                (BF ? (size_t)2 * s_pad32 * IMG_LD * 2 : 0);
-  auto kern = attn_bwd_kernel<T, HD, NT, STRUCT, DROP>;
-  if (lds > 64 * 1024) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("attention_bwd: cannot reserve %zu bytes of LDS", lds);
-      return MDT_ERR_LAUNCH;
-    }
-  }
-  hipLaunchKernelGGL(kern, dim3(p.f.H, p.f.nseq), 256, lds, st, p);
-  return check_launch("attention_bwd");
+  return launch_route<attn_bwd_kernel<T, HD, NT, STRUCT, DROP>>("v1", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
 }
 
 template <typename T, int HD, bool STRUCT, bool BWD>
@@ -593,37 +575,24 @@ template <bool BWD>
 static int dispatch(hipStream_t st, const AttnParams& p) {
   const mdt_attn_fwd_args& a = p.f;
   const bool st_bias = a.attn_bias != nullptr;
-  const bool binned = a.seq_ids != nullptr || a.s_cap > 0;        // length bins of a ragged set: the v2 forward / v3-v4 backward only
-  if (binned) {
-    if (a.S > 272 || a.dtype != MDT_BF16 || a.hd != 64 || !a.seq_offsets || switches().attn_v1) {
+  if (a.seq_ids != nullptr || a.s_cap > 0) {                     // length bins of a ragged set: the v2 forward / v3-v5 backward only
+    if (a.S > 272 || a.dtype != MDT_BF16 || a.hd != 64 || !a.seq_offsets) {
       set_error("attention: seq_ids / s_cap are for ragged bf16 launches with head_dim 64 and S <= 272");
       return MDT_ERR_UNSUPPORTED;
     }
-    return BWD ? attention_v3_bwd_dispatch(st, p) : attention_v2_dispatch(st, p, false);
-  }
-  if (a.S > 272) return attention_long_dispatch(st, p, BWD);      // discussion trees with more than 271 comments
+  } else if (a.S > 272) return attention_long_dispatch(st, p, BWD);      // discussion trees with more than 271 comments
   if (a.dtype == MDT_BF16) {
-    // a plain dense bias (no structural terms) is only handled by the kernels in this file
-    const bool dense_only = (a.dense_bias != nullptr || p.d_dense_bias != nullptr) && !st_bias;
-    if (a.hd == 64 && !dense_only && !switches().attn_v1) {
-      if (!BWD) return attention_v2_dispatch(st, p, false);              // forward: register-resident P
-      // backward, measured at C2 shapes (profiles/round1_attention_v2.txt): S <= 112 -> whole-row v2,
-      // longer sequences -> chunked v3 / one-pass v4; tiny graphs and short rows (S <= 80) stay on the LDS-scratch kernel below
-      const char* force = switches().attn_bwd[0] ? switches().attn_bwd : nullptr;      // MDT_ATTN_BWD = "v1" | "v2" | "v3" for A/B runs
-      const bool drop = a.drop_p > 0.f;                // with dropout the whole-row v2 falls to 1 wave / SIMD: chunked v3 wins
-      if (BWD && a.S > 256 && !force) return attention_v3_bwd_dispatch(st, p);   // ViT-L/14: 4 + 257 tokens
-      // (plain rows of up to 80 tokens take the one-pass kernel since round 4 — 3 x faster, 749 -> 225 us on 2048 ragged sequences
-      // of 10-64 tokens — now that its short-row form sums delta = sum P o dP itself, in fp32, like the scratch kernel does
-      // (attn_bwd_v4x); graphs with a structural bias stay here)
-      // neither the scratch kernel nor the whole-row v2 backward knows of q_limit (they would read the out / lse rows the v2 FORWARD
-      // skipped — unwritten memory): such launches take v3 / v4 whatever MDT_ATTN_BWD says (tests: ..._never_reads_what_forward_did_not_write)
-      const bool v1 = force ? (!strcmp(force, "v1") && a.q_limit == 0) : (a.S <= 80 && a.q_limit == 0 && (st_bias || !switches().attn_exact_delta));
-      const bool v2 = (force ? !strcmp(force, "v2") : !drop) && a.q_limit == 0 && a.S <= 112;
-      if (!v1) return v2 ? attention_v2_dispatch(st, p, true) : attention_v3_bwd_dispatch(st, p);
+    if (a.hd != 64) {
+      set_error("attention(bf16): head_dim %d unsupported (64 only)", a.hd);
+      return MDT_ERR_UNSUPPORTED;
     }
-    if (a.hd == 64) return st_bias ? dispatch_nt<bf16_t, 64, true, BWD>(st, p) : dispatch_nt<bf16_t, 64, false, BWD>(st, p);
-    set_error("attention(bf16): head_dim %d unsupported (64 only)", a.hd);
-    return MDT_ERR_UNSUPPORTED;
+    // forward: register-resident P (v2) unless a plain dense bias (no structural terms), which only the kernels in this file
+    // take; backward: attn_bwd_route (attention_v2.hip)
+    const bool dense_only = (a.dense_bias != nullptr || p.d_dense_bias != nullptr) && !st_bias;
+    const AttnRoute r = BWD ? attn_bwd_route(p) : dense_only ? AttnRoute::v1 : AttnRoute::v2;
+    if (r == AttnRoute::v2) return attention_v2_dispatch(st, p, BWD);
+    if (r != AttnRoute::v1) return attention_v3_bwd_dispatch(st, p, r);
+    return st_bias ? dispatch_nt<bf16_t, 64, true, BWD>(st, p) : dispatch_nt<bf16_t, 64, false, BWD>(st, p);
   }
   if (a.hd == 64) return st_bias ? dispatch_nt<float, 64, true, BWD>(st, p) : dispatch_nt<float, 64, false, BWD>(st, p);
   if (a.hd == 16) return st_bias ? dispatch_nt<float, 16, true, BWD>(st, p) : dispatch_nt<float, 16, false, BWD>(st, p);

@@ -229,7 +229,9 @@ static int long_launch(hipStream_t st, const AttnParams& p, bool bwd) {
   if (!bwd) {
     if (st_bias) hipLaunchKernelGGL((attn_long_fwd_kernel<T, HD, true>), grid, 64, 0, st, p);
     else hipLaunchKernelGGL((attn_long_fwd_kernel<T, HD, false>), grid, 64, 0, st, p);
-    return check_launch("attention_long_fwd");
+    if (int e = check_launch("attention_long_fwd")) return e;
+    set_last_route("long");
+    return MDT_OK;
   }
   if (st_bias) {
     hipLaunchKernelGGL((attn_long_dq_kernel<T, HD, true>), grid, 64, 0, st, p);
@@ -238,7 +240,9 @@ static int long_launch(hipStream_t st, const AttnParams& p, bool bwd) {
     hipLaunchKernelGGL((attn_long_dq_kernel<T, HD, false>), grid, 64, 0, st, p);
     hipLaunchKernelGGL((attn_long_dkv_kernel<T, HD, false>), grid, 64, 0, st, p);
   }
-  return check_launch("attention_long_bwd");
+  if (int e = check_launch("attention_long_bwd")) return e;
+  set_last_route("long");
+  return MDT_OK;
 }
 
 int attention_long_dispatch(hipStream_t st, const AttnParams& p, bool bwd) {

@@ -14,7 +14,7 @@
 // ds_writes + wave fences per tile), halves the LDS footprint (4 workgroups per CU at S = 104)
 // and reduces the softmax reductions from four shuffles to two.
 // Same C ABI, same masks / structural bias / dropout semantics; attention.hip keeps the fp32
-// parity path and remains selectable for bf16 with MDT_ATTN_V1=1.
+// parity path and the bf16 kernels for a dense bias (and the backward of short structural-bias rows).
 #include "attention_common.hpp"
 
 namespace mdt {
@@ -1430,108 +1430,89 @@ static size_t v4_lds_bytes(int S, int* rows_img, int* ldq) {
   return b <= 160 * 1024 ? b : 0;
 }
 
+// The backward kernel of a bf16 launch with head_dim 64 (S <= 272; length-binned launches: s_cap <= 272).  Default, in order:
+//   length-binned launches (seq_ids / s_cap)              -> the family below
+//   a dense bias without structural terms                -> v1 (attention.hip: the only kernels that take one)
+//   S > 256 (ViT-L/14: 4 + 257 tokens)                   -> family
+//   S <= 80, q_limit == 0, structural bias               -> v1 (LDS-scratch kernel: tiny graphs)
+//   no dropout, q_limit == 0, S <= 112                   -> v2 (whole row in registers; with dropout it falls to 1 wave / SIMD)
+//   otherwise                                            -> family
+// The family, without a structural bias, where the one-pass dS image fits LDS (S <= 208): v5 (9-13 key tiles, persistent),
+// v4x (<= 6 key tiles: delta = sum P o dP summed in the kernel, in fp32), v4 (7-8 key tiles); past that, and with a
+// structural bias: the two-pass v3.  Measured at C2 shapes: profiles/round1_attention_v2.txt, tools/attn_onepass_ab.py.
+// MDT_ATTN_BWD=<kernel> takes that kernel wherever its preconditions (ok() below) hold.  v1 and v2 never see q_limit or
+// length bins (they would read the out / lse rows the v2 forward skipped — unwritten memory; tests:
+// ..._never_reads_what_forward_did_not_write), v2 takes S <= 112 only, the one-pass kernels take no structural bias.
+AttnRoute attn_bwd_route(const AttnParams& p) {
+  const mdt_attn_fwd_args& a = p.f;
+  const bool st_bias = a.attn_bias != nullptr, binned = a.seq_ids != nullptr || a.s_cap > 0;
+  const bool dense_only = (a.dense_bias != nullptr || p.d_dense_bias != nullptr) && !st_bias;
+  const int cap = a.s_cap > 0 ? a.s_cap : a.S;                   // longest sequence of this launch
+  const int n_t = (cap + 15) / 16;
+  int rows_img = 0, ldq = 0;
+  const bool one_pass = !st_bias && !dense_only && v4_lds_bytes(cap, &rows_img, &ldq) != 0 && n_t <= 16;
+  auto ok = [&](AttnRoute r) {
+    switch (r) {
+      case AttnRoute::v1: return !binned && a.q_limit == 0;
+      case AttnRoute::v2: return !binned && !dense_only && a.q_limit == 0 && a.S <= 112;
+      case AttnRoute::v3: return !dense_only;
+      case AttnRoute::v4: return one_pass;
+      case AttnRoute::v4x: return one_pass && n_t <= 2 * V4_EXACT_PAIRS;
+      case AttnRoute::v5: return one_pass && n_t > 8 && rows_img * 8 <= 4 * 512;     // long rows (one workgroup per CU by LDS)
+      default: return false;
+    }
+  };
+  const AttnRoute family = ok(AttnRoute::v5) ? AttnRoute::v5 : ok(AttnRoute::v4x) ? AttnRoute::v4x : one_pass ? AttnRoute::v4 : AttnRoute::v3;
+  AttnRoute r;
+  if (binned) r = family;
+  else if (dense_only) r = AttnRoute::v1;
+  else if (a.S > 256) r = family;
+  else if (a.S <= 80 && a.q_limit == 0 && st_bias) r = AttnRoute::v1;
+  else if (!(a.drop_p > 0.f) && ok(AttnRoute::v2)) r = AttnRoute::v2;
+  else r = family;
+  const AttnRoute forced = switches().attn_bwd;
+  return forced != AttnRoute::none && ok(forced) ? forced : r;
+}
+
 template <bool STRUCT, bool DROP>
-static int launch_v3(hipStream_t st, const AttnParams& p) {
+static int launch_v3(hipStream_t st, const AttnParams& p, AttnRoute r) {
   const int cap = p.f.s_cap > 0 ? p.f.s_cap : p.f.S;          // longest sequence of this launch
   const int s_pad = (cap + 63) & ~63;
   const int nhist = STRUCT ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
   const size_t lds = (size_t)2 * s_pad * V2_LD * 2 + (size_t)3 * s_pad * 4 + (size_t)nhist * 4;
   if (lds > 160 * 1024) { set_error("attention_bwd_v3: S=%d needs %zu bytes of LDS", cap, lds); return MDT_ERR_UNSUPPORTED; }
-  auto kern = attn_bwd_v3_kernel<64, STRUCT, DROP>;
-  if (lds > 64 * 1024) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("attention_bwd_v3: cannot reserve %zu bytes of LDS", lds);
-      return MDT_ERR_LAUNCH;
+  const dim3 grid(p.f.H, p.f.nseq);
+  if constexpr (STRUCT) {
+    return launch_route<attn_bwd_v3_kernel<64, true, DROP>>("v3", grid, 256, lds, st, p, s_pad);
+  } else {
+    if (r == AttnRoute::v3) {
+      // long sequences (ViT: 13 tiles): LDS allows two workgroups per CU; 8 waves each in the 128-register build = 4 waves
+      // per SIMD instead of 2 (in-call A/B at the ViT shape: +0.7 % on the step)
+      return launch_route<attn_bwd_v3_occ4_kernel<64, DROP>>("v3", grid, s_pad <= 128 ? 256 : 512, lds, st, p, s_pad);
     }
-  }
-  if constexpr (!STRUCT) {
-    // one-pass kernel wherever its dS image fits LDS (S <= 224); MDT_ATTN_ONEPASS=0 keeps the two-pass kernels.  In-call
-    // A/B with dropout 0.1 (tools/attn_onepass_ab.py): ViT rows (512 x 201) 755 -> 525 us, padded BERT rows (2048 x 104)
-    // 993 -> 792 us, ragged BERT rows (8-100 tokens) 592 -> 493 us; gradients equal to bf16 rounding of delta.
-    const int op = switches().attn_onepass;
+    // one pass.  In-call A/B with dropout 0.1 (tools/attn_onepass_ab.py): ViT rows (512 x 201) 755 -> 525 us, padded BERT rows
+    // (2048 x 104) 993 -> 792 us, ragged BERT rows (8-100 tokens) 592 -> 493 us; gradients equal to bf16 rounding of delta.
     int rows_img = 0, ldq = 0;
     const size_t lds4 = v4_lds_bytes(cap, &rows_img, &ldq);
-    if (lds4 && op != 0) {
-      auto k4 = attn_bwd_v4_kernel<64, DROP>;
-      static bool attr_set = false;
-      if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k4, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-          (void)hipGetLastError();
-          set_error("attention_bwd_v4: cannot reserve 160 KiB of LDS");
-          return MDT_ERR_LAUNCH;
-        }
-        attr_set = true;
-      }
-      const int n_t = (cap + 15) / 16;
-      // long rows (one workgroup per CU by LDS): the persistent form; MDT_ATTN_ONEPASS=4 keeps v4 there
-      if (n_t > 8 && op != 4 && rows_img * 8 <= 4 * 512 && n_t <= 16) {
-        auto k5 = attn_bwd_v5_kernel<64, DROP>;
-        static bool attr5 = false;
-        if (!attr5) {
-          if (hipFuncSetAttribute((const void*)k5, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("attention_bwd_v5: cannot reserve 160 KiB of LDS");
-            return MDT_ERR_LAUNCH;
-          }
-          attr5 = true;
-        }
-        static int cus = 0;
-        if (!cus) {
-          int dev = 0;
-          hipDeviceProp_t prop;
-          if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-          if (cus <= 0) cus = 256;
-        }
-        const int64_t n_items = (int64_t)p.f.H * p.f.nseq;
-        const int grid = (int)(n_items < cus ? n_items : cus);
-        hipLaunchKernelGGL(k5, dim3(grid), 512, lds4, st, p, rows_img, ldq, (int)n_items);
-        return check_launch("attention_bwd_v5");
-      }
-      const int waves = n_t <= 4 ? 4 : n_t <= 8 ? 8 : 16;
-      if (rows_img * 8 > 2 * waves * 64 || n_t > waves) {      // two 16-byte chunks per thread and image, one key tile per wave
-        set_error("attention_bwd_v4: %d image rows for %d waves", rows_img, waves);
-        return MDT_ERR_UNSUPPORTED;
-      }
-      // rows of at most 96 tokens (three query-tile pairs): delta summed in the kernel from P and dP (MDT_ATTN_EXACT_DELTA=0: from the bf16 output)
-      if (n_t <= 2 * V4_EXACT_PAIRS && switches().attn_exact_delta) {
-        auto k4x = attn_bwd_v4x_kernel<64, DROP>;
-        static bool attr_x = false;
-        if (!attr_x) {
-          if (hipFuncSetAttribute((const void*)k4x, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("attention_bwd_v4x: cannot reserve 160 KiB of LDS");
-            return MDT_ERR_LAUNCH;
-          }
-          attr_x = true;
-        }
-        hipLaunchKernelGGL(k4x, dim3(p.f.H, p.f.nseq), waves * 64, lds4, st, p, rows_img, ldq);
-        return check_launch("attention_bwd_v4x");
-      }
-      hipLaunchKernelGGL(k4, dim3(p.f.H, p.f.nseq), waves * 64, lds4, st, p, rows_img, ldq);
-      return check_launch("attention_bwd_v4");
+    const int n_t = (cap + 15) / 16;
+    if (r == AttnRoute::v5) {
+      const int64_t n_items = (int64_t)p.f.H * p.f.nseq;
+      const int cus = device_cus();
+      return launch_route<attn_bwd_v5_kernel<64, DROP>>("v5", dim3((unsigned)(n_items < cus ? n_items : cus)), 512, lds4, st, p,
+                                                        rows_img, ldq, (int)n_items);
     }
-    if (s_pad <= 128 && !switches().attn_no_occ4) {
-      hipLaunchKernelGGL((attn_bwd_v3_occ4_kernel<64, DROP>), dim3(p.f.H, p.f.nseq), 256, lds, st, p, s_pad);
-      return check_launch("attention_bwd_v3_occ4");
-    }
-    // long sequences (ViT: 13 tiles): LDS allows two workgroups per CU; 8 waves each in the 128-register build
-    // = 4 waves per SIMD instead of 2
-    if (s_pad > 128 && !switches().attn_no_w8) {      // in-call A/B at the ViT shape: +0.7 % on the step
-      hipLaunchKernelGGL((attn_bwd_v3_occ4_kernel<64, DROP>), dim3(p.f.H, p.f.nseq), 512, lds, st, p, s_pad);
-      return check_launch("attention_bwd_v3_w8");
-    }
+    const int waves = n_t <= 4 ? 4 : n_t <= 8 ? 8 : 16;          // two 16-byte chunks per thread and image, one key tile per wave
+    if (r == AttnRoute::v4x) return launch_route<attn_bwd_v4x_kernel<64, DROP>>("v4x", grid, waves * 64, lds4, st, p, rows_img, ldq);
+    return launch_route<attn_bwd_v4_kernel<64, DROP>>("v4", grid, waves * 64, lds4, st, p, rows_img, ldq);
   }
-  hipLaunchKernelGGL(kern, dim3(p.f.H, p.f.nseq), 256, lds, st, p, s_pad);
-  return check_launch("attention_bwd_v3");
 }
 
-int attention_v3_bwd_dispatch(hipStream_t st, const AttnParams& p) {
+int attention_v3_bwd_dispatch(hipStream_t st, const AttnParams& p, AttnRoute r) {
   const bool s = p.f.attn_bias != nullptr, d = p.f.drop_p > 0.f;
-  if (s && d) return launch_v3<true, true>(st, p);
-  if (s) return launch_v3<true, false>(st, p);
-  if (d) return launch_v3<false, true>(st, p);
-  return launch_v3<false, false>(st, p);
+  if (s && d) return launch_v3<true, true>(st, p, r);
+  if (s) return launch_v3<true, false>(st, p, r);
+  if (d) return launch_v3<false, true>(st, p, r);
+  return launch_v3<false, false>(st, p, r);
 }
 
 template <int NT, bool STRUCT, bool DROP, bool BWD>
@@ -1540,24 +1521,13 @@ static int launch_v2(hipStream_t st, const AttnParams& p) {
   const int nhist = (STRUCT && BWD) ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
   const size_t lds = (size_t)2 * S_PAD * V2_LD * 2 + (size_t)(BWD ? 3 : 1) * S_PAD * 4 + (size_t)nhist * 4 + (BWD ? 0 : 16);   // forward: + the staging's spare chunk
   if constexpr (BWD && NT > 7) {
-    // the whole-row backward runs out of registers past 112 keys; attention.hip routes those to the chunked v3
+    // the whole-row backward runs out of registers past 112 keys; attn_bwd_route sends those to the v3 family
     set_error("attention_v2: backward supports S <= 112 (got %d)", p.f.S);
     return MDT_ERR_UNSUPPORTED;
   } else {
     constexpr int NWF = (NT >= 13 && !STRUCT) ? 8 : 4;     // forward: 8 waves for the long (ViT) rows, 4 waves per SIMD
-    const void* kern;
-    if constexpr (BWD) kern = (const void*)attn_bwd_v2_kernel<64, NT, STRUCT, DROP>;
-    else kern = (const void*)attn_fwd_v2_kernel<64, NT, STRUCT, DROP, NWF>;
-    if (lds > 64 * 1024) {
-      if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("attention_v2: cannot reserve %zu bytes of LDS", lds);
-        return MDT_ERR_LAUNCH;
-      }
-    }
-    if constexpr (BWD) hipLaunchKernelGGL((attn_bwd_v2_kernel<64, NT, STRUCT, DROP>), dim3(p.f.H, p.f.nseq), 256, lds, st, p);
-    else hipLaunchKernelGGL((attn_fwd_v2_kernel<64, NT, STRUCT, DROP, NWF>), dim3(p.f.H, p.f.nseq), NWF * 64, lds, st, p);
-    return check_launch(BWD ? "attention_bwd_v2" : "attention_fwd_v2");
+    if constexpr (BWD) return launch_route<attn_bwd_v2_kernel<64, NT, STRUCT, DROP>>("v2", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
+    else return launch_route<attn_fwd_v2_kernel<64, NT, STRUCT, DROP, NWF>>("v2", dim3(p.f.H, p.f.nseq), NWF * 64, lds, st, p);
   }
 }
 

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
+
 #include "../../include/mdt_hip.h"
 
 namespace mdt {
@@ -36,30 +38,50 @@ void set_error(const char* fmt, ...);
   } while (0)
 int check_launch(const char* what);
 
+// Routes: the kernel a GEMM / attention-backward launch takes (gemm.hip plan_gemm, attention_v2.hip attn_bwd_route).
+// MDT_GEMM_ROUTE / MDT_ATTN_BWD name one to force it; mdt_last_route() reports the route of the last launch.
+enum class GemmRoute { none, generic, tile128, tile256x128, pp256, pp256p, w4p, w4s };
+inline constexpr const char* GEMM_ROUTE_NAMES[] = {"", "generic", "tile128", "tile256x128", "pp256", "pp256p", "w4p", "w4s"};
+enum class AttnRoute { none, v1, v2, v3, v4, v4x, v5, long_ };
+inline constexpr const char* ATTN_ROUTE_NAMES[] = {"", "v1", "v2", "v3", "v4", "v4x", "v5", "long"};
+inline const char* route_name(GemmRoute r) { return GEMM_ROUTE_NAMES[(int)r]; }
+inline const char* route_name(AttnRoute r) { return ATTN_ROUTE_NAMES[(int)r]; }
+
 // Environment switches (tuning / diagnostics; production runs set none of them).  Read ONCE, at the first launch that
 // asks — the hot path makes no getenv calls — and again only when the host calls mdt_reload_env() (tests, A/B tools).
+// A forced route runs where its preconditions hold for the call; elsewhere the default route runs.
 struct Switches {
-  int gemm_pp_dist;          // MDT_GEMM_PP_DIST   (default 4)
-  int gemm_persist;          // MDT_GEMM_PERSIST   (default 1: persistent tile walk for K loops of at least 16 steps; 0: never; 2: for every K >= 128 — stress runs)
+  GemmRoute gemm_route;      // MDT_GEMM_ROUTE     (none: the default route) generic | tile128 | tile256x128 | pp256 | pp256p | w4p | w4s
   bool gemm_dynamic;         // MDT_GEMM_DYNAMIC   (default 0): dynamic tile queue, needs mdt_gemm_set_tile_queue
-  int gemm_group;            // MDT_GEMM_GROUP     (-1: unset)
   bool gemm_stamp;           // MDT_GEMM_STAMP
-  bool gemm_no_spec;         // MDT_GEMM_NO_SPEC
   int gemm_diag;             // MDT_GEMM_DIAG      (0: none)
-  char gemm_tile[16];        // MDT_GEMM_TILE      ("" unset)
-  bool gemm_no_pp;           // MDT_GEMM_NO_PP
   int gemm_f8w;              // MDT_GEMM_F8W       (default 1: 8-bit GEMMs on the 16x16x128 block-MFMA kernel where it has an instantiation; 0: the 8-wave kernel)
-  int gemm_w4;               // MDT_GEMM_W4        (default 2: the 4-wave persistent kernel where it is measured faster; 0: never; 1: every persistent launch)
-  bool attn_v1;              // MDT_ATTN_V1
-  char attn_bwd[8];          // MDT_ATTN_BWD       ("" unset)
-  bool attn_no_occ4;         // MDT_ATTN_NO_OCC4
-  bool attn_no_w8;           // MDT_ATTN_NO_W8
-  bool attn_exact_delta;     // MDT_ATTN_EXACT_DELTA (default 1: one-pass backward of rows <= 96 tokens sums delta = sum P o dP itself; 0: rowsum(dO o O) from the bf16 output)
-  int attn_onepass;          // MDT_ATTN_ONEPASS   (0: two-pass backward kernels only; default: one-pass wherever its dS image fits LDS)
+  AttnRoute attn_bwd;        // MDT_ATTN_BWD       (none: the default kernel) v1 | v2 | v3 | v4 | v4x | v5 — bf16 backward, head_dim 64
   bool ln_generic;           // MDT_LN_GENERIC     (default 0; 1: bf16 rows of 768 take the generic LayerNorm backward kernel — tests, A/B runs)
   int ln_bwd_wgs;            // MDT_LN_BWD_WGS     (workgroups a LayerNorm backward launch aims for; tuning)
 };
 const Switches& switches();
+int device_cus();            // compute units of the current device (cached; 256 if the query fails)
+
+// Launch of a route's kernel: raises Kern's dynamic-LDS limit first when the launch needs more than 64 KiB and more than was
+// raised for Kern before, checks the launch (errors name the route) and records the route for mdt_last_route().
+void set_last_route(const char* route);
+template <auto Kern, typename... Args>
+int launch_route(const char* route, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  static std::atomic<size_t> raised{64 * 1024};
+  if (lds > raised.load(std::memory_order_relaxed)) {
+    if (hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+      (void)hipGetLastError();
+      set_error("%s: cannot reserve %zu bytes of LDS", route, lds);
+      return MDT_ERR_LAUNCH;
+    }
+    raised.store(lds, std::memory_order_relaxed);
+  }
+  hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+  if (int e = check_launch(route)) return e;
+  set_last_route(route);
+  return MDT_OK;
+}
 
 // ---------------------------------------------------------------- scalar conversions
 template <typename T> __device__ __forceinline__ float to_f32(T v);

@@ -523,7 +523,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp256p(GemmParams p) {
   };
   auto issue_step = [&](const Desc& d, int hs, int buf) {
     char* st = smem + buf * PP_STAGE;
-    stage_step<A_KM, BM, 8, MDT_GEMM_A_AUX>(d.rsA, lda_b, (int64_t)hs * 32, d.a_col0, st, wave, lane);
+    stage_step<A_KM, BM, 8>(d.rsA, lda_b, (int64_t)hs * 32, d.a_col0, st, wave, lane);
     stage_step<B_KM, BN, 8>(d.rsB, ldb_b, (int64_t)hs * 32, d.b_col0, st + A_BYTES, wave, lane);
   };
   auto wait_pieces = [&](int halves) {
@@ -694,7 +694,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp256p(GemmParams p) {
   }
 }
 
-constexpr int W4_PEND_ROWS = MDT_W4_PEND_ROWS;          // row tiles (of a wave's eight) whose outputs wait in registers
+constexpr int W4_PEND_ROWS = EPI_PEND_ROWS;            // row tiles (of a wave's eight) whose outputs wait in registers
 constexpr int W4_NPEND = 4 * W4_PEND_ROWS;              // ... = pending 16-byte vectors per lane, one leaves per step
 constexpr int W4_NEXPL = W4_NPEND + 2;                  // explicit steps of a tile (compile-time vmcnt budget and pending index)
 // operations a wave issues in step s of a tile (8 LDS-DMA pieces + the pending store); steps before the tile: 8
@@ -783,7 +783,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   auto issue_piece = [&](const Desc& d, int sa, int sb, int buf, int q) __attribute__((always_inline)) {
     char* st = smem + buf * PP_STAGE;
     const int piece = wave + 4 * (q & 3);
-    if (q < 4) w4_dma<MDT_GEMM_A_AUX>(d.rsA, st + piece * 1024, voffA[q & 3], sa);
+    if (q < 4) w4_dma(d.rsA, st + piece * 1024, voffA[q & 3], sa);
     else w4_dma(d.rsB, st + A_BYTES + piece * 1024, voffB[q & 3], sb);
   };
   auto issue_step = [&](const Desc& d, int hs, int buf) {
@@ -805,17 +805,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int v_next = v + (int)gridDim.x < nvt ? v + (int)gridDim.x : -1;
   Desc cur = make_desc(v);
   bool has_next = v_next >= 0;
-#ifdef MDT_W4_STAMPS
-  // diagnostic build (-DMDT_W4_STAMPS, MDT_GEMM_STAMP=1): shader-clock stamps of every step of tiles 4 and 5 of workgroup 9,
-  // of the loop's end, the epilogue's end and the end of the fragment prime — same report as the 8-wave kernel's
-  const unsigned long long w4_t0c = __builtin_amdgcn_s_memtime(), w4_t0r = __builtin_amdgcn_s_memrealtime();
-  int tile_no = 0, n_tiles_done = 0;
-#define W4_STAMP(slot_)                                                                                         \
-  if (p.stamps && tid == 0 && blockIdx.x == 9 && (tile_no == 4 || tile_no == 5) && nhs <= 100)                \
-    p.stamps[4 * (size_t)gridDim.x + (tile_no - 4) * (nhs + 3) + (slot_)] = __builtin_amdgcn_s_memtime()
-#else
-#define W4_STAMP(slot_) (void)0
-#endif
   // after the last tile the ring keeps turning on a descriptor of zero records (every load reads as 0, nobody reads the
   // stage): the loop needs no "nothing left to request" case and the vmcnt arithmetic is the same in every step
   auto null_desc = [&](Desc d) {
@@ -922,7 +911,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const bool same = tgt < nhs;
     Desc d = nxt;
     if (same) d = cur;
-    W4_STAMP(hs);
     step(cs_c, first_c, nw_c, st_c, ld_c, d, same ? tgt : tgt - nhs);
   };
 #define W4_N(n_) std::integral_constant<int, n_> {}
@@ -974,7 +962,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       epi_prefetch<4, EPK, true>(p, lane, cur.m0 + wr * 128, cur.n0 + wc * 128, epf, &eb);
     }
     run_step(C1{}, F_{}, W4_N(16), W4_N(-1), F_{}, nhs - 1);
-    W4_STAMP(nhs);
 #if defined(__HIP_DEVICE_COMPILE__)
     // The MFMAs are asm statements: the compiler does not know that their results need wait states before a VALU may read
     // them, and it is free to hoist an accumulator read of the epilogue up to right behind the last MFMA that wrote it
@@ -986,7 +973,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       asm volatile("" : "+a"(acc[i][0]), "+a"(acc[i][1]), "+a"(acc[i][2]), "+a"(acc[i][3]), "+a"(acc[i][4]), "+a"(acc[i][5]), "+a"(acc[i][6]), "+a"(acc[i][7]));
 #endif
     direct_epilogue<4, EPK, PEND, PEND>(p, acc, lane, cur.m0 + wr * 128, cur.n0 + wc * 128, pend, &epf, &eb);
-    W4_STAMP(nhs + 1);
     {                                             // fragments of the next tile's first step (its stage landed a step ago)
       const char* t0 = smem + b_prime * PP_STAGE;
 #pragma unroll
@@ -996,10 +982,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    W4_STAMP(nhs + 2);
-#ifdef MDT_W4_STAMPS
-    ++tile_no; ++n_tiles_done;
-#endif
     if constexpr (PEND) {
       if (has_next) rsP = eb.rsC;
       else {                                      // nothing follows: the pending half leaves now
@@ -1017,16 +999,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     has_next = v_next >= 0;
     nxt = has_next ? make_desc(v_next) : null_desc(cur);
   }
-#ifdef MDT_W4_STAMPS
-  if (p.stamps && tid == 0) {
-    unsigned long long* o = p.stamps + 4 * (size_t)blockIdx.x;
-    o[0] = __builtin_amdgcn_s_memtime() - w4_t0c;
-    o[1] = __builtin_amdgcn_s_memrealtime() - w4_t0r;
-    o[2] = (unsigned long long)n_tiles_done * (nhs / 2);
-    o[3] = w4_t0r;
-  }
-#endif
-#undef W4_STAMP
 #undef W4_N
 #undef W4_MF
 }
@@ -1132,53 +1104,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(int64_t rows, int64_t co
     if (c0 + i < cols && r0 + tx < rows) d[(c0 + i) * ldd + r0 + tx] = from_f32<TD>(tile[tx][i]);
 }
 
-template <typename TIn, typename TOut>
-static int launch_generic(hipStream_t st, const GemmParams& p, int ta, int tb) {
-  dim3 grid((unsigned)((p.N + 63) / 64), (unsigned)((p.M + 63) / 64), (unsigned)p.split_k);
-  if (!ta && !tb) hipLaunchKernelGGL((gemm_generic_kernel<TIn, TOut, false, false>), grid, 256, 0, st, p);
-  else if (!ta && tb) hipLaunchKernelGGL((gemm_generic_kernel<TIn, TOut, false, true>), grid, 256, 0, st, p);
-  else if (ta && !tb) hipLaunchKernelGGL((gemm_generic_kernel<TIn, TOut, true, false>), grid, 256, 0, st, p);
-  else hipLaunchKernelGGL((gemm_generic_kernel<TIn, TOut, true, true>), grid, 256, 0, st, p);
-  return check_launch("gemm_generic");
-}
-
-template <typename TOut>
-static int launch_tile128(hipStream_t st, const GemmParams& p, int ta, int tb) {
-  dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)p.split_k);
-  const size_t lds = 4 * T_TILE_BYTES;
-  if (!ta && !tb) hipLaunchKernelGGL((gemm_bf16_tile128<TOut, false, false>), grid, 256, lds, st, p);
-  else if (!ta && tb) hipLaunchKernelGGL((gemm_bf16_tile128<TOut, false, true>), grid, 256, lds, st, p);
-  else if (ta && !tb) hipLaunchKernelGGL((gemm_bf16_tile128<TOut, true, false>), grid, 256, lds, st, p);
-  else hipLaunchKernelGGL((gemm_bf16_tile128<TOut, true, true>), grid, 256, lds, st, p);
-  return check_launch("gemm_bf16_tile128");
-}
-
-template <typename TOut, int BN, int WM, int WN, int NSTAGE>
-static int launch_tile256(hipStream_t st, const GemmParams& p, int ta, int tb) {
-  dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)p.split_k);
-  const size_t lds = (size_t)NSTAGE * (256 + BN) * 128;
-#define L256(A_, B_)                                                                                         \
-  {                                                                                                          \
-    auto kern = gemm_bf16_tile256<TOut, A_, B_, BN, WM, WN, NSTAGE>;                                         \
-    static bool attr_set = false;                                                                            \
-    if (!attr_set) {                                                                                         \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        (void)hipGetLastError();                                                                             \
-        set_error("gemm_bf16_tile256: cannot reserve %zu bytes of LDS", lds);                                \
-        return MDT_ERR_LAUNCH;                                                                               \
-      }                                                                                                      \
-      attr_set = true;                                                                                       \
-    }                                                                                                        \
-    hipLaunchKernelGGL(kern, grid, 512, lds, st, p);                                                         \
-  }
-  if (!ta && !tb) L256(false, false)
-  else if (!ta && tb) L256(false, true)
-  else if (ta && !tb) L256(true, false)
-  else L256(true, true)
-#undef L256
-  return check_launch("gemm_bf16_tile256");
-}
-
 // MDT_GEMM_STAMP=1: every ping-pong launch is followed by a device sync and one stderr line with the median
 // in-kernel clock and shader cycles per 64-deep K-tile of its main loop (tools/kbench.py; never in production).
 static void report_stamps(unsigned long long* dev, size_t nwg, const GemmParams& p) {
@@ -1210,311 +1135,221 @@ static void report_stamps(unsigned long long* dev, size_t nwg, const GemmParams&
 }
 
 static int num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-    n &= ~7;                      // the XCD-aware tile order needs a grid that is a multiple of the 8 XCDs
-    if (n < 8) n = 8;
-  }
-  return n;
+  const int n = device_cus() & ~7;   // the XCD-aware tile order needs a grid that is a multiple of the 8 XCDs
+  return n < 8 ? 8 : n;
 }
 
 // dynamic tile queue: caller-owned device memory (mdt_gemm_set_tile_queue), 16 ints per set
 static int* g_tile_queues = nullptr;
 static int g_tile_queue_sets = 0;
 
-template <typename TOut>
-static int launch_pp256(hipStream_t st, const GemmParams& p_in, int ta, int tb) {
-  GemmParams p = p_in;
-  dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)p.split_k);
+// Tile order of the 256 x 256 kernels.  Row-major (group_n = tiles_n) unless B is too wide for an XCD's 4-MiB L2 and splits
+// evenly in two halves that do fit: then XCDs 0-3 sweep the left half of the columns and XCDs 4-7 the right half, over the
+// same rows at the same time — each XCD keeps its half of B resident and the second reader of an A panel finds it in the
+// Infinity Cache.  In-call A/B at N = 3072, K = 768: +3-4 % (fabric reads 2.7 -> ~1.3 GB).  Finer groups lose (A then
+// streams from HBM once per group); odd splits (N = 2304) lose.  b_panel: bytes of one 256-column panel of B.
+static int xcd_group_n(int tiles_m, int tiles_n, double b_panel, int n_cus) {
+  if (tiles_n % 2 == 0 && b_panel * tiles_n > 3.5e6 && b_panel * (tiles_n / 2) <= 2.5e6 && (double)tiles_m * tiles_n >= 4.0 * n_cus)
+    return tiles_n / 2;
+  return tiles_n;
+}
+
+struct GemmPlan {
+  GemmRoute route;
+  int tiles_m, tiles_n, split_k, group_n;
+  int64_t k_chunk;
+  dim3 grid;
+  bool strip_asum;   // MDT_EPI_ASUM rides on pp256 / w4s only: elsewhere the column-sum kernel sums the stored A first
+};
+
+// The route of one validated mdt_gemm call (split_k >= 1 as asked).  No HIP calls.  Defaults, in this order:
+//   generic      where the tile kernels' contract fails (fp32 operands, unaligned or partial tiles, 32-bit buffer offsets);
+//   pp family    256 x 256 tiles whenever they still fill most of the chip (one block per CU): L2 -> LDS traffic per flop is
+//                half that of 128 x 128, measured 10-40 % faster at every C2 shape (profiles/);
+//   tile256x128  at least 256 such tiles; tile128 otherwise (2 blocks per CU).
+// Within the pp family: the persistent walk (one workgroup per CU) for bf16 output, no split-K, more tiles than CUs and at
+// least 16 32-deep steps per tile — there the 4-wave w4p for k-contiguous A, light epilogues and K >= 640, else the 8-wave
+// pp256p; without the walk the 4-wave split-K w4s for fp32 atomic weight gradients with slabs of at least 256, else pp256.
+// MDT_GEMM_ROUTE=<route> takes that route wherever its preconditions (ok() below) hold; forcing pp256p also walks tiles of
+// only PP_DIST steps (K >= 128: stress runs, tools/gemm_stress.py).
+static GemmPlan plan_gemm(const GemmParams& p, int dtype, int out_dtype, int ta, int tb, int n_cus) {
   const Switches& sw = switches();
-  const int dist = sw.gemm_pp_dist;
-  const int nhs_total = 2 * (int)((p.K + T_BK - 1) / T_BK);
+  const int64_t M = p.M, N = p.N, K = p.K;
+  const int epi = p.epilogue;
+  // tile-kernel contract: bf16 operands; output dims tiled along a contiguous axis are whole tiles (B rows beyond N would
+  // alias the next tensor); 16-byte aligned rows; 32-bit buffer offsets: one 128-row panel (k-contiguous) or one k-chunk
+  // (k-major) stays < 4 GiB; vector epilogue: 16-byte accesses on C (atomics are scalar) / bias / residual / aux
+  bool fast = dtype == MDT_BF16 && K > 0 && (ta ? M % T_BM == 0 : K % T_BK == 0) && (tb ? N % T_BN == 0 : K % T_BK == 0) &&
+              N % T_BN == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && ((uintptr_t)p.A | (uintptr_t)p.B) % 16 == 0 &&
+              p.lda * 2 * 128 < (1ll << 31) && p.ldb * 2 * 128 < (1ll << 31);
+  const int ov = out_dtype == MDT_F32 ? 4 : 8;
+  if (!(epi & MDT_EPI_ATOMIC) && (p.ldc % ov || ((uintptr_t)p.C & 15))) fast = false;
+  if ((epi & MDT_EPI_BIAS) && ((uintptr_t)p.bias & 15)) fast = false;
+  if ((epi & MDT_EPI_RESIDUAL) && (p.ldr % 8 || ((uintptr_t)p.residual & 15))) fast = false;
+  if (p.aux && (p.ldaux % 8 || ((uintptr_t)p.aux & 15))) fast = false;
+  const int64_t chunk = ((K + p.split_k - 1) / p.split_k + T_BK - 1) / T_BK * T_BK;
+  if (fast && (ta || tb) && chunk * (ta ? p.lda : p.ldb) * 2 >= (1ll << 32)) fast = false;
+  const int split = fast ? (int)((K + chunk - 1) / chunk) : 1;
+
+  const bool m256 = ta ? M % 256 == 0 : true;
+  const int tm256 = (int)((M + 255) / 256), tn256 = (int)(N / 256);
+  const bool pp = fast && m256 && N % 256 == 0;
+  const int nhs = 2 * (int)((K + T_BK - 1) / T_BK);                     // 32-deep steps of a tile
   // The persistent walk pays where a tile is short against its launch / first-fetch / drain (K = 768: 24 steps) and needs at
   // least PP_DIST steps per tile.  Launches with fewer than 16 steps per tile (K < 512) — none in a training step — take one
   // workgroup per tile: a tile boundary then never falls inside the prefetch window of the previous one (round 3 saw an
   // intermittent wrong result on ONE box at K = 256 with two tiles per workgroup that no other device and no jittered stress
-  // run reproduces, DESIGN.md "pp256p"; MDT_GEMM_PERSIST=2 — tools/gemm_stress.py — keeps the short-K walk reachable).
-  const int min_steps = sw.gemm_persist >= 2 ? 4 : 16;
-  const bool persist = sw.gemm_persist != 0 && sizeof(TOut) == 2 && p.split_k == 1 && nhs_total >= min_steps && (int)grid.x > num_cus();
-  if (persist) grid.x = (unsigned)num_cus();
-  p.tile_queue = nullptr;
-  if (persist && nhs_total >= W4_NEXPL + 2) {
-    // MDT_GEMM_W4: 0 off; 1 every persistent launch; 2 the launches it is measured faster on (k-contiguous operands, light
-    // epilogues: plain, bias, residual, bias + dropout + residual, saved derivative + column sums — not the GELU form, not k-major operands)
-    const int w4 = sw.gemm_w4;
-    const int e_ = p.epilogue & ((1 << 22) - 1);   // start-skew diagnostics (bits 22+) keep the compile-time epilogues
-    const bool light = e_ == 0 || e_ == MDT_EPI_BIAS || e_ == MDT_EPI_RESIDUAL || e_ == (MDT_EPI_BIAS | MDT_EPI_RESIDUAL | MDT_EPI_DROPOUT) ||
-                       e_ == (MDT_EPI_MULAUX | MDT_EPI_COLSUM);
-    const bool use_w4 = (w4 == 1 || (w4 == 2 && !ta && light && !sw.gemm_no_spec)) && !(sw.gemm_dynamic && g_tile_queues) &&
-                        !(p.epilogue & (1 << 24));      // the jittered stress build exists for the 8-wave kernel
-    if (use_w4) {
-#ifdef MDT_W4_STAMPS
-      if (sw.gemm_stamp) {
-        if (hipMalloc(&p.stamps, (size_t)grid.x * 32 + 256 * 8) != hipSuccess) { (void)hipGetLastError(); p.stamps = nullptr; }
-        else (void)hipMemsetAsync(p.stamps, 0, (size_t)grid.x * 32 + 256 * 8, st);
-      }
-#endif
-      p.group_n = p.tiles_n;
-      {
-        const double b_panel = 256.0 * (double)p.k_chunk * 2.0;
-        if (p.tiles_n % 2 == 0 && b_panel * p.tiles_n > 3.5e6 && b_panel * (p.tiles_n / 2) <= 2.5e6 && (double)p.tiles_m * p.tiles_n >= 4.0 * num_cus())
-          p.group_n = p.tiles_n / 2;
-      }
-      if (sw.gemm_group >= 1) p.group_n = sw.gemm_group < p.tiles_n ? sw.gemm_group : p.tiles_n;   // MDT_GEMM_GROUP: A/B runs
-      const size_t lds = (size_t)5 * PP_STAGE;
-#define LW4(A_, B_, E_)                                                                                      \
-  {                                                                                                          \
-    auto kern = gemm_bf16_w4p<A_, B_, E_>;                                                                   \
-    static bool attr_set = false;                                                                            \
-    if (!attr_set) {                                                                                         \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        (void)hipGetLastError();                                                                             \
-        set_error("gemm_bf16_w4p: cannot reserve %zu bytes of LDS", lds);                                    \
-        return MDT_ERR_LAUNCH;                                                                               \
-      }                                                                                                      \
-      attr_set = true;                                                                                       \
-    }                                                                                                        \
-    hipLaunchKernelGGL(kern, grid, 256, lds, st, p);                                                         \
-  }
-      constexpr int E_BIAS = MDT_EPI_BIAS, E_DENSE = MDT_EPI_BIAS | MDT_EPI_RESIDUAL | MDT_EPI_DROPOUT,
-                    E_FC1 = MDT_EPI_BIAS | MDT_EPI_GELU | MDT_EPI_AUX_GRAD, E_RES = MDT_EPI_RESIDUAL,
-                    E_DFC2 = MDT_EPI_MULAUX | MDT_EPI_COLSUM;
-      const int e = sw.gemm_no_spec ? -2 : (p.epilogue & ((1 << 22) - 1));
-      if (!ta && !tb) {
-        if (e == E_BIAS) LW4(false, false, E_BIAS)
-        else if (e == E_DENSE) LW4(false, false, E_DENSE)
-        else if (e == E_FC1 && p.aux) LW4(false, false, E_FC1)
-        else if (e == 0) LW4(false, false, 0)
-        else if (e == E_RES) LW4(false, false, E_RES)
-        else if (e == E_DFC2) LW4(false, false, E_DFC2)
-        else LW4(false, false, -1)
-      } else if (!ta && tb) {
-        if (e == 0) LW4(false, true, 0)
-        else if (e == E_RES) LW4(false, true, E_RES)
-        else if (e == E_DFC2) LW4(false, true, E_DFC2)
-        else LW4(false, true, -1)
-      } else if (ta && !tb) LW4(true, false, -1)
-      else LW4(true, true, -1)
-#undef LW4
-#ifdef MDT_W4_STAMPS
-      if (p.stamps) { report_stamps(p.stamps, grid.x, p); (void)hipFree(p.stamps); }
-#endif
-      return check_launch("gemm_bf16_w4p");
+  // run reproduces, DESIGN.md "pp256p"; forcing pp256p keeps the short-K walk reachable).
+  auto persist = [&](int min_steps) {
+    return pp && out_dtype == MDT_BF16 && split == 1 && nhs >= min_steps && tm256 * tn256 > n_cus;
+  };
+  const bool queue = sw.gemm_dynamic && g_tile_queues;
+  auto ok = [&](GemmRoute r) {
+    switch (r) {
+      case GemmRoute::generic: return true;
+      case GemmRoute::tile128: return fast;
+      case GemmRoute::tile256x128: return fast && m256;
+      case GemmRoute::pp256: return pp;
+      case GemmRoute::pp256p: return persist(4);
+      case GemmRoute::w4p:           // (the jittered stress build, MDT_GEMM_DIAG=16, exists for the 8-wave kernel only)
+        return persist(16) && nhs >= W4_NEXPL + 2 && !queue && !(epi & (1 << 24));
+      case GemmRoute::w4s:           // fp32-accumulating split-K launches with at least four 64-deep K-tiles per slab
+        return pp && out_dtype == MDT_F32 && !sw.gemm_stamp && (epi & MDT_EPI_ATOMIC) &&
+               !(epi & ((1 << 20) - 1) & ~(MDT_EPI_ATOMIC | MDT_EPI_ASUM)) && chunk >= 256 && K - (int64_t)(split - 1) * chunk >= 256;
+      default: return false;
     }
+  };
+  GemmRoute r;
+  const int64_t t256 = (int64_t)tm256 * (N / 128) * split;
+  if (!fast) r = GemmRoute::generic;
+  else if (pp && t256 / 2 >= 200) {
+    // w4p where it is measured faster: k-contiguous A, light epilogues (plain, bias, residual, bias + dropout + residual,
+    // saved derivative + column sums — not the GELU form); start-skew diagnostics (bits 22+) keep the compile-time epilogues
+    const int e = epi & ((1 << 22) - 1);
+    const bool light = e == 0 || e == MDT_EPI_BIAS || e == MDT_EPI_RESIDUAL || e == (MDT_EPI_BIAS | MDT_EPI_RESIDUAL | MDT_EPI_DROPOUT) ||
+                       e == (MDT_EPI_MULAUX | MDT_EPI_COLSUM);
+    if (persist(16)) r = ok(GemmRoute::w4p) && !ta && light ? GemmRoute::w4p : GemmRoute::pp256p;
+    else r = ok(GemmRoute::w4s) ? GemmRoute::w4s : GemmRoute::pp256;
+  } else if (m256 && t256 >= 256) r = GemmRoute::tile256x128;
+  else r = GemmRoute::tile128;
+  if (sw.gemm_route != GemmRoute::none && ok(sw.gemm_route)) r = sw.gemm_route;
+
+  GemmPlan pl{};
+  pl.route = r;
+  pl.group_n = 1 << 30;              // row-major
+  pl.strip_asum = r != GemmRoute::pp256 && r != GemmRoute::w4s;
+  if (r == GemmRoute::generic) {
+    const int64_t c16 = ((K + p.split_k - 1) / p.split_k + 15) / 16 * 16;
+    pl.k_chunk = c16 < 16 ? 16 : c16;
+    pl.split_k = K > 0 ? (int)((K + pl.k_chunk - 1) / pl.k_chunk) : 1;
+    pl.grid = dim3((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64), (unsigned)pl.split_k);
+    return pl;
   }
-  if (persist) {
-    // MDT_GEMM_DYNAMIC=1: dynamic tile queue instead of the static round-robin walk (in-call A/B on an otherwise idle
-    // chip: static is 1.5 % faster — two more barriers per tile, and raided tiles leave their XCD's L2; the queue is
-    // there for a node where other kernels — RCCL — hold compute units for long, see ddp.py).  The queue sets live in a
-    // CALLER-OWNED, zero-initialised device buffer (mdt_gemm_set_tile_queue; the library allocates nothing): they are
-    // used in turn, each put back to zero by the last workgroup of the launch that used it (launches of the two branch
-    // streams run concurrently, at most a few dozen launches apart in issue order).  Without a registered buffer the
-    // static walk is used.
-    static unsigned turn = 0;
-    if (sw.gemm_dynamic && g_tile_queues) p.tile_queue = g_tile_queues + 16 * (turn++ % (unsigned)g_tile_queue_sets);
-  }
-  {
-    // Tile order.  Row-major (group_n = tiles_n) unless B is too wide for an XCD's 4-MiB L2 and splits evenly in
-    // two halves that do fit: then XCDs 0-3 sweep the left half of the columns and XCDs 4-7 the right half, over the
-    // same rows at the same time — each XCD keeps its half of B resident and the second reader of an A panel finds
-    // it in the Infinity Cache.  In-call A/B at N = 3072, K = 768: +3-4 % (fabric reads 2.7 -> ~1.3 GB).  Finer
-    // groups lose (A then streams from HBM once per group); odd splits (N = 2304) lose.  MDT_GEMM_GROUP=n forces a
-    // width, MDT_GEMM_GROUP=0 asks the fabric-read model below.
-    p.group_n = p.tiles_n;
-    {
-      const double b_panel = 256.0 * (double)p.k_chunk * 2.0;
-      if (p.split_k == 1 && p.tiles_n % 2 == 0 && b_panel * p.tiles_n > 3.5e6 && b_panel * (p.tiles_n / 2) <= 2.5e6 &&
-          (double)p.tiles_m * p.tiles_n >= 4.0 * num_cus())
-        p.group_n = p.tiles_n / 2;
-      // split-K (weight gradients): an XCD takes a contiguous run of a slab's tiles, so the operand whose panels are
-      // the run's slow index is fetched once and the other once per XCD touching the slab — let the larger operand
-      // (more panels) be the slow index: column-major when dW is wider than tall (fc2: 1.66 -> 1.25 x operand bytes)
-      if (p.split_k > 1 && p.tiles_n > p.tiles_m) p.group_n = 1;
-    }
-    if (sw.gemm_group >= 0) {
-      int v = sw.gemm_group;
-      if (v == 0) {
-        const double a_bytes = (double)p.M * (double)p.k_chunk * 2.0, b_bytes = (double)p.N * (double)p.k_chunk * 2.0;
-        const double rounds = (double)p.tiles_m * p.tiles_n / 256.0;
-        double best_cost = 1e300;
-        for (int G = 1; G <= p.tiles_n; ++G) {
-          const int ngroups = (p.tiles_n + G - 1) / G;
-          const bool fits = (double)G * 256.0 * (double)p.k_chunk * 2.0 <= 1.6e6;
-          const double cost = a_bytes * ngroups + (fits ? b_bytes * 8.0 : b_bytes * 8.0 * (rounds > 1.0 ? rounds : 1.0));
-          if (cost < best_cost * 0.999) { best_cost = cost; v = G; }
-        }
-      }
-      if (v >= 1) p.group_n = v < p.tiles_n ? v : p.tiles_n;
-    }
-  }
-  // fp32-accumulating launches (the split-K weight gradients) with at least four 64-deep K-tiles per slab: the 4-wave kernel
-  // of gemm_wgrad.hip (MDT_GEMM_W4=0 keeps the 8-wave ping-pong kernel below)
-  if (!persist && sizeof(TOut) == 4 && sw.gemm_w4 != 0 && !sw.gemm_stamp && (p.epilogue & MDT_EPI_ATOMIC) &&
-      !(p.epilogue & ((1 << 20) - 1) & ~(MDT_EPI_ATOMIC | MDT_EPI_ASUM)) && p.k_chunk >= 256 && (p.K - (int64_t)(p.split_k - 1) * p.k_chunk) >= 256)
-    return launch_w4s(st, p, ta, tb);
-  const bool stamp = sw.gemm_stamp;
-  const size_t nwg = (size_t)grid.x * grid.z;
-  if (stamp) {
-    if (hipMalloc(&p.stamps, nwg * 32 + 256 * 8) != hipSuccess) { (void)hipGetLastError(); p.stamps = nullptr; }
-    else (void)hipMemsetAsync(p.stamps, 0, nwg * 32 + 256 * 8, st);
-  }
-  // prefetch distance in 32-k steps.  In-call A/B at the C2 shapes: 4 (five stages = all of LDS) beats 2 and 3 by
-  // 1-3 % per GEMM, 0.6 % on the whole step — the fill is throughput- rather than latency-bound
-  if (persist) {
-    const size_t lds = (size_t)pp_nb(4) * PP_STAGE;
-#define LPS(A_, B_, E_)                                                                                      \
-  {                                                                                                          \
-    auto kern = gemm_bf16_pp256p<A_, B_, 4, E_>;                                                             \
-    static bool attr_set = false;                                                                            \
-    if (!attr_set) {                                                                                         \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        (void)hipGetLastError();                                                                             \
-        set_error("gemm_bf16_pp256p: cannot reserve %zu bytes of LDS", lds);                                 \
-        return MDT_ERR_LAUNCH;                                                                               \
-      }                                                                                                      \
-      attr_set = true;                                                                                       \
-    }                                                                                                        \
-    hipLaunchKernelGGL(kern, grid, 512, lds, st, p);                                                         \
-  }
-    // the epilogue flag sets of a training step get instantiations with the flags folded in (see direct_epilogue);
-    // anything else — eval-mode combinations, diagnostics — runs the runtime-flag kernel
-    constexpr int E_BIAS = MDT_EPI_BIAS, E_DENSE = MDT_EPI_BIAS | MDT_EPI_RESIDUAL | MDT_EPI_DROPOUT,
-                  E_FC1 = MDT_EPI_BIAS | MDT_EPI_GELU | MDT_EPI_AUX_GRAD /* HF blocks have no activation dropout */, E_RES = MDT_EPI_RESIDUAL,
-                  E_DFC2 = MDT_EPI_MULAUX | MDT_EPI_COLSUM;
-    const int e = sw.gemm_no_spec ? -2 : (p.epilogue & ((1 << 22) - 1));
-    if (p.epilogue & (1 << 24)) {          // MDT_GEMM_DIAG=16: the jittered stress build of the same source (tools/gemm_stress.py)
-#define LPJ(A_, B_, E_)                                                                                      \
-  {                                                                                                          \
-    auto kern = gemm_bf16_pp256p<A_, B_, 4, E_, 0, true>;                                                    \
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-      (void)hipGetLastError();                                                                               \
-      set_error("gemm_bf16_pp256p (jitter): cannot reserve %zu bytes of LDS", lds);                          \
-      return MDT_ERR_LAUNCH;                                                                                 \
-    }                                                                                                        \
-    hipLaunchKernelGGL(kern, grid, 512, lds, st, p);                                                         \
-  }
-      if (!ta && !tb && e == E_FC1 && p.aux) LPJ(false, false, E_FC1)
-      else if (!ta && !tb && e == E_DENSE) LPJ(false, false, E_DENSE)
-      else if (!ta && !tb) LPJ(false, false, -1)
-      else if (!ta && tb && e == E_DFC2) LPJ(false, true, E_DFC2)
-      else if (!ta && tb) LPJ(false, true, -1)
-      else if (ta && !tb) LPJ(true, false, -1)
-      else LPJ(true, true, -1)
-#undef LPJ
-      return check_launch("gemm_bf16_pp256p (jitter)");
-    }
-    if (!ta && !tb) {
-      if (e == E_BIAS) LPS(false, false, E_BIAS)
-      else if (e == E_DENSE) LPS(false, false, E_DENSE)
-      else if (e == E_FC1 && p.aux) LPS(false, false, E_FC1)
-      else if (e == 0) LPS(false, false, 0)                 // input gradients against a transposed weight copy
-      else if (e == E_RES) LPS(false, false, E_RES)
-      else if (e == E_DFC2) LPS(false, false, E_DFC2)
-      else LPS(false, false, -1)
-    } else if (!ta && tb) {
-      if (e == 0) LPS(false, true, 0)
-      else if (e == E_RES) LPS(false, true, E_RES)
-      else if (e == E_DFC2) LPS(false, true, E_DFC2)
-      else LPS(false, true, -1)
-    } else if (ta && !tb) LPS(true, false, -1)
-    else LPS(true, true, -1)
-#undef LPS
-    if (p.stamps) {
-      report_stamps(p.stamps, nwg, p);
-      (void)hipFree(p.stamps);
-    }
-    return check_launch("gemm_bf16_pp256p");
-  }
-#define LPP(A_, B_, D_)                                                                                      \
-  {                                                                                                          \
-    const size_t lds = (size_t)pp_nb(D_) * PP_STAGE;                                                         \
-    auto kern = gemm_bf16_pp256<TOut, A_, B_, D_>;                                                           \
-    static bool attr_set = false;                                                                            \
-    if (!attr_set) {                                                                                         \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        (void)hipGetLastError();                                                                             \
-        set_error("gemm_bf16_pp256: cannot reserve %zu bytes of LDS", lds);                                  \
-        return MDT_ERR_LAUNCH;                                                                               \
-      }                                                                                                      \
-      attr_set = true;                                                                                       \
-    }                                                                                                        \
-    hipLaunchKernelGGL(kern, grid, 512, lds, st, p);                                                         \
-  }
-#define LPPD(D_)                          \
-  {                                       \
-    if (!ta && !tb) LPP(false, false, D_) \
-    else if (!ta && tb) LPP(false, true, D_) \
-    else if (ta && !tb) LPP(true, false, D_) \
-    else LPP(true, true, D_)              \
-  }
-  if (dist >= 4) LPPD(4)
-  else if (dist == 3) LPPD(3)
-  else LPPD(2)
-#undef LPPD
-#undef LPP
-  if (p.stamps) {
-    report_stamps(p.stamps, nwg, p);
-    (void)hipFree(p.stamps);
-  }
-  return check_launch("gemm_bf16_pp256");
+  pl.k_chunk = chunk;
+  pl.split_k = split;
+  pl.tiles_m = r == GemmRoute::tile128 ? (int)((M + T_BM - 1) / T_BM) : tm256;
+  pl.tiles_n = r == GemmRoute::tile128 || r == GemmRoute::tile256x128 ? (int)(N / T_BN) : tn256;
+  pl.grid = dim3((unsigned)(pl.tiles_m * pl.tiles_n), 1, (unsigned)split);
+  if (r == GemmRoute::tile128 || r == GemmRoute::tile256x128) return pl;
+  // split-K (weight gradients): an XCD takes a contiguous run of a slab's tiles, so the operand whose panels are the run's
+  // slow index is fetched once and the other once per XCD touching the slab — let the larger operand (more panels) be the
+  // slow index: column-major when dW is wider than tall (fc2: 1.66 -> 1.25 x operand bytes)
+  pl.group_n = split > 1 ? (pl.tiles_n > pl.tiles_m ? 1 : pl.tiles_n) : xcd_group_n(pl.tiles_m, pl.tiles_n, 256.0 * (double)chunk * 2.0, n_cus);
+  if (r == GemmRoute::pp256p || r == GemmRoute::w4p) pl.grid.x = (unsigned)n_cus;
+  return pl;
 }
 
-template int launch_pp256<float>(hipStream_t, const GemmParams&, int, int);
-template int launch_pp256<bf16_t>(hipStream_t, const GemmParams&, int, int);
+// The epilogue flag sets of a training step get instantiations of the 256 x 256 kernels with the flags folded in (see
+// direct_epilogue), per operand layout; anything else — eval-mode combinations, diagnostics — runs the runtime-flag kernel.
+// Calls f(std::integral_constant<int, EPK>) with EPK the compile-time flag set, or -1.
+constexpr int E_BIAS = MDT_EPI_BIAS, E_DENSE = MDT_EPI_BIAS | MDT_EPI_RESIDUAL | MDT_EPI_DROPOUT,
+              E_FC1 = MDT_EPI_BIAS | MDT_EPI_GELU | MDT_EPI_AUX_GRAD /* HF blocks have no activation dropout */, E_RES = MDT_EPI_RESIDUAL,
+              E_DFC2 = MDT_EPI_MULAUX | MDT_EPI_COLSUM;
+template <int E> using EpiK = std::integral_constant<int, E>;
+template <bool A_KM, bool B_KM, class F>
+static int with_epilogue(const GemmParams& p, F&& f) {
+  const int e = p.epilogue & ((1 << 22) - 1);   // start-skew diagnostics (bits 22+) keep the compile-time epilogues
+  if constexpr (!A_KM && !B_KM) {
+    if (e == E_BIAS) return f(EpiK<E_BIAS>{});
+    if (e == E_DENSE) return f(EpiK<E_DENSE>{});
+    if (e == E_FC1 && p.aux) return f(EpiK<E_FC1>{});
+  }
+  if constexpr (!A_KM) {            // NN and NT (input gradients against a transposed weight copy)
+    if (e == 0) return f(EpiK<0>{});
+    if (e == E_RES) return f(EpiK<E_RES>{});
+    if (e == E_DFC2) return f(EpiK<E_DFC2>{});
+  }
+  return f(EpiK<-1>{});
+}
+
+template <class F>
+static int with_layout(int ta, int tb, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  if (!ta && !tb) return f(N{}, N{});
+  if (!ta) return f(N{}, T{});
+  if (!tb) return f(T{}, N{});
+  return f(T{}, T{});
+}
+
+template <typename TIn, typename TOut>
+static int launch_generic(hipStream_t st, const GemmParams& p, dim3 grid, int ta, int tb) {
+  return with_layout(ta, tb, [&](auto a_t, auto b_t) {
+    return launch_route<gemm_generic_kernel<TIn, TOut, decltype(a_t)::value, decltype(b_t)::value>>("generic", grid, 256, 0, st, p);
+  });
+}
+
+template <typename TOut>
+static int launch_gemm(hipStream_t st, const GemmParams& p, GemmRoute r, dim3 grid, int ta, int tb) {
+  const size_t pp_lds = (size_t)pp_nb(4) * PP_STAGE;   // prefetch distance 4 (five stages = all of LDS): in-call A/B at the C2
+                                                       // shapes beats 2 and 3 by 1-3 % per GEMM — the fill is throughput-bound
+  const char* name = route_name(r);
+  return with_layout(ta, tb, [&](auto a_km, auto b_km) -> int {
+    constexpr bool A = decltype(a_km)::value, B = decltype(b_km)::value;
+    switch (r) {
+      case GemmRoute::tile128: return launch_route<gemm_bf16_tile128<TOut, A, B>>(name, grid, 256, 4 * T_TILE_BYTES, st, p);
+      case GemmRoute::tile256x128:
+        return launch_route<gemm_bf16_tile256<TOut, A, B, 128, 4, 2, 3>>(name, grid, 512, (size_t)3 * (256 + 128) * 128, st, p);
+      case GemmRoute::pp256: return launch_route<gemm_bf16_pp256<TOut, A, B, 4>>(name, grid, 512, pp_lds, st, p);
+      case GemmRoute::w4p:
+        return with_epilogue<A, B>(p, [&](auto ek) {
+          return launch_route<gemm_bf16_w4p<A, B, decltype(ek)::value>>(name, grid, 256, (size_t)5 * PP_STAGE, st, p);
+        });
+      case GemmRoute::pp256p:
+        return with_epilogue<A, B>(p, [&](auto ek) {
+          constexpr int EPK = decltype(ek)::value;
+          if (!(p.epilogue & (1 << 24))) return launch_route<gemm_bf16_pp256p<A, B, 4, EPK>>(name, grid, 512, pp_lds, st, p);
+          // MDT_GEMM_DIAG=16: the jittered stress build of the same source (tools/gemm_stress.py), for the fc1 / dense forward and
+          // the fc2 input-gradient flag sets
+          constexpr int EJ = (!B && (EPK == E_FC1 || EPK == E_DENSE)) || (B && EPK == E_DFC2) ? EPK : -1;
+          return launch_route<gemm_bf16_pp256p<A, B, 4, EJ, 0, true>>(name, grid, 512, pp_lds, st, p);
+        });
+      default: set_error("mdt_gemm: route %s has no launch here", name); return MDT_ERR_ARG;
+    }
+  });
+}
 
 // 8-bit operands: persistent kernel only (large problems), NN layout only.
 template <int F8>
-static int launch_pp256p_f8(hipStream_t st, const GemmParams& p_in) {
-  GemmParams p = p_in;
+static int launch_pp256p_f8(hipStream_t st, const GemmParams& p) {
   // one workgroup per CU walks the tiles; a problem with fewer tiles than CUs gets one workgroup per tile (the tile
   // order stays a bijection for any tile count, the walk just ends after the first tile)
   const int nvt = p.tiles_m * p.tiles_n;
-  dim3 grid((unsigned)(nvt < num_cus() ? nvt : num_cus()), 1, 1);
-  p.tile_queue = nullptr;
-  p.stamps = nullptr;
-  p.group_n = p.tiles_n;
-  {
-    const double b_panel = 256.0 * (double)p.K;      // bytes: one byte per element
-    if (p.tiles_n % 2 == 0 && b_panel * p.tiles_n > 3.5e6 && b_panel * (p.tiles_n / 2) <= 2.5e6 &&
-        (double)p.tiles_m * p.tiles_n >= 4.0 * num_cus())
-      p.group_n = p.tiles_n / 2;
-  }
+  const dim3 grid((unsigned)(nvt < num_cus() ? nvt : num_cus()), 1, 1);
   const size_t lds = (size_t)pp_nb(4) * PP_STAGE;
-#define LF8(E_)                                                                                              \
-  {                                                                                                          \
-    auto kern = gemm_bf16_pp256p<false, false, 4, E_, F8>;                                                   \
-    static bool attr_set = false;                                                                            \
-    if (!attr_set) {                                                                                         \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        (void)hipGetLastError();                                                                             \
-        set_error("gemm_fp8: cannot reserve %zu bytes of LDS", lds);                                         \
-        return MDT_ERR_LAUNCH;                                                                               \
-      }                                                                                                      \
-      attr_set = true;                                                                                       \
-    }                                                                                                        \
-    hipLaunchKernelGGL(kern, grid, 512, lds, st, p);                                                         \
-  }
-  constexpr int E_BIAS = MDT_EPI_BIAS, E_DENSE = MDT_EPI_BIAS | MDT_EPI_RESIDUAL | MDT_EPI_DROPOUT,
-                E_FC1 = MDT_EPI_BIAS | MDT_EPI_GELU | MDT_EPI_AUX_GRAD, E_RES = MDT_EPI_RESIDUAL,
-                E_DFC2 = MDT_EPI_MULAUX | MDT_EPI_COLSUM;
   const int e = p.epilogue;
+#define LF8(E_) return launch_route<gemm_bf16_pp256p<false, false, 4, E_, F8>>("f8_pp256p", grid, 512, lds, st, p)
   if constexpr (F8 == 1) {          // forward: activations e4m3
-    if (e == E_BIAS) LF8(E_BIAS)
-    else if (e == E_DENSE) LF8(E_DENSE)
-    else if (e == E_FC1 && p.aux) LF8(E_FC1)
-    else LF8(-1)
+    if (e == E_BIAS) LF8(E_BIAS);
+    if (e == E_DENSE) LF8(E_DENSE);
+    if (e == E_FC1 && p.aux) LF8(E_FC1);
   } else {                          // input gradients: dY e5m2 against the transposed e4m3 weight copy
-    if (e == 0) LF8(0)
-    else if (e == E_RES) LF8(E_RES)
-    else if (e == E_DFC2) LF8(E_DFC2)
-    else LF8(-1)
+    if (e == 0) LF8(0);
+    if (e == E_RES) LF8(E_RES);
+    if (e == E_DFC2) LF8(E_DFC2);
   }
+  LF8(-1);
 #undef LF8
-  return check_launch("gemm_fp8_pp256p");
 }
 
 }  // namespace mdt
@@ -1552,85 +1387,52 @@ extern "C" int mdt_gemm(void* stream, int dtype, int out_dtype, int trans_a, int
   p.stamps = nullptr;
   p.tile_queue = nullptr;
   p.alpha_dev = p.alpha_dev2 = nullptr;
-  p.group_n = 1 << 30;   // row-major unless launch_pp256 decides otherwise
   p.epilogue |= switches().gemm_diag << 20;   // diagnostics: 1 skip stores, 2 sc1 stores, 16 jittered stress build of the 8-wave persistent kernel, 4 skewed starts within an XCD, 8 every tile loads tile (0,0)'s panels, 64 XCDs skewed against each other, 256 row-panel groups skewed inside an XCD (4-wave kernel)
   MDT_CHECK_ARG(!(epilogue & MDT_EPI_COLSUM) || (colsum && split_k == 1), "mdt_gemm: MDT_EPI_COLSUM needs a colsum buffer and split_k == 1");
   // (MDT_EPI_ATOMIC already implies an fp32 C; said again because the kernels compute the sums in their fp32-output form only)
   MDT_CHECK_ARG(!(epilogue & MDT_EPI_ASUM) || (colsum && trans_a && (epilogue & MDT_EPI_ATOMIC) && !(epilogue & MDT_EPI_COLSUM) && dtype == MDT_BF16 && out_dtype == MDT_F32),
                 "mdt_gemm: MDT_EPI_ASUM needs bf16 operands, an fp32 C, trans_a = 1, MDT_EPI_ATOMIC, a colsum buffer and no MDT_EPI_COLSUM");
-  // tile128 contract: bf16, output dims that are tiled along a contiguous axis must be
-  // whole tiles, 16-B aligned rows.
-  // MDT_EPI_ASUM rides on the 256 x 256 ping-pong kernel only; every other path sums the stored A ([K, M]) with the
-  // column-sum kernel first and runs without the flag
-  auto strip_asum = [&]() -> int {
-    if (!(p.epilogue & MDT_EPI_ASUM)) return MDT_OK;
+  const GemmPlan pl = plan_gemm(p, dtype, out_dtype, trans_a, trans_b, num_cus());
+  p.k_chunk = pl.k_chunk; p.split_k = pl.split_k; p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.group_n = pl.group_n;
+  if (pl.strip_asum && (p.epilogue & MDT_EPI_ASUM)) {      // the row sums of the stored A ([K, M]) by the column-sum kernel
     p.epilogue &= ~MDT_EPI_ASUM;
-    return mdt_colsum(stream, dtype, K, M, A, lda, colsum, nullptr);
-  };
-  bool fast = dtype == MDT_BF16 && K > 0;
-  if (fast) {
-    const bool a_ok = trans_a ? (M % T_BM == 0) : (K % T_BK == 0);
-    const bool b_ok = trans_b ? (N % T_BN == 0) : (K % T_BK == 0);
-    const bool al = (lda % 8 == 0) && (ldb % 8 == 0) && (((uintptr_t)A | (uintptr_t)B) % 16 == 0);
-    // 32-bit buffer offsets: one 128-row panel (k-contiguous) or one k-chunk (k-major) must stay < 4 GiB
-    fast = a_ok && b_ok && al && (N % T_BN == 0 || !trans_b) && lda * 2 * 128 < (1ll << 31) && ldb * 2 * 128 < (1ll << 31);
-    if (!trans_b && N % T_BN != 0) fast = false;  // B rows beyond N would alias the next tensor
-    // vector epilogue: 16-byte accesses on C / bias / residual / aux
-    const int ov = out_dtype == MDT_F32 ? 4 : 8;
-    if (!(epilogue & MDT_EPI_ATOMIC) && (ldc % ov || ((uintptr_t)C & 15))) fast = false;   // atomics are scalar
-    if ((epilogue & MDT_EPI_BIAS) && ((uintptr_t)bias & 15)) fast = false;
-    if ((epilogue & MDT_EPI_RESIDUAL) && (ldr % 8 || ((uintptr_t)residual & 15))) fast = false;
-    if (aux && (ldaux % 8 || ((uintptr_t)aux & 15))) fast = false;
+    if (int e = mdt_colsum(stream, dtype, K, M, A, lda, colsum, nullptr)) return e;
   }
-  if (fast) {
-    int64_t chunk = ((K + split_k - 1) / split_k + T_BK - 1) / T_BK * T_BK;
-    p.k_chunk = chunk;
-    p.split_k = (int)((K + chunk - 1) / chunk);
-    p.tiles_m = (int)((M + T_BM - 1) / T_BM);
-    p.tiles_n = (int)(N / T_BN);
-    if ((trans_a || trans_b) && chunk * (trans_a ? lda : ldb) * 2 >= (1ll << 32)) fast = false;
+  switch (pl.route) {
+    case GemmRoute::generic:
+      if (dtype == MDT_F32) return launch_generic<float, float>(st, p, pl.grid, trans_a, trans_b);
+      return out_dtype == MDT_F32 ? launch_generic<bf16_t, float>(st, p, pl.grid, trans_a, trans_b)
+                                  : launch_generic<bf16_t, bf16_t>(st, p, pl.grid, trans_a, trans_b);
+    case GemmRoute::w4s: return launch_w4s(st, p, pl.grid, trans_a, trans_b);
+    case GemmRoute::pp256p:
+      // MDT_GEMM_DYNAMIC=1: dynamic tile queue instead of the static round-robin walk (in-call A/B on an otherwise idle
+      // chip: static is 1.5 % faster — two more barriers per tile, and raided tiles leave their XCD's L2; the queue is
+      // there for a node where other kernels — RCCL — hold compute units for long, see ddp.py).  The queue sets live in a
+      // CALLER-OWNED, zero-initialised device buffer (mdt_gemm_set_tile_queue; the library allocates nothing): they are
+      // used in turn, each put back to zero by the last workgroup of the launch that used it (launches of the two branch
+      // streams run concurrently, at most a few dozen launches apart in issue order).  Without a registered buffer the
+      // static walk is used.
+      if (switches().gemm_dynamic && g_tile_queues) {
+        static unsigned turn = 0;
+        p.tile_queue = g_tile_queues + 16 * (turn++ % (unsigned)g_tile_queue_sets);
+      }
+      [[fallthrough]];
+    case GemmRoute::pp256:
+      if (switches().gemm_stamp) {
+        const size_t bytes = (size_t)pl.grid.x * pl.grid.z * 32 + 256 * 8;
+        if (hipMalloc(&p.stamps, bytes) != hipSuccess) { (void)hipGetLastError(); p.stamps = nullptr; }
+        else (void)hipMemsetAsync(p.stamps, 0, bytes, st);
+      }
+      break;
+    default: break;
   }
-  if (fast) {
-    // big problems: 256-row tiles, one 8-wave block per CU; small ones keep 128x128 (2 blocks / CU)
-    const char* force = switches().gemm_tile[0] ? switches().gemm_tile : nullptr;      // "128" | "256x128" | "256x256" | "pp" (tuning / A-B runs)
-    const bool m256 = trans_a ? (M % 256 == 0) : true;
-    const int64_t t256 = ((M + 255) / 256) * (N / 128) * p.split_k;
-    const bool n256 = N % 256 == 0;
-    // 256x256 whenever it still fills most of the chip (1 block per CU): its L2 -> LDS traffic per
-    // flop is half that of 128x128 and measured 10-40 % faster at every C2 shape (profiles/)
-    bool use256x256 = m256 && n256 && t256 / 2 >= 200;
-    bool use256x128 = m256 && !use256x256 && t256 >= 256;
-    if (force) {
-      use256x256 = m256 && n256 && !strcmp(force, "256x256");
-      use256x128 = m256 && !strcmp(force, "256x128");
-    }
-    if (use256x256 || (force && m256 && n256 && !strcmp(force, "pp"))) {
-      p.tiles_m = (int)((M + 255) / 256);
-      p.tiles_n = (int)(N / 256);
-      const bool pp = force ? !strcmp(force, "pp") : !switches().gemm_no_pp;
-      if (pp) return out_dtype == MDT_F32 ? launch_pp256<float>(st, p, trans_a, trans_b)
-                                          : launch_pp256<bf16_t>(st, p, trans_a, trans_b);
-      if (int e = strip_asum()) return e;
-      return out_dtype == MDT_F32 ? launch_tile256<float, 256, 2, 4, 2>(st, p, trans_a, trans_b)
-                                  : launch_tile256<bf16_t, 256, 2, 4, 2>(st, p, trans_a, trans_b);
-    }
-    if (int e = strip_asum()) return e;
-    if (use256x128) {
-      p.tiles_m = (int)((M + 255) / 256);
-      return out_dtype == MDT_F32 ? launch_tile256<float, 128, 4, 2, 3>(st, p, trans_a, trans_b)
-                                  : launch_tile256<bf16_t, 128, 4, 2, 3>(st, p, trans_a, trans_b);
-    }
-    return out_dtype == MDT_F32 ? launch_tile128<float>(st, p, trans_a, trans_b)
-                                : launch_tile128<bf16_t>(st, p, trans_a, trans_b);
+  const int e = out_dtype == MDT_F32 ? launch_gemm<float>(st, p, pl.route, pl.grid, trans_a, trans_b)
+                                     : launch_gemm<bf16_t>(st, p, pl.route, pl.grid, trans_a, trans_b);
+  if (p.stamps) {
+    if (e == MDT_OK) report_stamps(p.stamps, (size_t)pl.grid.x * pl.grid.z, p);
+    (void)hipFree(p.stamps);
   }
-  if (int e = strip_asum()) return e;
-  int64_t chunk = ((K + split_k - 1) / split_k + 15) / 16 * 16;
-  if (chunk < 16) chunk = 16;
-  p.k_chunk = chunk;
-  p.split_k = K > 0 ? (int)((K + chunk - 1) / chunk) : 1;
-  if (dtype == MDT_F32) return launch_generic<float, float>(st, p, trans_a, trans_b);
-  return out_dtype == MDT_F32 ? launch_generic<bf16_t, float>(st, p, trans_a, trans_b)
-                              : launch_generic<bf16_t, bf16_t>(st, p, trans_a, trans_b);
+  return e;
 }
 
 extern "C" size_t mdt_gemm_tile_queue_bytes(void) { return (size_t)512 * 16 * sizeof(int); }
@@ -1687,15 +1489,11 @@ extern "C" int mdt_gemm_fp8_q8(void* stream, int a_format, int64_t M, int64_t N,
     MDT_CHECK_ARG(q8_scale && q8_amax && ld_q8 >= N, "mdt_gemm_fp8_q8: the fp8 output needs its scale, its maximum slot and rows of at least N bytes");
     p.q8_out = q8_out; p.ld_q8 = ld_q8; p.q8_fmt = q8_format; p.q8_scale = q8_scale; p.q8_amax = q8_amax;
   }
+  p.tile_queue = nullptr;
+  p.stamps = nullptr;
+  p.group_n = xcd_group_n(p.tiles_m, p.tiles_n, 256.0 * (double)K, num_cus());     // bytes: one byte per element
   if (switches().gemm_f8w) {
-    GemmParams q = p;
-    q.tile_queue = nullptr;
-    q.stamps = nullptr;
-    q.group_n = q.tiles_n;
-    const double b_panel = 256.0 * (double)K;        // bytes: one byte per element
-    if (q.tiles_n % 2 == 0 && b_panel * q.tiles_n > 3.5e6 && b_panel * (q.tiles_n / 2) <= 2.5e6 && (double)q.tiles_m * q.tiles_n >= 4.0 * num_cus())
-      q.group_n = q.tiles_n / 2;
-    const int r = launch_f8_w4((hipStream_t)stream, q, a_format, num_cus());
+    const int r = launch_f8_w4((hipStream_t)stream, p, a_format, num_cus());
     if (r != -1) return r;
   }
   // only the block-MFMA kernel writes the fp8 copy (and only for the epilogues a training step asks it for): the caller quantises the bf16 output itself

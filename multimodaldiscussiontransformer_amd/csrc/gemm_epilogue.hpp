@@ -16,7 +16,7 @@ namespace mdt {
 // per wave instruction — no LDS parking, no workgroup barrier, and no wave waits for another one.
 //
 // EPK >= 0: the epilogue flag set is a compile-time constant (the hot combinations of a training step get their own
-// kernel instantiation, see launch_pp256).  The code is then straight-line, which is what lets the vectors the
+// kernel instantiation, see with_epilogue in gemm.hip).  The code is then straight-line, which is what lets the vectors the
 // epilogue READS — saved GELU derivative, residual — be requested ahead: 8 row groups of the first column pair up
 // front, and a row group that has consumed its vector requests the one of the next column pair into the same
 // registers (32 VGPRs live).  With runtime flags (EPK = -1) every such load sits in its own branch and the compiler
@@ -25,10 +25,7 @@ namespace mdt {
 // GEMMs against 1.05-1.13 on the same shapes without).
 // PEND: the outputs of row tiles 4-7 are not stored but handed back packed (pend[(i - 4) * NJP + jp], 16 bytes per lane each):
 // the 4-wave kernel keeps them in registers and lets them leave during the next tile's first steps.
-#ifndef MDT_W4_PEND_ROWS
-#define MDT_W4_PEND_ROWS 4
-#endif
-constexpr int EPI_PEND_ROWS = MDT_W4_PEND_ROWS;          // PEND epilogues: the last EPI_PEND_ROWS row tiles are handed back, not stored
+constexpr int EPI_PEND_ROWS = 4;          // PEND epilogues: the last EPI_PEND_ROWS row tiles are handed back, not stored
 // What a compile-time epilogue reads before it can start — the bias vectors of the wave's columns and the first column pair's
 // residual / saved-derivative vectors — requested ahead (EPF: the 4-wave kernel asks for them before its last 32-k step, whose
 // free fragment registers hold them: at the epilogue they have long arrived, and the wait in front of their first use

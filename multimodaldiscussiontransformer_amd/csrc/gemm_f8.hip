@@ -317,21 +317,7 @@ int launch_f8_w4(hipStream_t st, const GemmParams& p_in, int a_format, int n_cus
   const int nvt = p.tiles_m * p.tiles_n;
   dim3 grid((unsigned)(nvt < n_cus ? nvt : n_cus), 1, 1);
   const size_t lds = (size_t)5 * PP_STAGE;
-#define LF8W(FA_, E_, X_, Q_, PR_)                                                                           \
-  {                                                                                                          \
-    auto kern = gemm_f8_w4<FA_, E_, X_, Q_, PR_>;                                                                                       \
-    static bool attr_set = false;                                                                            \
-    if (!attr_set) {                                                                                         \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        (void)hipGetLastError();                                                                             \
-        set_error("gemm_f8_w4: cannot reserve %zu bytes of LDS", lds);                                       \
-        return MDT_ERR_LAUNCH;                                                                               \
-      }                                                                                                      \
-      attr_set = true;                                                                                       \
-    }                                                                                                        \
-    hipLaunchKernelGGL(kern, grid, 256, lds, st, p);                                                         \
-    return check_launch("gemm_f8_w4");                                                                       \
-  }
+#define LF8W(FA_, E_, X_, Q_, PR_) return launch_route<gemm_f8_w4<FA_, E_, X_, Q_, PR_>>("f8_w4", grid, 256, lds, st, p);
   constexpr int E_BIAS = MDT_EPI_BIAS, E_FC1 = MDT_EPI_BIAS | MDT_EPI_GELU | MDT_EPI_AUX_GRAD, E_DFC2 = MDT_EPI_MULAUX | MDT_EPI_COLSUM,
                 E_DENSE = MDT_EPI_BIAS | MDT_EPI_RESIDUAL | MDT_EPI_DROPOUT, E_RES = MDT_EPI_RESIDUAL;
   const int e = p.epilogue;

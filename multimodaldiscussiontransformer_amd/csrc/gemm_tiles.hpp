@@ -125,11 +125,7 @@ __device__ __forceinline__ bf16x8 load_frag(const char* lds_tile, int rc_base, i
 // swizzled by swz_km(k) as in the 64-k image (conflict-free ds_read_b64_tr_b16).
 __device__ __forceinline__ int swz_h(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }
 
-// AUX: cache-policy bits of the LDS-DMA request (1 = sc0, 2 = nt, 16 = sc1); MDT_GEMM_A_AUX (build-time, experiments) sets it for
-// the A operand of the persistent forward / input-gradient kernels — the streamed activation panels, read once per column group
-#ifndef MDT_GEMM_A_AUX
-#define MDT_GEMM_A_AUX 0
-#endif
+// AUX: cache-policy bits of the LDS-DMA request (1 = sc0, 2 = nt, 16 = sc1)
 template <bool KM, int ROWS, int NW, int AUX = 0>
 __device__ __forceinline__ void stage_step(__amdgpu_buffer_rsrc_t rs, int64_t ld_bytes, int64_t k0, int col0,
                                            char* lds_tile, int wave, int lane) {
@@ -351,7 +347,7 @@ __device__ __forceinline__ void w4_dma(__amdgpu_buffer_rsrc_t rs, char* lds, uns
 
 
 // 4-wave split-K kernel for fp32-accumulating launches (weight gradients), gemm_wgrad.hip
-int launch_w4s(hipStream_t st, const GemmParams& p, int ta, int tb);
+int launch_w4s(hipStream_t st, const GemmParams& p, dim3 grid, int ta, int tb);
 // 4-wave 8-bit kernel on the 16x16x128 block MFMA, gemm_f8.hip; -1: no instantiation for this (format, epilogue, shape)
 int launch_f8_w4(hipStream_t st, const GemmParams& p, int a_format, int n_cus);
 

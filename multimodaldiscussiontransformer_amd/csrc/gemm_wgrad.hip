@@ -231,29 +231,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 }
 
-int launch_w4s(hipStream_t st, const GemmParams& p, int ta, int tb) {
-  dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)p.split_k);
+int launch_w4s(hipStream_t st, const GemmParams& p, dim3 grid, int ta, int tb) {
   const size_t lds = (size_t)5 * PP_STAGE;
-#define LW4S(A_, B_)                                                                                         \
-  {                                                                                                          \
-    auto kern = gemm_bf16_w4s<A_, B_>;                                                                       \
-    static bool attr_set = false;                                                                            \
-    if (!attr_set) {                                                                                         \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        (void)hipGetLastError();                                                                             \
-        set_error("gemm_bf16_w4s: cannot reserve %zu bytes of LDS", lds);                                    \
-        return MDT_ERR_LAUNCH;                                                                               \
-      }                                                                                                      \
-      attr_set = true;                                                                                       \
-    }                                                                                                        \
-    hipLaunchKernelGGL(kern, grid, 256, lds, st, p);                                                         \
-  }
-  if (ta && tb) LW4S(true, true)
-  else if (!ta && tb) LW4S(false, true)
-  else if (ta && !tb) LW4S(true, false)
-  else LW4S(false, false)
-#undef LW4S
-  return check_launch("gemm_bf16_w4s");
+  if (ta && tb) return launch_route<gemm_bf16_w4s<true, true>>("w4s", grid, 256, lds, st, p);
+  if (!ta && tb) return launch_route<gemm_bf16_w4s<false, true>>("w4s", grid, 256, lds, st, p);
+  if (ta && !tb) return launch_route<gemm_bf16_w4s<true, false>>("w4s", grid, 256, lds, st, p);
+  return launch_route<gemm_bf16_w4s<false, false>>("w4s", grid, 256, lds, st, p);
 }
 
 }  // namespace mdt

@@ -31,34 +31,32 @@ int check_launch(const char* what) {
   return MDT_OK;
 }
 
+static thread_local const char* g_route = "";
+void set_last_route(const char* route) { g_route = route; }
+
 static Switches g_sw;
 static bool g_sw_valid = false;
+
+// the index of the value of `var` in names[1..]; 0 when unset (or unknown: said on stderr)
+template <size_t N>
+static int pick(const char* var, const char* const (&names)[N]) {
+  const char* v = getenv(var);
+  if (!v || !*v) return 0;
+  for (size_t i = 1; i < N; ++i)
+    if (!strcmp(v, names[i])) return (int)i;
+  fprintf(stderr, "[mdt] %s=%s names no route: the default routes run\n", var, v);
+  return 0;
+}
 
 static void read_switches() {
   auto flag = [](const char* n) { return getenv(n) != nullptr; };
   auto num = [](const char* n, int dflt) { const char* v = getenv(n); return v ? atoi(v) : dflt; };
-  auto str = [](const char* n, char* dst, size_t cap) {
-    const char* v = getenv(n);
-    dst[0] = 0;
-    if (v) { strncpy(dst, v, cap - 1); dst[cap - 1] = 0; }
-  };
-  g_sw.gemm_pp_dist = num("MDT_GEMM_PP_DIST", 4);
-  g_sw.gemm_persist = num("MDT_GEMM_PERSIST", 1);
+  g_sw.gemm_route = (GemmRoute)pick("MDT_GEMM_ROUTE", GEMM_ROUTE_NAMES);
   g_sw.gemm_dynamic = num("MDT_GEMM_DYNAMIC", 0) != 0;
-  g_sw.gemm_group = num("MDT_GEMM_GROUP", -1);
   g_sw.gemm_stamp = flag("MDT_GEMM_STAMP");
-  g_sw.gemm_no_spec = flag("MDT_GEMM_NO_SPEC");
-  g_sw.attn_exact_delta = num("MDT_ATTN_EXACT_DELTA", 1) != 0;
   g_sw.gemm_diag = num("MDT_GEMM_DIAG", 0);
-  str("MDT_GEMM_TILE", g_sw.gemm_tile, sizeof(g_sw.gemm_tile));
-  g_sw.gemm_no_pp = flag("MDT_GEMM_NO_PP");
-  g_sw.gemm_w4 = num("MDT_GEMM_W4", 2);
   g_sw.gemm_f8w = num("MDT_GEMM_F8W", 1);
-  g_sw.attn_v1 = flag("MDT_ATTN_V1");
-  str("MDT_ATTN_BWD", g_sw.attn_bwd, sizeof(g_sw.attn_bwd));
-  g_sw.attn_no_occ4 = flag("MDT_ATTN_NO_OCC4");
-  g_sw.attn_no_w8 = flag("MDT_ATTN_NO_W8");
-  g_sw.attn_onepass = num("MDT_ATTN_ONEPASS", -1);
+  g_sw.attn_bwd = (AttnRoute)pick("MDT_ATTN_BWD", ATTN_ROUTE_NAMES);
   g_sw.ln_generic = flag("MDT_LN_GENERIC");
   g_sw.ln_bwd_wgs = num("MDT_LN_BWD_WGS", 2048);
   g_sw_valid = true;
@@ -69,11 +67,23 @@ const Switches& switches() {
   return g_sw;
 }
 
+int device_cus() {
+  static int n = 0;
+  if (!n) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
+    if (n <= 0) n = 256;
+  }
+  return n;
+}
+
 }  // namespace mdt
 
 extern "C" void mdt_reload_env(void) { mdt::read_switches(); }
 extern "C" int mdt_abi_version(void) { return MDT_ABI_VERSION; }
 extern "C" const char* mdt_last_error_string(void) { return mdt::g_err; }
+extern "C" const char* mdt_last_route(void) { return mdt::g_route; }
 
 // --------------------------------------------------------------------------- packer
 // (up, down) hops through the lowest common ancestor → 21-bucket spatial index

@@ -136,6 +136,10 @@ def test_attention_dropout(ops, dtype, bwd, nseq, S, H, monkeypatch):
     tol = dict(atol=2e-4, rtol=1e-4) if dtype == torch.float32 else dict(atol=0.04, rtol=3e-2)
     torch.testing.assert_close(out.float().cpu().view(nseq, S, D), oref.detach(), **tol)
     dqkv, _ = ops.attention_bwd(d2, q2, out, lse, nseq, S, H, key_mask=km.cuda(), drop_p=p, drop_seed=seed)
+    from multimodaldiscussiontransformer_amd import _lib
+    n_t = (S + 15) // 16                        # default with dropout: the v3 family's pick (v4x / v4 / v5 / v3 by key tiles)
+    family = "v3" if n_t > 13 else "v5" if n_t > 8 else "v4" if n_t > 6 else "v4x"
+    assert _lib.last_route() == (bwd or ("v1" if dtype == torch.float32 else family)), _lib.last_route()
     gtol = dict(atol=5e-4, rtol=1e-3) if dtype == torch.float32 else dict(atol=0.08, rtol=6e-2)
     torch.testing.assert_close(dqkv.float().cpu().view(nseq, S, 3 * D), qr.grad, **gtol)
 

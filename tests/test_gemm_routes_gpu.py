@@ -1,7 +1,8 @@
 """Every GEMM route x the epilogue flag sets a training step launches x the shapes where kernels break, against the fp64
 reference of tests/gemm_reference.py with per-element bounds.
 
-Routes are forced with the library's switches (MDT_GEMM_TILE / _PERSIST / _DYNAMIC / _W4); each case writes C, the saved
+Routes are forced with the library's switches (MDT_GEMM_ROUTE, MDT_GEMM_DYNAMIC) and every case asserts the route that ran
+(mdt_last_route: a forced route whose preconditions fail runs the default one); each case writes C, the saved
 aux tensor, the column sums and the row sums (MDT_EPI_ASUM) into views of larger sentinel-filled buffers whose row strides
 exceed N, and every sentinel byte must survive the call.  Operands come from the generator and scales the CPU mutant
 tests (tests/test_gemm_reference_cpu.py) prove the bounds against."""
@@ -17,30 +18,28 @@ bf16, f32 = torch.bfloat16, torch.float32
 P_DROP = 0.4
 P256_M = 86 * 256 + 37        # 87 row tiles x 3 column tiles (N = 768) = 261 tiles: the last persistent round is partial
 
-ROUTE_ENV = ("MDT_GEMM_TILE", "MDT_GEMM_NO_PP", "MDT_GEMM_PERSIST", "MDT_GEMM_DYNAMIC", "MDT_GEMM_W4")
+ROUTE_ENV = ("MDT_GEMM_ROUTE", "MDT_GEMM_DYNAMIC")
 
-# route: (switches, dtype of A / B, M, N, K, trans_a, row-stride padding of C / residual / aux)
+# route: (switches, the route that runs, dtype of A / B, M, N, K, trans_a, row-stride padding of C / residual / aux)
 ROUTES = {
-    "generic_f32": ({}, f32, 101, 70, 45, False, 3),
-    "generic_bf16": ({}, bf16, 77, 130, 100, False, 3),                     # N % 128 != 0
-    "generic_head": ({}, bf16, 300, 2, 768, False, 3),                      # the classifier head's N = 2, unaligned rows
-    "tile128": ({"MDT_GEMM_TILE": "128"}, bf16, 128 + 37, 256, 128, False, 8),
-    "tile128_m13": ({"MDT_GEMM_TILE": "128"}, bf16, 13, 256, 64, False, 8),                  # M < 16, one K tile
-    "tile128_kmajor": ({"MDT_GEMM_TILE": "128"}, bf16, 256, 256, 200, True, 8),              # partial last 64-deep k-major tile
-    "tile256x128": ({"MDT_GEMM_TILE": "256x128"}, bf16, 256 + 255, 256, 192, False, 8),
-    "tile256x256": ({"MDT_GEMM_TILE": "256x256"}, bf16, 256 + 1, 512, 128, False, 8),
-    "pp256": ({"MDT_GEMM_TILE": "pp", "MDT_GEMM_PERSIST": "0"}, bf16, 512 + 13, 512, 320, False, 8),
-    "pp256_255tiles": ({}, bf16, 85 * 256 - 1, 768, 576, False, 8),          # default choice, one tile short of persistence
-    "pp256p": ({"MDT_GEMM_TILE": "pp", "MDT_GEMM_PERSIST": "1", "MDT_GEMM_W4": "0"}, bf16, P256_M, 768, 576, False, 8),
-    "pp256p_dynamic": ({"MDT_GEMM_TILE": "pp", "MDT_GEMM_PERSIST": "1", "MDT_GEMM_DYNAMIC": "1", "MDT_GEMM_W4": "0"}, bf16,
-                       P256_M, 768, 640, False, 8),
-    "w4p": ({"MDT_GEMM_TILE": "pp", "MDT_GEMM_W4": "1"}, bf16, P256_M, 768, 640, False, 8),
+    "generic_f32": ({}, "generic", f32, 101, 70, 45, False, 3),
+    "generic_bf16": ({}, "generic", bf16, 77, 130, 100, False, 3),                     # N % 128 != 0
+    "generic_head": ({}, "generic", bf16, 300, 2, 768, False, 3),                      # the classifier head's N = 2, unaligned rows
+    "tile128": ({"MDT_GEMM_ROUTE": "tile128"}, "tile128", bf16, 128 + 37, 256, 128, False, 8),
+    "tile128_m13": ({"MDT_GEMM_ROUTE": "tile128"}, "tile128", bf16, 13, 256, 64, False, 8),             # M < 16, one K tile
+    "tile128_kmajor": ({"MDT_GEMM_ROUTE": "tile128"}, "tile128", bf16, 256, 256, 200, True, 8),         # partial last 64-deep k-major tile
+    "tile256x128": ({"MDT_GEMM_ROUTE": "tile256x128"}, "tile256x128", bf16, 256 + 255, 256, 192, False, 8),
+    "pp256": ({"MDT_GEMM_ROUTE": "pp256"}, "pp256", bf16, 512 + 13, 512, 320, False, 8),
+    "pp256_255tiles": ({}, "pp256", bf16, 85 * 256 - 1, 768, 576, False, 8),          # default choice, one tile short of persistence
+    "pp256p": ({"MDT_GEMM_ROUTE": "pp256p"}, "pp256p", bf16, P256_M, 768, 576, False, 8),
+    "pp256p_dynamic": ({"MDT_GEMM_ROUTE": "pp256p", "MDT_GEMM_DYNAMIC": "1"}, "pp256p", bf16, P256_M, 768, 640, False, 8),
+    "w4p": ({"MDT_GEMM_ROUTE": "w4p"}, "w4p", bf16, P256_M, 768, 640, False, 8),
     # the 4-wave kernel forced, but K = 576 is 18 32-deep steps, fewer than its 18 explicit steps + 2: stays on pp256p
-    "w4p_forced_8wave": ({"MDT_GEMM_TILE": "pp", "MDT_GEMM_W4": "1"}, bf16, P256_M, 768, 576, False, 8),
-    "w4p_default": ({"MDT_GEMM_W4": "2"}, bf16, P256_M, 768, 768, False, 8),
-    "splitk_pp256": ({"MDT_GEMM_TILE": "pp", "MDT_GEMM_W4": "0"}, bf16, 512, 512, 2013, True, 8),
-    "splitk_w4s": ({"MDT_GEMM_TILE": "pp", "MDT_GEMM_W4": "2"}, bf16, 512, 512, 2013, True, 8),
-    "asum_fallback": ({"MDT_GEMM_TILE": "128"}, bf16, 512, 512, 2013, True, 8),
+    "w4p_forced_8wave": ({"MDT_GEMM_ROUTE": "w4p"}, "pp256p", bf16, P256_M, 768, 576, False, 8),
+    "w4p_default": ({}, "w4p", bf16, P256_M, 768, 768, False, 8),
+    "splitk_pp256": ({"MDT_GEMM_ROUTE": "pp256"}, "pp256", bf16, 512, 512, 2013, True, 8),
+    "splitk_w4s": ({"MDT_GEMM_ROUTE": "w4s"}, "w4s", bf16, 512, 512, 2013, True, 8),
+    "asum_fallback": ({"MDT_GEMM_ROUTE": "tile128"}, "tile128", bf16, 512, 512, 2013, True, 8),
 }
 
 E = R                         # the flag constants
@@ -73,8 +72,6 @@ MATRIX = (
     + [("tile128_kmajor", "plain", bf16, None, 1), ("tile128_kmajor", "atomic", f32, None, 1)]
     + [("tile256x128", e, bf16, None, 1) for e in ("plain", "dense", "fc1", "mulaux_colsum", "accum_colsum")]
     + [("tile256x128", "accum", f32, None, 1)]
-    + [("tile256x256", e, bf16, None, 1) for e in ("plain", "bias", "gelu_aux", "dgelu_drop", "accum_colsum")]
-    + [("tile256x256", "accum_colsum", f32, None, 1)]
     + [("pp256", e, bf16, None, 1) for e in ALL] + [("pp256", e, f32, None, 1) for e in ("accum_colsum", "dgelu_drop")]
     + [("pp256_255tiles", e, bf16, None, 1) for e in ("plain", "dense")]
     + [("pp256p", e, bf16, None, 1) for e in ALL + ["fc1_nodrop"]]
@@ -111,7 +108,7 @@ def route_env(monkeypatch):
 
 def run_case(ops, route, epi, out_dtype, K_over=None, split=1, alpha=1.0, nonfinite=False, seed=0):
     """One mdt_gemm call of the matrix: (outputs, fp64 reference, guarded buffers, the reference's inputs)."""
-    _, dtype, M, N, K, ta, pad = ROUTES[route]
+    _, _, dtype, M, N, K, ta, pad = ROUTES[route]
     K = K_over or K
     flags, tb = EPIS[epi]
     dev = "cuda"
@@ -163,6 +160,7 @@ def run_case(ops, route, epi, out_dtype, K_over=None, split=1, alpha=1.0, nonfin
     ep = flags & ~(E.EPI_BIAS | E.EPI_RESIDUAL | E.EPI_DROPOUT | E.EPI_COLSUM | E.EPI_ASUM)
     ops.gemm(a, b, trans_a=ta, trans_b=tb, out=C.view, epilogue=ep, alpha=alpha, split_k=split, **kw)
     torch.cuda.synchronize()
+    assert L.last_route() == ROUTES[route][1], f"{route}-{epi}: ran {L.last_route()}, expected {ROUTES[route][1]}"
     if flags & E.EPI_GELU:
         ref_kw["aux"] = aux_out.view                  # without AUX_GRAD: activated at the stored value, as the kernel does
     ref = R.reference(a, b, trans_a=ta, trans_b=tb, alpha=alpha, epilogue=flags, split_k=split, **ref_kw)
@@ -213,13 +211,13 @@ def test_gemm_nonfinite_inputs_propagate_like_ieee(ops, route_env, route, epi):
     """A NaN in one row of op(A) and an Inf in one column of op(B): the output is non-finite exactly on that row and
     column (the reference's pattern), and the finite rest still meets its bound."""
     route_env(ROUTES[route][0])
-    od = f32 if ROUTES[route][1] == f32 else bf16
+    od = f32 if ROUTES[route][2] == f32 else bf16
     got, ref, guards, _ = run_case(ops, route, epi, od, alpha=0.75, nonfinite=True, seed=900)
     assert not bool(torch.isfinite(ref["out"][0]).all())
     _check(got, ref, guards, f"nonfinite {route}-{epi}")
 
 
-@pytest.mark.parametrize("route", ["generic_f32", "generic_bf16", "tile128", "tile256x128", "tile256x256", "pp256", "pp256p",
+@pytest.mark.parametrize("route", ["generic_f32", "generic_bf16", "tile128", "tile256x128", "pp256", "pp256p",
                                    "pp256p_dynamic", "w4p"])
 def test_gemm_colsum_with_accum_sums_this_call_only(ops, route_env, route):
     """MDT_EPI_COLSUM with MDT_EPI_ACCUM (include/mdt_hip.h): the column sums are those of this call's fp32 result r, the

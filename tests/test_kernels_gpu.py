@@ -132,7 +132,8 @@ def test_gemm_wgrad_four_wave_split_k(ops, rows, N, K, split, asum, monkeypatch)
     """gemm_bf16_w4s (gemm_wgrad.hip): the split-K weight gradient dW[N, K] = dY[rows, N]^T X[rows, K] in the 4-wave form —
     both operands k-major, fp32 atomics into what the buffer held, the bias gradient riding in tile column 0
     (MDT_EPI_ASUM), a reduction length that is not a multiple of 64 (zero-filled through the descriptor) and slabs as short
-    as four K-tiles — against fp32 torch and against the 8-wave kernel (MDT_GEMM_W4=0) on the same inputs."""
+    as four K-tiles — against fp32 torch and against the 8-wave kernel (MDT_GEMM_ROUTE=pp256) on the same inputs.  (The last
+    case's 140-row slab is too short for the 4-wave kernel: the default route runs there.)"""
     from multimodaldiscussiontransformer_amd import _lib as L
     dy, x = rnd(rows, N, seed=41, scale=0.25).bfloat16(), rnd(rows, K, seed=42, scale=0.25).bfloat16()
     w0, b0 = rnd(N, K, seed=43), rnd(N, seed=44)
@@ -140,31 +141,32 @@ def test_gemm_wgrad_four_wave_split_k(ops, rows, N, K, split, asum, monkeypatch)
     ref_w = (dev(w0).double() + dyd.double().t() @ xd.double()).float().cpu()
     ref_b = b0 + dy.float().sum(0)
     outs = {}
-    for w4 in ("2", "0"):
-        monkeypatch.setenv("MDT_GEMM_W4", w4)
+    for route in ("w4s", "pp256"):
+        monkeypatch.setenv("MDT_GEMM_ROUTE", route)
         L.reload_env()
         gw, gb = dev(w0.clone()), dev(b0.clone())
         ops.gemm(dyd, xd, trans_a=True, trans_b=True, out=gw, epilogue=ops.EPI_ATOMIC, split_k=split, asum=gb if asum else None)
         torch.cuda.synchronize()
-        outs[w4] = (gw.cpu(), gb.cpu())
-        torch.testing.assert_close(outs[w4][0], ref_w, atol=2e-2, rtol=1e-4, msg=f"dW, MDT_GEMM_W4={w4}")
+        assert L.last_route() == (route if rows != 1100 or route == "pp256" else "tile128"), L.last_route()
+        outs[route] = (gw.cpu(), gb.cpu())
+        torch.testing.assert_close(outs[route][0], ref_w, atol=2e-2, rtol=1e-4, msg=f"dW, MDT_GEMM_ROUTE={route}")
         if asum:
-            torch.testing.assert_close(outs[w4][1], ref_b, atol=2e-3 * (rows ** 0.5), rtol=1e-4, msg=f"db, MDT_GEMM_W4={w4}")
+            torch.testing.assert_close(outs[route][1], ref_b, atol=2e-3 * (rows ** 0.5), rtol=1e-4, msg=f"db, MDT_GEMM_ROUTE={route}")
         else:
-            assert torch.equal(outs[w4][1], b0)
-    monkeypatch.delenv("MDT_GEMM_W4")
+            assert torch.equal(outs[route][1], b0)
+    monkeypatch.delenv("MDT_GEMM_ROUTE")
     L.reload_env()
     # the two kernels add the same per-slab partial sums (same k order inside a slab); only the atomics' order differs
-    torch.testing.assert_close(outs["2"][0], outs["0"][0], atol=2e-3, rtol=1e-5)
+    torch.testing.assert_close(outs["w4s"][0], outs["pp256"][0], atol=2e-3, rtol=1e-5)
 
 
 @pytest.mark.parametrize("tb,kind", [(False, "bias"), (False, "dense"), (True, "plain"), (True, "res"), (False, "res"), (False, "plain"),
                                      (True, "mulaux"), (False, "mulaux"), (False, "gelu")])
 def test_gemm_four_wave_form_is_bit_identical(ops, tb, kind, monkeypatch):
-    """MDT_GEMM_W4: the 4-wave persistent kernel (gemm_bf16_w4p: one wave per SIMD, 128 x 128 per wave, hand-ordered
+    """MDT_GEMM_ROUTE=w4p: the 4-wave persistent kernel (gemm_bf16_w4p: one wave per SIMD, 128 x 128 per wave, hand-ordered
     MFMA / fragment-read / LDS-DMA stream, half of a finished tile leaving during the next tile's first steps) accumulates
-    every element in the same k order through the same epilogue code as the 8-wave kernel (MDT_GEMM_W4=0): identical
-    bits, ragged last row tile included.  =1 forces it on every persistent launch (k-major operands too)."""
+    every element in the same k order through the same epilogue code as the 8-wave kernel (MDT_GEMM_ROUTE=pp256p): identical
+    bits, ragged last row tile included — forced on any persistent launch (k-major operands, heavy epilogues too)."""
     from multimodaldiscussiontransformer_amd import _lib as L
     M, N, K = 66000 + 37, 768, 768
     bf = torch.bfloat16
@@ -183,8 +185,8 @@ def test_gemm_four_wave_form_is_bit_identical(ops, tb, kind, monkeypatch):
         kw.update(bias=dev(rnd(N, seed=33).to(bf)), epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD)
     outs, extra = [], []
     try:
-        for v in ("0", "1"):
-            monkeypatch.setenv("MDT_GEMM_W4", v)
+        for v in ("pp256p", "w4p"):
+            monkeypatch.setenv("MDT_GEMM_ROUTE", v)
             L.reload_env()
             kw2 = dict(kw)
             if kind == "mulaux":
@@ -192,9 +194,10 @@ def test_gemm_four_wave_form_is_bit_identical(ops, tb, kind, monkeypatch):
             if kind == "gelu":
                 kw2["aux"] = torch.empty(M, N, device="cuda", dtype=bf)
             outs.append(ops.gemm(a, b, **kw2).clone())
+            assert L.last_route() == v
             extra.append(kw2.get("colsum", kw2.get("aux") if kind == "gelu" else None))
     finally:
-        monkeypatch.delenv("MDT_GEMM_W4")
+        monkeypatch.delenv("MDT_GEMM_ROUTE")
         L.reload_env()
     assert torch.equal(outs[0], outs[1])
     if kind == "gelu":
@@ -220,12 +223,13 @@ def test_gemm_four_wave_form_short_and_odd_k(ops, K, monkeypatch):
         kw = dict(trans_b=tb, bias=dev(rnd(N, seed=43).to(bf)), residual=dev(rnd(M, N, seed=44).to(bf)), drop_p=0.4, drop_seed=9)
         outs = []
         try:
-            for v in ("0", "1"):
-                monkeypatch.setenv("MDT_GEMM_W4", v)
+            for v in ("pp256p", "w4p"):
+                monkeypatch.setenv("MDT_GEMM_ROUTE", v)
                 L.reload_env()
                 outs.append(ops.gemm(a, b, **kw).clone())
+                assert L.last_route() == ("pp256p" if K == 576 else v)
         finally:
-            monkeypatch.delenv("MDT_GEMM_W4")
+            monkeypatch.delenv("MDT_GEMM_ROUTE")
             L.reload_env()
         assert torch.equal(outs[0], outs[1])
         ref = a.float() @ (b.float() if tb else b.float().t())
@@ -289,16 +293,20 @@ def test_gemm_bf16_out_big_tiles(ops, M, N, K, tb, monkeypatch):
     ad, bd = dev(a), dev(b)
     ref = ad.float() @ (bd.float() if tb else bd.float().t())
     tol = dict(atol=0.06, rtol=1.5e-2)
-    for persist, dynamic in (("1", "0"), ("1", "1"), ("0", "0")):     # static walk, dynamic tile queue, one tile per workgroup
-        monkeypatch.setenv("MDT_GEMM_PERSIST", persist)
+    walk = K >= 512 and -(-M // 256) * (N // 256) > 256             # 16 32-deep steps per tile, more tiles than CUs
+    default = ("w4p" if K >= 640 else "pp256p") if walk else "pp256"
+    # static walk, dynamic tile queue, one tile per workgroup
+    for route, dynamic, want in (("", "0", default), ("", "1", "pp256p" if walk else "pp256"), ("pp256", "0", "pp256")):
+        monkeypatch.setenv("MDT_GEMM_ROUTE", route)
         monkeypatch.setenv("MDT_GEMM_DYNAMIC", dynamic)
         L.enable_dynamic_tile_queue()                                 # caller-owned queue memory (the library allocates nothing)
         L.reload_env()                                                # the switches are cached: say that they changed
         for _ in range(2):                                            # twice: the queue must come back zeroed
             out = ops.gemm(ad, bd, trans_b=bool(tb))
+            assert L.last_route() == want, (route, dynamic, L.last_route())
             torch.testing.assert_close(out.float(), ref, **tol)
     monkeypatch.setenv("MDT_GEMM_DYNAMIC", "0")
-    monkeypatch.setenv("MDT_GEMM_PERSIST", "1")
+    monkeypatch.delenv("MDT_GEMM_ROUTE")
     L.reload_env()
     cs = torch.zeros(N, dtype=torch.float32).cuda()
     out = ops.gemm(ad, bd, trans_b=bool(tb), bias=dev(bias), residual=dev(res), colsum=cs)
@@ -567,6 +575,8 @@ def test_attention(ops, dtype, nseq, S, H, hd, mode, time_major):
         d2 = dev(dout.view(nseq * S, D))
         lay = dict(seq_stride=S, pos_stride=1)
     out, lse = ops.attention_fwd(q2, nseq, S, H, scale=scale, **lay, **kw)
+    if dtype == torch.bfloat16:       # a dense bias without structural terms: the only way to the bf16 v1 kernels
+        assert L.last_route() == ("v1" if mode == "dense" else "v2"), L.last_route()
 
     def unlay(t, width):
         t = t.float().cpu()
@@ -809,6 +819,12 @@ def test_node_ce_matches_torch_cpu_half(ops, n, near_tie):
 
 
 # ----------------------------------------------------------------------------- ragged attention
+def _family(S):
+    """The backward kernel the v3 family picks for rows of up to S tokens without a structural bias (attn_bwd_route)."""
+    n_t = (S + 15) // 16
+    return "v3" if n_t > 13 else "v5" if n_t > 8 else "v4" if n_t > 6 else "v4x"
+
+
 @pytest.mark.parametrize("dtype,bwd", [(torch.float32, None), (torch.bfloat16, None), (torch.bfloat16, "v1"), (torch.bfloat16, "v2")])
 @pytest.mark.parametrize("Smax,H", [(40, 2), (104, 3), (201, 2)])
 def test_attention_ragged_sequences_equal_masked_padding(ops, dtype, bwd, Smax, H, monkeypatch):
@@ -840,6 +856,7 @@ def test_attention_ragged_sequences_equal_masked_padding(ops, dtype, bwd, Smax, 
                                 key_mask=dev(km), drop_p=p, drop_seed=seed)
     out_r, lse_r = ops.attention_fwd(dev(qkv_r), nseq, Smax, H, seq_offsets=dev(off), drop_p=p, drop_seed=seed)
     dq_r, _ = ops.attention_bwd(dev(dout_r), dev(qkv_r), out_r, lse_r, nseq, Smax, H, seq_offsets=dev(off), drop_p=p, drop_seed=seed)
+    assert L.last_route() == (bwd or ("v1" if dtype == torch.float32 else _family(Smax))), L.last_route()
     tol = dict(atol=1e-5, rtol=1e-5) if dtype == torch.float32 else dict(atol=2e-2, rtol=2e-2)
     out_p, dq_p = out_p.view(nseq, Smax, D).float().cpu(), dq_p.view(nseq, Smax, 3 * D).float().cpu()
     for s_, n in enumerate(lens):
@@ -892,6 +909,8 @@ def test_attention_backward_never_reads_what_forward_did_not_write(ops, route, S
         monkeypatch.setattr(torch, "empty_like", lambda t, *a, **k: real_empty_like(t, *a, **k).fill_(poison) if t.is_floating_point() else real_empty_like(t, *a, **k))
         dq, _ = ops.attention_bwd(dout, qkv, out_p, lse_p, nseq, Smax, H, **kw)
         monkeypatch.setattr(torch, "empty_like", real_empty_like)
+        # v1 / v2 never take q_limit: the family's default kernel runs instead
+        assert L.last_route() == (route if route == "v3" or (route and not qlim) else _family(Smax)), L.last_route()
         assert bool(torch.isfinite(dq.float()).all()), poison
         res.append(dq)
     for r in res[1:]:
@@ -929,12 +948,17 @@ def test_attention_query_limit(ops, dtype, S, H, qlim):
 
 
 # ----------------------------------------------------------------------------- one-pass backward against the two-pass kernels
+ONE_PASS = {201: "v5", 104: "v4", 65: "v4x", 224: "v3", 17: "v4x"}     # the kernel the v3 family picks for rows of S tokens
+
+
 @pytest.mark.parametrize("S,ragged,qlim,p", [(201, False, 0, 0.1), (104, False, 0, 0.3), (104, True, 0, 0.1), (201, True, 0, 0.0),
                                                (65, False, 33, 0.1), (224, False, 0, 0.1), (17, False, 0, 0.2)])
 def test_attention_backward_one_pass_equals_two_pass(ops, S, ragged, qlim, p, monkeypatch):
     """csrc/attention_v2.hip attn_bwd_v4 (dS^T parked in LDS, dQ from a transposed read) against attn_bwd_v3 (S and dP
     computed twice) on the same inputs and dropout masks: the same operands reach the same MFMAs, so the gradients may
-    differ only by the summation order of delta = rowsum(dO * O)."""
+    differ only by the summation order of delta = rowsum(dO * O).  ONE_PASS[S]: the kernel the v3 family picks for S (S = 224: the
+    one-pass dS image does not fit LDS, v3 both times)."""
+    one_pass = ONE_PASS[S]
     from multimodaldiscussiontransformer_amd import _lib as L
     nseq, H, hd = 5, 3, 64
     g = torch.Generator().manual_seed(S + 7)
@@ -955,16 +979,16 @@ def test_attention_backward_one_pass_equals_two_pass(ops, S, ragged, qlim, p, mo
     out, lse = ops.attention_fwd(qkv, nseq, S, H, **kw)
     grads = []
     try:
-        for v in ("0", "1"):
-            monkeypatch.setenv("MDT_ATTN_BWD", "v3")
-            monkeypatch.setenv("MDT_ATTN_ONEPASS", v)
+        for v in ("v3", one_pass):
+            monkeypatch.setenv("MDT_ATTN_BWD", v)
             L.reload_env()
             d, _ = ops.attention_bwd(dout, qkv, out, lse, nseq, S, H, **kw)
+            assert L.last_route() == v
             grads.append(d.float().cpu())
     finally:
         monkeypatch.delenv("MDT_ATTN_BWD")
-        monkeypatch.delenv("MDT_ATTN_ONEPASS")
         L.reload_env()
+    assert _family(S) == one_pass
     assert torch.isfinite(grads[1]).all()
     scale = grads[0].abs().max().item()
     assert (grads[0] - grads[1]).abs().max().item() <= 8e-3 * max(scale, 1.0)
@@ -1008,13 +1032,14 @@ def test_attention_backward_persistent_is_bit_identical(ops, S, ragged, qlim, p,
     out, lse = ops.attention_fwd(qkv, nseq, S, H, **kw)
     grads = []
     try:
-        for v in ("4", "1"):
-            monkeypatch.setenv("MDT_ATTN_ONEPASS", v)
+        for v in ("v4", "v5"):
+            monkeypatch.setenv("MDT_ATTN_BWD", v)
             L.reload_env()
             d, _ = ops.attention_bwd(dout, qkv, out, lse, nseq, S, H, **kw)
+            assert L.last_route() == v
             grads.append(d.float().cpu())
     finally:
-        monkeypatch.delenv("MDT_ATTN_ONEPASS")
+        monkeypatch.delenv("MDT_ATTN_BWD")
         L.reload_env()
     assert torch.isfinite(grads[1]).all()
     assert torch.equal(grads[0], grads[1])
@@ -1162,13 +1187,13 @@ def test_attention_beyond_272_tokens_key_chunked_path(ops, dtype, S, struct, p):
 
 # ----------------------------------------------------------------------------- delta = sum P o dP formed in the one-pass backward (short rows)
 @pytest.mark.parametrize("S,ragged,p", [(52, False, 0.0), (80, True, 0.0), (96, False, 0.3), (33, True, 0.1)])
-def test_attention_backward_short_rows_sum_delta_themselves(ops, S, ragged, p, monkeypatch):
+def test_attention_backward_v4x_sums_delta_itself_on_short_rows(ops, S, ragged, p, monkeypatch):
     """VERDICT r3 item 6.  Where the value rows of a sequence are nearly equal (the deep pre-fusion blocks of the C4F fixture) the
     query / key gradients are what is left after dP - delta almost cancels, and
     delta = rowsum(dO o O) taken from the forward's bf16-rounded O is off by dO . (O_bf16 - O): the same offset for every key of a
     row, a large fraction of that remnant.  attn_bwd_v4x (rows <= 96 tokens) sums delta = sum_j P_ij dP_ij itself in fp32: dQ / dK
     must sit within 2 % (relative L2) of an fp64 computation on the same bf16 inputs and masks, and the old form
-    (MDT_ATTN_EXACT_DELTA=0) must be visibly worse on the same launch — otherwise this test would not be testing anything."""
+    (attn_bwd_v4: delta from the bf16 output) must be visibly worse on the same launch — otherwise this test would not be testing anything."""
     from multimodaldiscussiontransformer_amd import _lib as L
     nseq, H, hd = 6, 2, 64
     D = H * hd
@@ -1211,15 +1236,14 @@ def test_attention_backward_short_rows_sum_delta_themselves(ops, S, ragged, p, m
         ref[r0:r0 + n] = x.grad
     res = {}
     try:
-        monkeypatch.setenv("MDT_ATTN_BWD", "v3")             # the route of the length-binned production launches: one-pass kernels
-        for exact in ("1", "0"):
-            monkeypatch.setenv("MDT_ATTN_EXACT_DELTA", exact)
+        for exact, kernel in (("1", "v4x"), ("0", "v4")):   # the one-pass kernels of the length-binned production launches
+            monkeypatch.setenv("MDT_ATTN_BWD", kernel)
             L.reload_env()
             d, _ = ops.attention_bwd(dev(dout), dev(qkv), out, lse, nseq, S, H, **kw)
+            assert L.last_route() == kernel
             d = d.double().cpu()
             res[exact] = [float((d[:, i * D:(i + 1) * D] - ref[:, i * D:(i + 1) * D]).norm() / ref[:, i * D:(i + 1) * D].norm()) for i in range(3)]
     finally:
-        monkeypatch.delenv("MDT_ATTN_EXACT_DELTA")
         monkeypatch.delenv("MDT_ATTN_BWD")
         L.reload_env()
     print(f"[S {S} ragged {ragged} p {p}] rel-L2 of dQ / dK / dV: delta summed in the kernel {res['1']}, from the bf16 output {res['0']}")

@@ -14,9 +14,9 @@ bf = torch.bfloat16
 
 def setenv(v):
     if v is None:
-        os.environ.pop("MDT_ATTN_ONEPASS", None)
+        os.environ.pop("MDT_ATTN_BWD", None)
     else:
-        os.environ["MDT_ATTN_ONEPASS"] = str(v)
+        os.environ["MDT_ATTN_BWD"] = v
     L.reload_env()
 
 
@@ -37,7 +37,7 @@ def run(name, nseq, S, lens=None, p=0.1, q_limit=0):
     dout = torch.randn(rows, H * hd, device="cuda", dtype=bf, generator=g)
     out, lse = ops.attention_fwd(qkv, nseq, S, H, drop_p=p, drop_seed=5, **kw)
     res = []
-    for v in (0, 1):
+    for v in ("v3", None):          # the two-pass kernel against the one-pass kernel the family picks
         setenv(v)
         d = ops.attention_bwd(dout, qkv, out, lse, nseq, S, H, drop_p=p, drop_seed=5, **kw)
         d = d[0] if isinstance(d, (tuple, list)) else d

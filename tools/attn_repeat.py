@@ -44,11 +44,11 @@ def main():
     # the two forms of delta against each other (same launch set): close everywhere, finite
     from multimodaldiscussiontransformer_amd import _lib
     res = {}
-    for e in ("1", "0"):
-        os.environ["MDT_ATTN_EXACT_DELTA"] = e
+    for e, kernel in (("1", "v4x"), ("0", "v4")):
+        os.environ["MDT_ATTN_BWD"] = kernel
         _lib.reload_env()
         res[e] = ops.attention_bwd(dout, qkv, out, lse, nseq, S, H, **kw)[0].float()
-    os.environ.pop("MDT_ATTN_EXACT_DELTA")
+    os.environ.pop("MDT_ATTN_BWD")
     _lib.reload_env()
     dd = (res["1"] - res["0"]).abs()
     print(f"q_limit {qlim}: delta summed in the kernel vs from the bf16 output: max |diff| {float(dd.max()):.3e} at |g| max {float(res['0'].abs().max()):.3e}, "
@@ -74,7 +74,7 @@ def main():
                 seqs = sorted({int(np.searchsorted(off.numpy(), int(r_), side="right") - 1) for r_ in idx[:2000, 0].tolist()})
                 print(f"  rep {r}: {int((diff > 0).sum())} elements differ (max {float(diff.max()):.3e}), sequences {seqs[:10]} lengths {[int(lens[s]) for s in seqs[:10]]}, "
                       f"columns {int(idx[:, 1].min())}-{int(idx[:, 1].max())}", flush=True)
-    print(f"attention backward, {nseq} ragged sequences in {len(bins)} length bins, dropout {p}, MDT_ATTN_EXACT_DELTA={os.environ.get('MDT_ATTN_EXACT_DELTA', '1')}: "
+    print(f"attention backward, {nseq} ragged sequences in {len(bins)} length bins, dropout {p}, MDT_ATTN_BWD={os.environ.get('MDT_ATTN_BWD', 'default')}: "
           f"{bad} of {reps - 1} repetitions differ, {nonfinite} with non-finite values", flush=True)
 
 

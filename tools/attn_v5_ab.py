@@ -1,4 +1,4 @@
-"""One-pass attention backward on long rows: v4 (one workgroup per item, MDT_ATTN_ONEPASS=4) against the persistent v5
+"""One-pass attention backward on long rows: v4 (one workgroup per item, MDT_ATTN_BWD=v4) against the persistent v5
 (default); gradients must be bit-identical.  GPU box only."""
 import hashlib
 import os
@@ -15,9 +15,9 @@ bf = torch.bfloat16
 
 def setenv(v):
     if v is None:
-        os.environ.pop("MDT_ATTN_ONEPASS", None)
+        os.environ.pop("MDT_ATTN_BWD", None)
     else:
-        os.environ["MDT_ATTN_ONEPASS"] = str(v)
+        os.environ["MDT_ATTN_BWD"] = v
     L.reload_env()
 
 
@@ -37,7 +37,7 @@ def run(name, nseq, S, lens=None, p=0.3, q_limit=0):
     dout = torch.randn(rows, H * hd, device="cuda", dtype=bf, generator=g)
     out, lse = ops.attention_fwd(qkv, nseq, S, H, drop_p=p, drop_seed=5, **kw)
     res = []
-    for v in (4, None):
+    for v in ("v4", "v5"):
         setenv(v)
         d = ops.attention_bwd(dout, qkv, out, lse, nseq, S, H, drop_p=p, drop_seed=5, **kw)[0]
         torch.cuda.synchronize()

@@ -1,5 +1,5 @@
 """A/B of library switches on the (shape, epilogue) combinations of a training step's GEMMs, in one process:
-    python tools/gemm_ab.py MDT_GEMM_NT=0 MDT_GEMM_NT=1 MDT_GEMM_NT=3 [--both] [--only=fc1]
+    python tools/gemm_ab.py MDT_GEMM_ROUTE=pp256p MDT_GEMM_ROUTE=w4p [--both] [--only=fc1]
 Every argument NAME=VALUE[,NAME=VALUE...] is one variant (the first is the baseline); outputs of all variants must be
 bit-identical.  GPU box only."""
 import os
@@ -66,7 +66,7 @@ def combos(M):
         out = [("NN bias N1024", x768, r(1024, 768), dict(bias=r(1024))),
                ("NN bias+res+drop N1024", x768, r(1024, 768), dict(bias=r(1024), residual=r(M, 1024), drop_p=0.4, drop_seed=3)),
                ("NN plain N1024 K3072", x3072, r(1024, 3072), dict())]
-    if "--wgrad" in sys.argv:    # the split-K weight gradients of a block (dW = dY^T X, fp32 atomics, bias gradient riding): MDT_GEMM_W4=0 | 2
+    if "--wgrad" in sys.argv:    # the split-K weight gradients of a block (dW = dY^T X, fp32 atomics, bias gradient riding): MDT_GEMM_ROUTE=pp256 | w4s
         out = []
         for (nm, dy_, x_) in [("wgrad qkv", x2304, x768), ("wgrad o", x768, x768), ("wgrad fc1", x3072, x768), ("wgrad fc2", x768, x3072)]:
             n_out, k_in = dy_.shape[1], x_.shape[1]

@@ -29,4 +29,4 @@ for (M, N, K) in [(16640, 1024, 256), (16677, 1024, 256), (16677, 1024, 768), (7
     g = torch.randn(M, N, device="cuda", dtype=bf)
     out = ops.gemm(g, b.t().contiguous().t().contiguous(), trans_b=True) if False else ops.gemm(a, bt, trans_b=True)
     e4 = (out.float() - ref).abs().max().item()
-    print(f"M={M} N={N} K={K} persist={os.environ.get('MDT_GEMM_PERSIST', '1')}: plain {e0:.3f} bias {e1:.3f} dropout {e2:.3f} gelu+auxgrad+dropout {e3:.3f} NT {e4:.3f}  (|ref| max {ref.abs().max().item():.1f})", flush=True)
+    print(f"M={M} N={N} K={K} route={os.environ.get('MDT_GEMM_ROUTE', 'default')}: plain {e0:.3f} bias {e1:.3f} dropout {e2:.3f} gelu+auxgrad+dropout {e3:.3f} NT {e4:.3f}  (|ref| max {ref.abs().max().item():.1f})", flush=True)

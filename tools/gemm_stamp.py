@@ -4,6 +4,7 @@ import os
 import sys
 
 os.environ["MDT_GEMM_STAMP"] = "1"
+os.environ.setdefault("MDT_GEMM_ROUTE", "pp256p")      # the stamps are written by the 8-wave kernels only
 import torch
 
 sys.path.insert(0, ".")

@@ -9,7 +9,7 @@ ring still turning) at a short or long K loop.  The launch is repeated `reps` ti
           the jitter walks through thousands of them per launch
 
 and every output (C, the saved derivative, the column sums) is compared BIT FOR BIT on the device against the same problem on the
-128 x 128 kernel (MDT_GEMM_TILE=128: another ring, another epilogue, same MFMA and k order).  Differences are accumulated as an
+128 x 128 kernel (MDT_GEMM_ROUTE=tile128: another ring, another epilogue, same MFMA and k order).  Differences are accumulated as an
 element mask, so a failure names its tiles.  `python tools/gemm_stress.py [reps] [--quick]`; prints one line per case and
 "STRESS_OK" / "STRESS_FAILED n".  GPU box only."""
 import os
@@ -61,13 +61,14 @@ def stress(M, N, K, form, reps):
     t = (t[0], t[1], t[1].t().contiguous(), t[3], t[4], t[5])
     new = lambda: (torch.empty(M, N, dtype=bf, device="cuda"), torch.empty(M, N, dtype=bf, device="cuda"), torch.zeros(N, dtype=torch.float32, device="cuda"))
     # reference: the 128 x 128 kernel
-    set_env(MDT_GEMM_TILE="128", MDT_GEMM_DIAG=None)
+    set_env(MDT_GEMM_ROUTE="tile128", MDT_GEMM_DIAG=None)
     ref = new()
     launch(form, t, *ref)
     torch.cuda.synchronize()
+    assert _lib.last_route() == "tile128", _lib.last_route()
     res = {}
     for mode, diag in (("plain", None), ("jitter", 16)):
-        set_env(MDT_GEMM_TILE=None, MDT_GEMM_DIAG=diag, MDT_GEMM_PERSIST=2)      # 2: the persistent walk also for K < 512
+        set_env(MDT_GEMM_ROUTE="pp256p", MDT_GEMM_DIAG=diag)      # forced: the persistent walk also for K < 512
         cur = new()
         mask = torch.zeros(M, N, dtype=torch.bool, device="cuda")
         bad = torch.zeros((), dtype=torch.int64, device="cuda")
@@ -80,6 +81,8 @@ def stress(M, N, K, form, reps):
             if uses_aux:
                 cur[1].fill_(float("nan"))
             launch(form, t, *cur)
+            if it == 0:
+                assert _lib.last_route() == "pp256p", _lib.last_route()
             d = cur[0].view(torch.int16) != ref[0].view(torch.int16)          # bit compare (NaN-safe)
             if uses_aux:
                 d |= cur[1].view(torch.int16) != ref[1].view(torch.int16)
@@ -97,7 +100,7 @@ def stress(M, N, K, form, reps):
             tiles = sorted({(int(r) // 256, int(c) // 256) for r, c in idx[:: max(1, idx.shape[0] // 4096)].tolist()})
             where = f"  {int(mask.sum())} distinct elements, tiles (row, col) {tiles[:12]}{' ...' if len(tiles) > 12 else ''}"
         res[mode] = (nb, ncs, where, us)
-    set_env(MDT_GEMM_TILE=None, MDT_GEMM_DIAG=None, MDT_GEMM_PERSIST=None)
+    set_env(MDT_GEMM_ROUTE=None, MDT_GEMM_DIAG=None)
     tiles_n = ((M + 255) // 256) * (N // 256)
     line = f"M{M:6d} N{N:5d} K{K:4d} tiles {tiles_n:4d} {form:24s}"
     fails = 0
@@ -114,7 +117,7 @@ def stress(M, N, K, form, reps):
 def discriminate(form, t, new, reps):
     """A case failed: is it this kernel or this device?  The same problem repeated on kernels that share nothing with the 8-wave
     ring — the 128 x 128 kernel against its own first result, and the vendor GEMM (torch.matmul) against its own first result."""
-    set_env(MDT_GEMM_TILE="128", MDT_GEMM_DIAG=None, MDT_GEMM_PERSIST=None)
+    set_env(MDT_GEMM_ROUTE="tile128", MDT_GEMM_DIAG=None)
     ref = new()
     launch(form, t, *ref)
     cur = new()
@@ -128,7 +131,7 @@ def discriminate(form, t, new, reps):
     for it in range(reps):
         vbad += ((a @ b.t()).view(torch.int16) != v0.view(torch.int16)).any()
     torch.cuda.synchronize()
-    set_env(MDT_GEMM_TILE=None)
+    set_env(MDT_GEMM_ROUTE=None)
     print(f"    discriminator: 128 x 128 kernel vs itself {int(bad)}/{reps} differ; vendor GEMM vs itself {int(vbad)}/{reps} differ "
           f"(both 0: the 8-wave kernel is at fault; either > 0: the DEVICE does not repeat its own results)", flush=True)
 
