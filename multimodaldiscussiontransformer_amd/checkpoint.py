@@ -226,7 +226,7 @@ def load_checkpoint(path: str, model, *, optimizer=None, reset_optimizer: bool =
         out["epoch"] = int(it.get("epoch", 1))
         out["iterations_in_epoch"] = int(it.get("iterations_in_epoch", 0) or 0)
     from . import engine
-    engine.weights_changed()          # cached transposed weight copies (engine.dgrad) are stale
+    engine.weights_changed()          # cached zero-padded weight copies (engine._k_padded) are stale
     return out
 
 

@@ -333,7 +333,7 @@ class DataParallel:
                     off += b.numel()
                 batch, size = ([t], t.numel() * t.element_size()) if t is not None else ([], 0)
         from . import engine
-        engine.weights_changed()          # written through .data: cached transposed copies (engine.dgrad) are stale
+        engine.weights_changed()          # written through .data: cached zero-padded copies (engine._k_padded) are stale
 
     def replicas_checksum(self) -> dict:
         """After a finished exchange every rank must hold the SAME bytes in its gradient arena (an all-reduce hands every

@@ -286,12 +286,10 @@ _LN_BIAS_RIDE = os.environ.get("MDT_LN_BIAS_RIDE", "1") != "0"    # 0: those sum
 
 
 # ------------------------------------------------------------------------------------------
-# input gradients against a transposed weight copy
-_NN_DGRAD = os.environ.get("MDT_NN_DGRAD", "0") == "1"     # 1: the big launches read W through a transposed copy (A/B runs)
+# A/B switches of the embedding ops, and the epoch of weights rewritten behind torch's back
 EMBED_LN_FUSED = os.environ.get("MDT_EMBED_LN_FUSED", "1") != "0"         # 0: embedding sum and its LayerNorm as two launches (A/B runs, tests)
 PATCH_K_PAD = os.environ.get("MDT_PATCH_K_PAD", "1") != "0"               # 0: ViT-L/14's K = 588 patch GEMMs stay on the any-shape kernel (A/B runs)
 PATCH_EMBED_FUSED = os.environ.get("MDT_PATCH_EMBED_FUSED", "1") != "0"   # 0: patch gather, GEMM and assembly as three launches (A/B runs, tests)
-_WT_CACHE: dict = {}
 WEIGHT_EPOCH = 0            # bumped by whoever rewrites weights behind torch's back (optim.FusedAdam.step)
 
 
@@ -300,24 +298,12 @@ def weights_changed():
     WEIGHT_EPOCH += 1
 
 
-def _transposed(w: torch.nn.Parameter) -> torch.Tensor:
-    """W^T ([in, out], contiguous) of a Linear weight [out, in], cached until the weight changes (torch-side writes bump
-    ``_version``, the fused optimiser bumps WEIGHT_EPOCH)."""
-    key = id(w)
-    ver = (w._version, WEIGHT_EPOCH, w.data_ptr())
-    hit = _WT_CACHE.get(key)
-    if hit is not None and hit[0]() is w and hit[1] == ver:
-        return hit[2]
-    wt = ops.transpose2d(w.data)
-    _WT_CACHE[key] = (weakref.ref(w), ver, wt)
-    return wt
-
-
 _KP_CACHE: dict = {}
 
 
 def _k_padded(w: torch.nn.Parameter, wmat: torch.Tensor, kp: int) -> torch.Tensor:
-    """[out, kp] copy of a weight viewed as [out, k] with zero columns behind k, cached until the weight changes."""
+    """[out, kp] copy of a weight viewed as [out, k] with zero columns behind k, cached until the weight changes (torch-side
+    writes bump ``_version``, the fused optimiser bumps WEIGHT_EPOCH)."""
     key = (id(w), kp)
     ver = (w._version, WEIGHT_EPOCH, w.data_ptr())
     hit = _KP_CACHE.get(key)
@@ -332,12 +318,21 @@ def _k_padded(w: torch.nn.Parameter, wmat: torch.Tensor, kp: int) -> torch.Tenso
 def dgrad(dy: torch.Tensor, w: torch.nn.Parameter, **kw) -> torch.Tensor:
     """dX[M, in] = dY[M, out] @ W[out, in] (+ epilogue).  W is read in place as the k-major operand: since the 4-wave
     kernel reads k-major fragments with asm ds_read_b64_tr_b16 pairs (gemm.hip, w4_frag) that form runs as fast as the
-    k-contiguous one (tools/gemm_ab.py --nn-dgrad; whole step 137.9 / 138.0 ms either way in one call).  MDT_NN_DGRAD=1
-    keeps the earlier route for A/B runs: the big launches read a transposed bf16 copy of W, cached until the weight
-    changes (2 bytes per block parameter, one transpose per optimiser step)."""
-    if _NN_DGRAD and dy.dtype == torch.bfloat16 and dy.shape[0] >= 8192 and w.shape[0] * w.shape[1] >= 1_500_000:
-        return ops.gemm(dy, _transposed(w), **kw)
+    k-contiguous one through a cached transposed copy of W (tools/gemm_ab.py --nn-dgrad; whole step 137.9 / 138.0 ms
+    either way in one call), so no copy is kept."""
     return ops.gemm(dy, w.data, trans_b=True, **kw)
+
+
+def linear(f8, x: torch.Tensor, w: torch.nn.Parameter, tag: str, *, grad=False, x8=None, q8_site=None, q8_grad=False, **kw):
+    """One 8-bit-capable GEMM of a block: x @ W^T, or with ``grad`` the input gradient x @ W.  The 8-bit kernel where ``f8``
+    (fp8.ACTIVE as the block read it; None: bf16 everywhere) takes the site (tag, id(w)), else the bf16 GEMM with the same
+    epilogue keywords ``kw``.  ``x8``: x already quantised by its producer; ``q8_site`` / ``q8_grad``: the site (and format)
+    of the GEMM that consumes the output.  → (out, (out8, inv scale) or None)"""
+    r = None if f8 is None else f8.linear(x, w, (tag, id(w)), transposed_weight=grad, grad=grad, x8=x8, q8_site=q8_site,
+                                          q8_grad=q8_grad, **kw)
+    if r is None:
+        return (dgrad(x, w, **kw) if grad else ops.gemm(x, w.data, **kw)), None
+    return r if q8_site is not None else (r, None)
 
 
 def dyd_rides(g: torch.Tensor) -> bool:
@@ -365,7 +360,9 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
                       p_hidden: float = 0.0, p_attn: float = 0.0, p_act: float = 0.0, keep_rows=None) -> Var:
     """One encoder block (post-LN: HF BertLayer / Graphormer layer; pre-LN: HF ViTLayer or
     Graphormer with --pre-layernorm).  7 GEMM-class launches + attention + 2 LayerNorms
-    forward; the adjoint below mirrors it with the residual adds folded into epilogues.
+    forward; the adjoint mirrors it with the residual adds folded into epilogues.  The attention half
+    (``attn_fwd`` / ``attn_bwd``) and the FFN half (``ffn_fwd`` / ``ffn_bwd``) are written once; the two placements
+    differ in what each LayerNorm normalises, what the FFN's residual is, and the tails of ``bwd``.
     Dropout (training): ``p_attn`` on attention probabilities (inside the attention kernel),
     ``p_hidden`` on the two dense outputs before their residual adds and ``p_act`` after GELU
     (both in the GEMM epilogue); masks are regenerated in backward from per-site seeds.  The FFN
@@ -378,10 +375,10 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     the block's GEMM work — run on the R kept rows only, and the block returns [R, D] in ``keep_rows`` order.
     Exact: the dropped rows' outputs are dead values in the reference too."""
     xd = x.data
-    kw = spec.kwargs()
     s_attn, s_o, s_act, s_f2 = (tape.next_seed() for _ in range(4))
-    akw = dict(drop_p=p_attn, drop_seed=s_attn)
+    kw = dict(spec.kwargs(), drop_p=p_attn, drop_seed=s_attn)
     R = None if keep_rows is None else int(keep_rows.numel())
+    f8 = F8.ACTIVE
 
     def gather(src):
         """rows ``keep_rows`` of src (identity when the block keeps everything)"""
@@ -391,19 +388,13 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
         ops.row_axpby(out_, R, a=src, ai=keep_rows)
         return out_
 
-    def spread(g_, rows):
-        """adjoint of gather: a [rows, D] tensor that is zero except g_ at ``keep_rows``"""
+    def spread(g_):
+        """adjoint of gather: a tensor of the block input's rows that is zero except g_ at ``keep_rows``"""
         if keep_rows is None:
             return g_
-        full = torch.zeros(rows, g_.shape[1], dtype=g_.dtype, device=g_.device)
+        full = torch.zeros(xd.shape[0], g_.shape[1], dtype=g_.dtype, device=g_.device)
         ops.row_axpby(full, R, di=keep_rows, a=g_)
         return full
-
-    f8 = F8.ACTIVE
-
-    def lin8(x_, w_, tag, **kw_):
-        """the 8-bit kernel where it pays (fp8.py) and the shape allows, else None"""
-        return None if f8 is None else f8.linear(x_, w_, (tag, id(w_)), **kw_)
 
     def ln8(x_, lw, lb, w_, tag):
         """LayerNorm whose output feeds the 8-bit GEMM (tag, w_): the fp8 copy leaves the LayerNorm kernel itself when that site
@@ -413,128 +404,103 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
             return (*ops.layernorm_fwd(x_, lw.data, lb.data, eps), None)
         return (*ops.layernorm_fwd(x_, lw.data, lb.data, eps, q8=slot[:4]), (slot[0], slot[4]))
 
+    def attn_fwd(src, src8):
+        """attention half: QKV of ``src`` (all rows), attention, output projection + residual x on the kept rows"""
+        qkv_, _ = linear(f8, src, P.qkv_w, "qkv", x8=src8, bias=P.qkv_b.data)
+        ctx_full_, lse_ = ops.attention_fwd(qkv_, spec.nseq, spec.S, spec.H, **kw)
+        ctx_, xk = gather(ctx_full_), gather(xd)
+        return qkv_, ctx_full_, lse_, ctx_, ops.gemm(ctx_, P.o_w.data, bias=P.o_b.data, residual=xk, drop_p=p_hidden, drop_seed=s_o)
+
+    def ffn_fwd(src, src8, res):
+        """FFN half: fc1 writes h and u (and, 8-bit, the quantised h that fc2 then reads), fc2 adds ``res``"""
+        u_ = torch.empty(src.shape[0], P.fc1_w.shape[0], dtype=src.dtype, device=src.device)
+        h_, h8 = linear(f8, src, P.fc1_w, "fc1", x8=src8, q8_site=("fc2", id(P.fc2_w)), bias=P.fc1_b.data, aux=u_,
+                        epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD, drop_p=p_act, drop_seed=s_act)
+        return u_, h_, linear(f8, h_, P.fc2_w, "fc2", x8=h8, bias=P.fc2_b.data, residual=res, drop_p=p_hidden, drop_seed=s_f2)[0]
+
+    # a_in / f_in: what the attention / FFN half reads; t: the attention half's output (its residual is always x)
     if not pre_ln:
-        qkv = lin8(xd, P.qkv_w, "qkv", bias=P.qkv_b.data)
-        if qkv is None:
-            qkv = ops.gemm(xd, P.qkv_w.data, bias=P.qkv_b.data)
-        ctx_full, lse = ops.attention_fwd(qkv, spec.nseq, spec.S, spec.H, **kw, **akw)
-        ctx, xk = gather(ctx_full), gather(xd)
-        t = ops.gemm(ctx, P.o_w.data, bias=P.o_b.data, residual=xk, drop_p=p_hidden, drop_seed=s_o)
-        a, m1, r1, a8 = ln8(t, P.ln1_w, P.ln1_b, P.fc1_w, "fc1")
-        u = torch.empty(a.shape[0], P.fc1_w.shape[0], dtype=a.dtype, device=a.device)
-        h, h8 = lin8(a, P.fc1_w, "fc1", x8=a8, bias=P.fc1_b.data, aux=u, epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD, drop_p=p_act, drop_seed=s_act,
-                     q8_site=("fc2", id(P.fc2_w))) or (None, None)
-        if h is None:
-            h = ops.gemm(a, P.fc1_w.data, bias=P.fc1_b.data, aux=u, epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD, drop_p=p_act, drop_seed=s_act)
-        y = lin8(h, P.fc2_w, "fc2", x8=h8, bias=P.fc2_b.data, residual=a, drop_p=p_hidden, drop_seed=s_f2)   # 8-bit when fc1 handed over the quantised h
-        if y is None:
-            y = ops.gemm(h, P.fc2_w.data, bias=P.fc2_b.data, residual=a, drop_p=p_hidden, drop_seed=s_f2)
+        a_in = xd
+        qkv, ctx_full, lse, ctx, t = attn_fwd(a_in, None)
+        f_in, m1, r1, f_in8 = ln8(t, P.ln1_w, P.ln1_b, P.fc1_w, "fc1")
+        u, h, y = ffn_fwd(f_in, f_in8, f_in)
         out, m2, r2 = ops.layernorm_fwd(y, P.ln2_w.data, P.ln2_b.data, eps)
     else:
-        n1, m1, r1, n18 = ln8(xd, P.ln1_w, P.ln1_b, P.qkv_w, "qkv")
-        qkv = lin8(n1, P.qkv_w, "qkv", x8=n18, bias=P.qkv_b.data)
-        if qkv is None:
-            qkv = ops.gemm(n1, P.qkv_w.data, bias=P.qkv_b.data)
-        ctx_full, lse = ops.attention_fwd(qkv, spec.nseq, spec.S, spec.H, **kw, **akw)
-        ctx, xk = gather(ctx_full), gather(xd)
-        hmid = ops.gemm(ctx, P.o_w.data, bias=P.o_b.data, residual=xk, drop_p=p_hidden, drop_seed=s_o)
-        n2, m2, r2, n28 = ln8(hmid, P.ln2_w, P.ln2_b, P.fc1_w, "fc1")
-        u = torch.empty(n2.shape[0], P.fc1_w.shape[0], dtype=n2.dtype, device=n2.device)
-        f, f8q = lin8(n2, P.fc1_w, "fc1", x8=n28, bias=P.fc1_b.data, aux=u, epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD, drop_p=p_act, drop_seed=s_act,
-                      q8_site=("fc2", id(P.fc2_w))) or (None, None)
-        if f is None:
-            f = ops.gemm(n2, P.fc1_w.data, bias=P.fc1_b.data, aux=u, epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD, drop_p=p_act, drop_seed=s_act)
-        out = lin8(f, P.fc2_w, "fc2", x8=f8q, bias=P.fc2_b.data, residual=hmid, drop_p=p_hidden, drop_seed=s_f2)
-        if out is None:
-            out = ops.gemm(f, P.fc2_w.data, bias=P.fc2_b.data, residual=hmid, drop_p=p_hidden, drop_seed=s_f2)
+        a_in, m1, r1, a_in8 = ln8(xd, P.ln1_w, P.ln1_b, P.qkv_w, "qkv")
+        qkv, ctx_full, lse, ctx, t = attn_fwd(a_in, a_in8)
+        f_in, m2, r2, f_in8 = ln8(t, P.ln2_w, P.ln2_b, P.fc1_w, "fc1")
+        u, h, out = ffn_fwd(f_in, f_in8, t)
     o = Var(out)
 
-    def hdrop(g, seed):
-        """gradient w.r.t. a dense output that went through hidden dropout"""
-        return ops.dropout(g, p_hidden, seed) if p_hidden > 0 else g
+    def ffn_bwd(gd, fc2_b, dres):
+        """FFN half: ``gd`` = gradient of fc2's output behind its dropout; ``fc2_b``: the bias whose gradient rides on the
+        weight-gradient GEMM (None: summed elsewhere).  → gradient of the half's input (+ ``dres``)"""
+        wgrad(tape, gd, h, P.fc2_w, fc2_b)
+        gb1 = tape.pgrad(P.fc1_b)           # fc1 bias gradient = colsum(du): fused into the GEMM epilogue
+        du, du8 = linear(f8, gd, P.fc2_w, "d_fc2", grad=True, q8_site=("d_fc1", id(P.fc1_w)), q8_grad=True, aux=u,
+                         epilogue=ops.EPI_MULAUX, colsum=None if gb1 is None else gb1.view(-1))
+        wgrad(tape, du, f_in, P.fc1_w, None)
+        return linear(f8, du, P.fc1_w, "d_fc1", grad=True, x8=du8, residual=dres)[0]     # 8-bit when the GEMM above handed over the quantised du
 
-    def attn_bwd(dctx):
-        extra = {}
-        if spec.sp_table is not None:
-            extra = dict(d_sp_table=tape.pgrad(spec.sp_table),
-                         d_virt=None if tape.pgrad(spec.virt) is None else tape.pgrad(spec.virt).view(-1))
-        want_dense = spec.dense_bias_var is not None and spec.dense_bias_var.needs_grad
-        dqkv, dbias = ops.attention_bwd(spread(dctx, xd.shape[0]), qkv, ctx_full, lse, spec.nseq, spec.S, spec.H, **kw,
-                                        want_dense_dbias=want_dense, **extra, **akw)
-        if want_dense:
-            tape.add_grad(spec.dense_bias_var, dbias)
-        return dqkv
+    def attn_bwd(dtd, o_b, want_dx, dres=None):
+        """attention half: ``dtd`` = gradient of the output projection behind its dropout (R rows; attention backward and the
+        QKV weight gradient see all rows).  → gradient of the half's input (+ ``dres`` at the kept rows), None unless wanted"""
+        wgrad(tape, dtd, ctx, P.o_w, o_b)
+        dctx = ops.gemm(dtd, P.o_w.data, trans_b=True)
+        dqkv = _attention_bwd(tape, spec, kw, dctx, qkv, ctx_full, lse, spread)
+        wgrad(tape, dqkv, a_in, P.qkv_w, P.qkv_b)
+        return dgrad(dqkv, P.qkv_w, residual=None if dres is None else spread(dres)) if want_dx else None
 
-    def bwd_post():
+    def bwd():
         g = o.grad
         o.grad = None
         if g is None:
             return
         ride = _WGRAD_ASUM and dyd_rides(g)     # bias gradients ride on the weight-gradient GEMMs (wgrad) where they can
-        dy, dyd = _ln_bwd_dense(tape, g, y, P.ln2_w, P.ln2_b, m2, r2, None if ride else P.fc2_b, p_hidden, s_f2)
-        wgrad(tape, dyd, h, P.fc2_w, P.fc2_b if ride else None)
-        gb1 = tape.pgrad(P.fc1_b)           # fc1 bias gradient = colsum(du): fused into the GEMM epilogue
-        du, du8 = lin8(dyd, P.fc2_w, "d_fc2", transposed_weight=True, grad=True, aux=u, epilogue=ops.EPI_MULAUX,
-                       colsum=None if gb1 is None else gb1.view(-1), q8_site=("d_fc1", id(P.fc1_w)), q8_grad=True) or (None, None)
-        if du is None:
-            du = dgrad(dyd, P.fc2_w, aux=u, epilogue=ops.EPI_MULAUX,
-                          colsum=None if gb1 is None else gb1.view(-1))
-        wgrad(tape, du, a, P.fc1_w, None)
-        da = lin8(du, P.fc1_w, "d_fc1", transposed_weight=True, grad=True, x8=du8, residual=dy)      # 8-bit when the GEMM above handed over the quantised du
-        if da is None:
-            da = dgrad(du, P.fc1_w, residual=dy)
-        dt_, dtd = _ln_bwd_dense(tape, da, t, P.ln1_w, P.ln1_b, m1, r1, None if ride else P.o_b, p_hidden, s_o)
-        wgrad(tape, dtd, ctx, P.o_w, P.o_b if ride else None)
-        dctx = ops.gemm(dtd, P.o_w.data, trans_b=True)
-        dqkv = attn_bwd(dctx)
-        wgrad(tape, dqkv, xd, P.qkv_w, P.qkv_b)
-        if x.needs_grad:
-            tape.add_grad(x, dgrad(dqkv, P.qkv_w, residual=spread(dt_, xd.shape[0])))
+        if not pre_ln:
+            dy, dyd = _ln_bwd_dense(tape, g, y, P.ln2_w, P.ln2_b, m2, r2, None if ride else P.fc2_b, p_hidden, s_f2)
+            df = ffn_bwd(dyd, P.fc2_b if ride else None, dy)
+            dt_, dtd = _ln_bwd_dense(tape, df, t, P.ln1_w, P.ln1_b, m1, r1, None if ride else P.o_b, p_hidden, s_o)
+            dx = attn_bwd(dtd, P.o_b if ride else None, x.needs_grad, dt_)
+            if x.needs_grad:
+                tape.add_grad(x, dx)
+        else:
+            gd = ops.dropout(g, p_hidden, s_f2) if p_hidden > 0 else g     # fc2's output went through hidden dropout
+            df = ffn_bwd(gd, P.fc2_b, None)
+            dt_, dtd = _ln_bwd_dense(tape, df, t, P.ln2_w, P.ln2_b, m2, r2, None if ride else P.o_b, p_hidden, s_o, add=g)
+            da = attn_bwd(dtd, P.o_b if ride else None, True)
+            if x.needs_grad:
+                tape.add_grad(x, _ln_bwd(tape, da, xd, P.ln1_w, P.ln1_b, m1, r1, add=spread(dt_)))
+            else:   # LayerNorm parameters still need their gradients
+                _ln_bwd(tape, da, xd, P.ln1_w, P.ln1_b, m1, r1)
         if tape.on_params_ready:
             tape.on_params_ready(P.all())
 
-    def bwd_pre():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
-        gd = hdrop(g, s_f2)
-        wgrad(tape, gd, f, P.fc2_w, P.fc2_b)
-        gb1 = tape.pgrad(P.fc1_b)
-        du, du8 = lin8(gd, P.fc2_w, "d_fc2", transposed_weight=True, grad=True, aux=u, epilogue=ops.EPI_MULAUX,
-                       colsum=None if gb1 is None else gb1.view(-1), q8_site=("d_fc1", id(P.fc1_w)), q8_grad=True) or (None, None)
-        if du is None:
-            du = dgrad(gd, P.fc2_w, aux=u, epilogue=ops.EPI_MULAUX,
-                          colsum=None if gb1 is None else gb1.view(-1))
-        wgrad(tape, du, n2, P.fc1_w, None)
-        dn2 = lin8(du, P.fc1_w, "d_fc1", transposed_weight=True, grad=True, x8=du8)
-        if dn2 is None:
-            dn2 = dgrad(du, P.fc1_w)
-        ride = _WGRAD_ASUM and dyd_rides(g)
-        dh, dhd = _ln_bwd_dense(tape, dn2, hmid, P.ln2_w, P.ln2_b, m2, r2, None if ride else P.o_b, p_hidden, s_o, add=g)
-        wgrad(tape, dhd, ctx, P.o_w, P.o_b if ride else None)
-        dctx = ops.gemm(dhd, P.o_w.data, trans_b=True)
-        dqkv = attn_bwd(dctx)
-        wgrad(tape, dqkv, n1, P.qkv_w, P.qkv_b)
-        if x.needs_grad:
-            dn1 = dgrad(dqkv, P.qkv_w)
-            tape.add_grad(x, _ln_bwd(tape, dn1, xd, P.ln1_w, P.ln1_b, m1, r1, add=spread(dh, xd.shape[0])))
-        else:   # LayerNorm parameters still need their gradients
-            dn1 = dgrad(dqkv, P.qkv_w)
-            _ln_bwd(tape, dn1, xd, P.ln1_w, P.ln1_b, m1, r1)
-        if tape.on_params_ready:
-            tape.on_params_ready(P.all())
-
-    tape.record(bwd_pre if pre_ln else bwd_post)
+    tape.record(bwd)
     return o
+
+
+def _attention_bwd(tape: Tape, spec: AttnSpec, kw: dict, dctx, qkv, ctx, lse, spread=lambda g: g):
+    """ops.attention_bwd (``kw``: spec.kwargs() and the dropout site, as forward) with its bias gradients: the structural
+    tables' go to their parameters, a dense bias' to ``spec.dense_bias_var``.  ``spread``: takes ``dctx`` to all rows of
+    ``qkv`` (a block with keep_rows).  → dqkv"""
+    extra = {}
+    if spec.sp_table is not None:
+        extra = dict(d_sp_table=tape.pgrad(spec.sp_table),
+                     d_virt=None if tape.pgrad(spec.virt) is None else tape.pgrad(spec.virt).view(-1))
+    want_dense = spec.dense_bias_var is not None and spec.dense_bias_var.needs_grad
+    dqkv, dbias = ops.attention_bwd(spread(dctx), qkv, ctx, lse, spec.nseq, spec.S, spec.H, **kw, want_dense_dbias=want_dense,
+                                    **extra)
+    if want_dense:
+        tape.add_grad(spec.dense_bias_var, dbias)
+    return dqkv
 
 
 def attention_layer(tape: Tape, x: Var, qkv_w, qkv_b, o_w, o_b, spec: AttnSpec, p_attn: float = 0.0, stash: Optional[dict] = None) -> Var:
     """Bare multi-head self-attention + output projection (modules/multihead_attention.py:91-214).  ``stash``: receives
     the qkv buffer and the log-sum-exp (what the need_weights=True path recomputes the probabilities from)."""
     xd = x.data
-    kw = spec.kwargs()
-    kw.update(drop_p=p_attn, drop_seed=tape.next_seed())
+    kw = dict(spec.kwargs(), drop_p=p_attn, drop_seed=tape.next_seed())
     qkv = ops.gemm(xd, qkv_w.data, bias=None if qkv_b is None else qkv_b.data)
     ctx, lse = ops.attention_fwd(qkv, spec.nseq, spec.S, spec.H, **kw)
     if stash is not None:
@@ -548,16 +514,7 @@ def attention_layer(tape: Tape, x: Var, qkv_w, qkv_b, o_w, o_b, spec: AttnSpec, 
         if g is None:
             return
         wgrad(tape, g, ctx, o_w, o_b)
-        dctx = ops.gemm(g, o_w.data, trans_b=True)
-        extra = {}
-        if spec.sp_table is not None:
-            extra = dict(d_sp_table=tape.pgrad(spec.sp_table),
-                         d_virt=None if tape.pgrad(spec.virt) is None else tape.pgrad(spec.virt).view(-1))
-        want_dense = spec.dense_bias_var is not None and spec.dense_bias_var.needs_grad
-        dqkv, dbias = ops.attention_bwd(dctx, qkv, ctx, lse, spec.nseq, spec.S, spec.H, **kw,
-                                        want_dense_dbias=want_dense, **extra)
-        if want_dense:
-            tape.add_grad(spec.dense_bias_var, dbias)
+        dqkv = _attention_bwd(tape, spec, kw, ops.gemm(g, o_w.data, trans_b=True), qkv, ctx, lse)
         wgrad(tape, dqkv, xd, qkv_w, qkv_b)
         if x.needs_grad:
             tape.add_grad(x, ops.gemm(dqkv, qkv_w.data, trans_b=True))

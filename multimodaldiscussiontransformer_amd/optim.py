@@ -72,7 +72,7 @@ class FusedAdam:
         if fp8.ACTIVE is not None:
             fp8.ACTIVE.optimizer_stepped()      # the cached 8-bit weight copies are stale now
         from . import engine
-        engine.weights_changed()                # ... and the transposed copies the input gradients read
+        engine.weights_changed()                # ... and the zero-padded copies the patch projection reads (engine._k_padded)
 
     def _step_rest(self, lr, grad_scale, done):
         for p in self.params:
