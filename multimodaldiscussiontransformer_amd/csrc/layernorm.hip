@@ -3,6 +3,12 @@
 // HBM-bound: algorithmic bytes = rows * D * sizeof(T) * 2 (fwd), * 3 (+ residual 4) (bwd).
 // Replaces fairseq LayerNorm / HF nn.LayerNorm (modules/graphormer_graph_encoder_layer.py:
 // 127-130,138-141; modules/multigraphormer_graph_encoder.py:400-403; HF BertLayer/ViTLayer).
+//
+// Layout of this file: the row arithmetic (ln_fwd_row; ln_bwd_row and ln_bwd_reduce_columns) works on the register-resident
+// vectors of a row; the kernels around it are shells that differ in how a row's vectors get into and out of registers.
+// One exception, measured: layernorm_bwd_rows_kernel keeps its own copy of ln_bwd_row's statements (see there).  The launch
+// code below the kernels decides each question (vectors per lane, fp8 format, backward form) in one place and writes each
+// kernel family's argument list once.
 #include <algorithm>
 #include <type_traits>
 
@@ -35,12 +41,80 @@ template <> struct VecH<bf16_t> {
   __device__ __forceinline__ void set(int i, float x) { v[i] = (bf16_t)x; }
 };
 
+// One row forward, from the vectors xv a lane holds of it (vector i starts at column (i * 64 + lane) * V::N; vectors past D
+// are absent): mean, variance and rstd over the wave, mean[row] / rstd[row], and y = (x - mean) * rstd * gamma + beta stored
+// to yr.  The one place this arithmetic is written: the plain and the embedding-fused forward agree bit for bit because both
+// come through here.
+// Q8 (bf16 only): y ALSO leaves as fp8 (1: e4m3, 2: e5m2) for the 8-bit GEMM that consumes it — qr = saturate(bf16(y) * qs),
+// qmax = max(qmax, max |bf16(y)|), the bytes and the maximum mdt_fp8_quantize would make of y (fp8.hip), without its pass
+template <int NV, int Q8, typename T, typename V>
+__device__ __forceinline__ void ln_fwd_row(const V* xv, const V* gv, const V* bv, int lane, int D, float eps, int64_t row,
+                                           T* yr, float* mean, float* rstd, uint8_t* qr, float qs, float& qmax) {
+  constexpr int VN = V::N;
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * 64 + lane) * VN;
+    if (c < D) {
+#pragma unroll
+      for (int j = 0; j < VN; ++j) s += xv[i].get(j);
+    }
+  }
+  const float mu = wave_sum_dpp(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * 64 + lane) * VN;
+    if (c < D) {
+#pragma unroll
+      for (int j = 0; j < VN; ++j) { const float d = xv[i].get(j) - mu; q += d * d; }
+    }
+  }
+  const float rs = rsqrtf(wave_sum_dpp(q) / (float)D + eps);
+  if (lane == 0) { if (mean) mean[row] = mu; if (rstd) rstd[row] = rs; }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * 64 + lane) * VN;
+    if (c < D) {
+      V o;
+#pragma unroll
+      for (int j = 0; j < VN; ++j) o.set(j, (xv[i].get(j) - mu) * rs * gv[i].get(j) + bv[i].get(j));
+      *(V*)(yr + c) = o;
+      if constexpr (Q8 != 0 && (VN == 8 || VN == 4)) {
+        constexpr float FMAX = Q8 == 1 ? 448.0f : 57344.0f;
+        // mirrors fp8.hip: a NaN / infinity passes through as NaN (the MFMA propagates it to the loss) and marks the running
+        // maximum +inf, which fp8_scale_update leaves the scale alone for
+        float qv[VN];
+#pragma unroll
+        for (int j = 0; j < VN; ++j) {
+          const float r = o.get(j);                 // the ROUNDED output
+          const bool bad = !(fabsf(r) <= 3.0e38f);
+          qmax = bad ? __builtin_inff() : fmaxf(qmax, fabsf(r));
+          const float xq = r * qs;
+          qv[j] = (xq != xq) ? xq : fminf(fmaxf(xq, -FMAX), FMAX);
+        }
+        int w[VN / 4];
+#pragma unroll
+        for (int k = 0; k < VN / 4; ++k) {
+          w[k] = 0;
+          if constexpr (Q8 == 1) {
+            w[k] = __builtin_amdgcn_cvt_pk_fp8_f32(qv[4 * k], qv[4 * k + 1], w[k], false); w[k] = __builtin_amdgcn_cvt_pk_fp8_f32(qv[4 * k + 2], qv[4 * k + 3], w[k], true);
+          } else {
+            w[k] = __builtin_amdgcn_cvt_pk_bf8_f32(qv[4 * k], qv[4 * k + 1], w[k], false); w[k] = __builtin_amdgcn_cvt_pk_bf8_f32(qv[4 * k + 2], qv[4 * k + 3], w[k], true);
+          }
+        }
+        if constexpr (VN == 8) *(int2*)(qr + c) = make_int2(w[0], w[1]);
+        else *(int*)(qr + c) = w[0];
+      }
+    }
+  }
+}
+
 // NV = number of 16-B vectors per lane: D = NV * 64 * Vec<T>::N exactly, or masked tail.
 // A wave walks rows wid, wid + nwaves, ...; the next row is requested before the current one is reduced, so a wave keeps
 // two rows (and an 8-workgroup CU 64 of them, ~100 KiB) in flight — with one row per wave and no look-ahead the kernel
 // moved 4.1 TB/s, bounded by bytes in flight over the ~2 us of an HBM round trip.
-// Q8 (bf16 only): y ALSO leaves as fp8 (1: e4m3, 2: e5m2) for the 8-bit GEMM that consumes it — q8 = saturate(bf16(y) * *q8_scale),
-// *q8_amax = max(*q8_amax, max |bf16(y)|), the bytes and the maximum mdt_fp8_quantize would make of y (fp8.hip), without its pass
+// Q8: the fp8 copy of ln_fwd_row, q8 = saturate(bf16(y) * *q8_scale), *q8_amax = max(*q8_amax, max |bf16(y)|)
 template <typename T, int NV, int Q8 = 0, typename V = Vec<T>>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(int64_t rows, int D, const T* __restrict__ x, int64_t ldx,
                                                             const T* __restrict__ gamma, const T* __restrict__ beta,
@@ -79,64 +153,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(int64_t rows, int D,
         if (c < D) xn[i] = *(const V*)(x + next * ldx + c);
       }
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * 64 + lane) * VN;
-      if (c < D) {
-#pragma unroll
-        for (int j = 0; j < VN; ++j) s += xv[i].get(j);
-      }
-    }
-    const float mu = wave_sum_dpp(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * 64 + lane) * VN;
-      if (c < D) {
-#pragma unroll
-        for (int j = 0; j < VN; ++j) { const float d = xv[i].get(j) - mu; q += d * d; }
-      }
-    }
-    const float rs = rsqrtf(wave_sum_dpp(q) / (float)D + eps);
-    if (lane == 0) { if (mean) mean[row] = mu; if (rstd) rstd[row] = rs; }
-    T* yr = y + row * ldy;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * 64 + lane) * VN;
-      if (c < D) {
-        V o;
-#pragma unroll
-        for (int j = 0; j < VN; ++j) o.set(j, (xv[i].get(j) - mu) * rs * gv[i].get(j) + bv[i].get(j));
-        *(V*)(yr + c) = o;
-        if constexpr (Q8 != 0 && (VN == 8 || VN == 4)) {
-          constexpr float FMAX = Q8 == 1 ? 448.0f : 57344.0f;
-          // mirrors fp8.hip: a NaN / infinity passes through as NaN (the MFMA propagates it to the loss) and marks the running
-          // maximum +inf, which fp8_scale_update leaves the scale alone for
-          float qv[VN];
-#pragma unroll
-          for (int j = 0; j < VN; ++j) {
-            const float r = o.get(j);                 // the ROUNDED output
-            const bool bad = !(fabsf(r) <= 3.0e38f);
-            qmax = bad ? __builtin_inff() : fmaxf(qmax, fabsf(r));
-            const float xq = r * qs;
-            qv[j] = (xq != xq) ? xq : fminf(fmaxf(xq, -FMAX), FMAX);
-          }
-          int w[VN / 4];
-#pragma unroll
-          for (int k = 0; k < VN / 4; ++k) {
-            w[k] = 0;
-            if constexpr (Q8 == 1) {
-              w[k] = __builtin_amdgcn_cvt_pk_fp8_f32(qv[4 * k], qv[4 * k + 1], w[k], false); w[k] = __builtin_amdgcn_cvt_pk_fp8_f32(qv[4 * k + 2], qv[4 * k + 3], w[k], true);
-            } else {
-              w[k] = __builtin_amdgcn_cvt_pk_bf8_f32(qv[4 * k], qv[4 * k + 1], w[k], false); w[k] = __builtin_amdgcn_cvt_pk_bf8_f32(qv[4 * k + 2], qv[4 * k + 3], w[k], true);
-            }
-          }
-          if constexpr (VN == 8) *(int2*)(q8 + row * ldq + c) = make_int2(w[0], w[1]);
-          else *(int*)(q8 + row * ldq + c) = w[0];
-        }
-      }
-    }
+    ln_fwd_row<NV, Q8>(xv, gv, bv, lane, D, eps, row, y + row * ldy, mean, rstd, Q8 != 0 ? q8 + row * ldq : nullptr, qs, qmax);
     if (next >= rows) break;
     row = next;
 #pragma unroll
@@ -194,41 +211,17 @@ __global__ __launch_bounds__(256) void bert_embed_ln_rows_kernel(int64_t rows, i
     const int64_t next = row + nwaves;
     if (next < rows) request(next, wn, pn, tn);
     V xv[NV];
-    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * VN;
       if (c < D) {
 #pragma unroll
-        for (int j = 0; j < VN; ++j) {
-          xv[i].set(j, wv[i].get(j) + tv[i].get(j) + pv[i].get(j));      // the order and the rounding of bert_embed_rows_kernel
-          s += xv[i].get(j);
-        }
+        for (int j = 0; j < VN; ++j) xv[i].set(j, wv[i].get(j) + tv[i].get(j) + pv[i].get(j));      // the order and the rounding of bert_embed_rows_kernel
         if (xs) *(V*)(xs + row * ldxs + c) = xv[i];
       }
     }
-    const float mu = wave_sum_dpp(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * 64 + lane) * VN;
-      if (c < D) {
-#pragma unroll
-        for (int j = 0; j < VN; ++j) { const float d = xv[i].get(j) - mu; q += d * d; }
-      }
-    }
-    const float rs = rsqrtf(wave_sum_dpp(q) / (float)D + eps);
-    if (lane == 0) { if (mean) mean[row] = mu; if (rstd) rstd[row] = rs; }
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * 64 + lane) * VN;
-      if (c < D) {
-        V o;
-#pragma unroll
-        for (int j = 0; j < VN; ++j) o.set(j, (xv[i].get(j) - mu) * rs * gv[i].get(j) + bv[i].get(j));
-        *(V*)(y + row * ldy + c) = o;
-      }
-    }
+    float unused = 0.f;
+    ln_fwd_row<NV, 0>(xv, gv, bv, lane, D, eps, row, y + row * ldy, mean, rstd, (uint8_t*)nullptr, 1.0f, unused);
     if (next >= rows) break;
     row = next;
 #pragma unroll
@@ -236,10 +229,97 @@ __global__ __launch_bounds__(256) void bert_embed_ln_rows_kernel(int64_t rows, i
   }
 }
 
-// Backward: each wave walks rows_per_wave consecutive rows (the next row's x / dy / residual-gradient vectors are
-// requested before the current row is reduced), keeps per-lane partial dgamma / dbeta / column sums in registers,
-// the block combines them through ONE [4 waves][row] LDS buffer used three times (16 KiB at D = 768: the 48 KiB of
-// three buffers held a CU to three workgroups) and issues one float atomic per column.
+// Backward.  What a lane accumulates over the rows its wave walks: per-column partial dgamma / dbeta and (CS) column sums of
+// the tail output, one float per element of its NV vectors.
+template <int NV, int VN, bool CS>
+struct LnBwdPartials {
+  float g[NV][VN], b[NV][VN], c[CS ? NV : 1][CS ? VN : 1];
+  __device__ __forceinline__ void zero(int i) {
+#pragma unroll
+    for (int j = 0; j < VN; ++j) { g[i][j] = 0.f; b[i][j] = 0.f; if constexpr (CS) c[i][j] = 0.f; }
+  }
+};
+
+// One row backward, from the vectors a lane holds of it (x, dy, the residual-path gradient av when has_add, gamma):
+// the two row sums, the partials, dx and — when dropped — dxd, the gradient of the dense layer behind a hidden dropout.
+// store(i, c, o, od) takes vector i (column c) of dx and dxd to memory; vectors past D are absent.
+template <int NV, bool CS, typename V, typename Store>
+__device__ __forceinline__ void ln_bwd_row(int64_t row, int D, int lane, const V* xv, const V* gy, const V* av, const V* gv,
+                                           float mu, float rs, bool has_add, bool dropped, const DropCfg& drop,
+                                           LnBwdPartials<NV, V::N, CS>& part, Store&& store) {
+  constexpr int VN = V::N;
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * 64 + lane) * VN;
+    if (c < D) {
+#pragma unroll
+      for (int j = 0; j < VN; ++j) {
+        const float xh = (xv[i].get(j) - mu) * rs;
+        const float g = gy[i].get(j);
+        const float gg = g * gv[i].get(j);
+        s1 += gg;
+        s2 += gg * xh;
+        part.g[i][j] += g * xh;
+        part.b[i][j] += g;
+      }
+    }
+  }
+  const float m1 = wave_sum_dpp(s1) / (float)D, m2 = wave_sum_dpp(s2) / (float)D;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * 64 + lane) * VN;
+    if (c < D) {
+      V o, od;
+      float ds0 = 0.f, ds1 = 0.f;
+#pragma unroll
+      for (int j = 0; j < VN; ++j) {
+        const float xh = (xv[i].get(j) - mu) * rs;
+        float v = rs * (gy[i].get(j) * gv[i].get(j) - m1 - xh * m2);
+        if (has_add) v += av[i].get(j);
+        o.set(j, v);
+        if (dropped) {
+          if ((j & 1) == 0) drop_scale2(drop, (uint64_t)row * D + c + j, ds0, ds1);   // D and c are even
+          v = o.get(j) * ((j & 1) ? ds1 : ds0);
+          od.set(j, v);
+          v = od.get(j);
+        } else {
+          v = o.get(j);
+        }
+        if constexpr (CS) part.c[i][j] += v;
+      }
+      store(i, c, o, od);
+    }
+  }
+}
+
+// The workgroup's four waves combine their partials through ONE [4 waves][W = NV * 64 * VN] LDS buffer used three times
+// (dgamma, dbeta, column sums; 16 KiB at D = 768: the 48 KiB of three buffers held a CU to three workgroups) and issue one
+// float atomic per column.
+template <int NV, int VN, bool CS>
+__device__ __forceinline__ void ln_bwd_reduce_columns(const LnBwdPartials<NV, VN, CS>& part, float* red, int lane, int wave, int D,
+                                                      float* dgamma, float* dbeta, float* colsum) {
+  if (!dgamma && !dbeta && !colsum) return;
+  constexpr int W = NV * 64 * VN;
+#pragma unroll
+  for (int round = 0; round < (CS ? 3 : 2); ++round) {
+    float* dst = round == 0 ? dgamma : round == 1 ? dbeta : colsum;
+    if (round) __syncthreads();           // the previous round's readers are done
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int j = 0; j < VN; ++j) {
+        const int c = (i * 64 + lane) * VN + j;
+        red[wave * W + c] = round == 0 ? part.g[i][j] : round == 1 ? part.b[i][j] : part.c[CS ? i : 0][CS ? j : 0];
+      }
+    __syncthreads();
+    if (dst)
+      for (int c = threadIdx.x; c < D; c += 256) atomicAdd(dst + c, red[c] + red[W + c] + red[2 * W + c] + red[3 * W + c]);
+  }
+}
+
+// The generic backward shell: each wave walks rows_per_wave consecutive rows (the next row's x / dy / residual-gradient
+// vectors are requested before the current row is reduced) through 64-bit pointers, vectors past D masked.
 template <typename T, int NV, bool TAIL, bool CS = TAIL, typename V = Vec<T>>   // TAIL: second (dropped) output and / or column sums; CS: the column sums
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(int64_t rows, int D, const T* __restrict__ dy, int64_t lddy,
                                                             const T* __restrict__ x, int64_t ldx,
@@ -255,14 +335,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(int64_t rows, int D,
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * rows_per_wave;
   const int64_t r1 = (r0 + rows_per_wave < rows) ? r0 + rows_per_wave : rows;
-  float pg[NV][VN], pb[NV][VN], pc[CS ? NV : 1][CS ? VN : 1];
+  LnBwdPartials<NV, VN, CS> part;
   V gv[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (i * 64 + lane) * VN;
     if (c < D) gv[i] = *(const V*)(gamma + c);
-#pragma unroll
-    for (int j = 0; j < VN; ++j) { pg[i][j] = 0.f; pb[i][j] = 0.f; if constexpr (CS) pc[i][j] = 0.f; }
+    part.zero(i);
   }
   V xv[NV], gy[NV], av[NV], xn[NV], gn[NV], an[NV];
   float mu = 0.f, rs = 0.f, mu_n = 0.f, rs_n = 0.f;
@@ -291,83 +370,29 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(int64_t rows, int D,
         }
       }
     }
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * 64 + lane) * VN;
-      if (c < D) {
-#pragma unroll
-        for (int j = 0; j < VN; ++j) {
-          const float xh = (xv[i].get(j) - mu) * rs;
-          const float g = gy[i].get(j);
-          const float gg = g * gv[i].get(j);
-          s1 += gg;
-          s2 += gg * xh;
-          pg[i][j] += g * xh;
-          pb[i][j] += g;
-        }
-      }
-    }
-    const float m1 = wave_sum_dpp(s1) / (float)D, m2 = wave_sum_dpp(s2) / (float)D;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * 64 + lane) * VN;
-      if (c < D) {
-        V o, od;
-        float ds0 = 0.f, ds1 = 0.f;
-#pragma unroll
-        for (int j = 0; j < VN; ++j) {
-          const float xh = (xv[i].get(j) - mu) * rs;
-          float v = rs * (gy[i].get(j) * gv[i].get(j) - m1 - xh * m2);
-          if (add) v += av[i].get(j);
-          o.set(j, v);
-          if constexpr (TAIL) {
-            if (dxd) {   // second output: the gradient of the dense layer behind a hidden dropout
-              if ((j & 1) == 0) drop_scale2(drop, (uint64_t)row * D + c + j, ds0, ds1);   // D and c are even
-              v = o.get(j) * ((j & 1) ? ds1 : ds0);
-              od.set(j, v);
-              v = od.get(j);
-            } else {
-              v = o.get(j);
-            }
-            if constexpr (CS) pc[i][j] += v;
-          }
-        }
-        *(V*)(dx + row * lddx + c) = o;
-        if constexpr (TAIL) {
-          if (dxd) *(V*)(dxd + row * lddxd + c) = od;
-        }
-      }
-    }
+    ln_bwd_row<NV, CS>(row, D, lane, xv, gy, av, gv, mu, rs, add != nullptr, TAIL && dxd != nullptr, drop, part,
+                              [&](int, int c, const V& o, const V& od) {
+                                *(V*)(dx + row * lddx + c) = o;
+                                if constexpr (TAIL) {
+                                  if (dxd) *(V*)(dxd + row * lddxd + c) = od;
+                                }
+                              });
     mu = mu_n; rs = rs_n;
 #pragma unroll
     for (int i = 0; i < NV; ++i) { xv[i] = xn[i]; gy[i] = gn[i]; av[i] = an[i]; }
   }
-  if (!dgamma && !dbeta && !colsum) return;
-  const int W = NV * 64 * VN;
-  // three rounds through the one buffer: dgamma, dbeta, column sums
-#pragma unroll
-  for (int round = 0; round < (CS ? 3 : 2); ++round) {
-    float* dst = round == 0 ? dgamma : round == 1 ? dbeta : colsum;
-    if (round) __syncthreads();           // the previous round's readers are done
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int j = 0; j < VN; ++j) {
-        const int c = (i * 64 + lane) * VN + j;
-        red[wave * W + c] = round == 0 ? pg[i][j] : round == 1 ? pb[i][j] : pc[CS ? i : 0][CS ? j : 0];
-      }
-    __syncthreads();
-    if (dst)
-      for (int c = threadIdx.x; c < D; c += 256) atomicAdd(dst + c, red[c] + red[W + c] + red[2 * W + c] + red[3 * W + c]);
-  }
+  ln_bwd_reduce_columns(part, red, lane, wave, D, dgamma, dbeta, colsum);
 }
 
-// The backward kernel for bf16 rows of 256 * NV elements (768: every LayerNorm of mDT-base; 1024: mDT-large) with its addresses in SCALAR registers: a wave owns whole
+// The backward shell for bf16 rows of 256 * NV elements (768: every LayerNorm of mDT-base; 1024: mDT-large) with its addresses in SCALAR registers: a wave owns whole
 // rows, so a row's byte offset is wave-uniform — each tensor is a buffer descriptor based at the wave's first row, the row offset
 // goes into the instruction's SGPR operand, the vector's place in the row into its 12-bit immediate (0 / 512 / 1024), and ONE VGPR
 // (lane * 8) serves every load and store of the kernel.  Same arithmetic in the same order as layernorm_bwd_kernel<bf16_t, 3, ...,
 // VecH>: what changes is the register budget (no 64-bit address per tensor and row, no vectors for an absent residual gradient).
+// That budget is why the row loop below repeats the statements of ln_bwd_row instead of calling it: through the call (its
+// vectors handed over as pointers, with or without __restrict__, the flags as template arguments, the stores inside or outside)
+// the compiler packs the row's operations differently and every instantiation with NV >= 2 takes 2 to 17 more VGPRs; six of
+// them (NV 2: fff ftf ftt ttf ttt, NV 4: ftf) lose a wave of occupancy.  Edit the two together: the D = 768 test compares them bit for bit.
 template <int NV, bool DROPPED, bool CS, bool ADD>
 __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(int64_t rows, const bf16_t* __restrict__ dy, int64_t lddy,
                                                                 const bf16_t* __restrict__ x, int64_t ldx,
@@ -404,13 +429,12 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(int64_t rows, c
   auto st8 = [&](__amdgpu_buffer_rsrc_t rs, int i, int soff, const V& v) {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v.v), rs, voff + i * 512, soff, 0);
   };
-  float pg[NV][VN], pb[NV][VN], pc[CS ? NV : 1][CS ? VN : 1];
+  LnBwdPartials<NV, VN, CS> part;
   V gv[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     gv[i] = *(const V*)(gamma + (i * 64 + lane) * VN);
-#pragma unroll
-    for (int j = 0; j < VN; ++j) { pg[i][j] = 0.f; pb[i][j] = 0.f; if constexpr (CS) pc[i][j] = 0.f; }
+    part.zero(i);
   }
   V xv[NV], gy[NV], av[ADD ? NV : 1], xn[NV], gn[NV], an[ADD ? NV : 1];
   float mu = 0.f, rs = 0.f, mu_n = 0.f, rs_n = 0.f;
@@ -434,6 +458,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(int64_t rows, c
         if constexpr (ADD) an[i] = ld8(rs_add, i, (k + 1) * s_add);
       }
     }
+    // ln_bwd_row, operation for operation, written out: see above the kernel
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -444,8 +469,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(int64_t rows, c
         const float gg = g * gv[i].get(j);
         s1 += gg;
         s2 += gg * xh;
-        pg[i][j] += g * xh;
-        pb[i][j] += g;
+        part.g[i][j] += g * xh;
+        part.b[i][j] += g;
       }
     }
     const float m1 = wave_sum_dpp(s1) / (float)D, m2 = wave_sum_dpp(s2) / (float)D;
@@ -468,7 +493,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(int64_t rows, c
         } else {
           v = o.get(j);
         }
-        if constexpr (CS) pc[i][j] += v;
+        if constexpr (CS) part.c[i][j] += v;
       }
       st8(rs_dx, i, k * s_dx, o);
       if constexpr (DROPPED) st8(rs_dxd, i, k * s_dxd, od);
@@ -477,64 +502,67 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(int64_t rows, c
 #pragma unroll
     for (int i = 0; i < NV; ++i) { xv[i] = xn[i]; gy[i] = gn[i]; if constexpr (ADD) av[i] = an[i]; }
   }
-  if (!dgamma && !dbeta && !colsum) return;
-  constexpr int W = D;
-#pragma unroll
-  for (int round = 0; round < (CS ? 3 : 2); ++round) {
-    float* dst = round == 0 ? dgamma : round == 1 ? dbeta : colsum;
-    if (round) __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int j = 0; j < VN; ++j)
-        red[wave * W + (i * 64 + lane) * VN + j] = round == 0 ? pg[i][j] : round == 1 ? pb[i][j] : pc[CS ? i : 0][CS ? j : 0];
-    __syncthreads();
-    if (dst)
-      for (int c = threadIdx.x; c < D; c += 256) atomicAdd(dst + c, red[c] + red[W + c] + red[2 * W + c] + red[3 * W + c]);
+  ln_bwd_reduce_columns(part, red, lane, wave, D, dgamma, dbeta, colsum);
+}
+
+// ---- launch: every choice made once, every argument list written once
+// Runtime value -> template argument: f(std::integral_constant<int, v>) for the v among Vs that equals value; false if none does.
+template <int... Vs, typename F>
+static bool ln_pick(int value, F&& f) {
+  return ((value == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// How a lane holds a row of D elements: f(NV, V) with NV vectors of type V per lane.  bf16 rows of 768 are three 8-byte
+// vectors, every lane busy (VecH); all else is ceil(D / (64 * Vec<T>::N)) 16-byte vectors, the last ones masked.
+// false: no kernel is instantiated for that many vectors per lane.
+template <typename T> static int ln_vectors_per_lane(int D) { return (D + 64 * Vec<T>::N - 1) / (64 * Vec<T>::N); }
+template <typename T, typename F>
+static bool ln_row_layout(int D, F&& f) {
+  if constexpr (std::is_same<T, bf16_t>::value) {
+    if (D == 768) { f(std::integral_constant<int, 3>{}, VecH<T>{}); return true; }
   }
+  return ln_pick<1, 2, 3, 4, 6, 8>(ln_vectors_per_lane<T>(D), [&](auto nv) { f(nv, Vec<T>{}); });
+}
+
+// Forward grids: 8 resident workgroups per CU (32 waves, two rows in flight each); short inputs get one row per wave
+static unsigned ln_fwd_grid(int64_t rows) {
+  const int64_t wgs = (rows + 3) / 4;
+  return (unsigned)(wgs < 2048 ? wgs : 2048);
+}
+
+// The one launch: the arguments are converted to the kernel's own parameter types (the C ABI hands tensors over as void*)
+template <typename... P, typename... A>
+static void ln_launch(void (*kernel)(P...), unsigned grid, size_t lds, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(kernel, grid, 256, lds, st, (P)args...);
 }
 
 template <typename T>
 static int ln_fwd_dispatch(hipStream_t st, int64_t rows, int D, const void* x, int64_t ldx, const void* gamma,
                            const void* beta, float eps, void* y, int64_t ldy, float* mean, float* rstd, void* q8 = nullptr,
                            int64_t ldq = 0, int q8_fmt = 0, const float* q8_scale = nullptr, float* q8_amax = nullptr) {
-  constexpr int VN = Vec<T>::N;
-  const int nv = (D + 64 * VN - 1) / (64 * VN);
-  // 8 resident workgroups per CU (32 waves, two rows in flight each); short inputs get one row per wave
-  const int64_t wgs = (rows + 3) / 4;
-  const unsigned grid = (unsigned)(wgs < 2048 ? wgs : 2048);
-  if constexpr (std::is_same<T, bf16_t>::value) {
-    if (D == 768) {          // three 8-byte vectors per lane, every lane busy (VecH)
-#define LN_FWD_H(Q_) hipLaunchKernelGGL((layernorm_fwd_kernel<T, 3, Q_, VecH<T>>), grid, 256, 0, st, rows, D, (const T*)x, ldx, (const T*)gamma, (const T*)beta, \
-                                        eps, (T*)y, ldy, mean, rstd, (uint8_t*)q8, ldq, q8_scale, q8_amax)
-      if (q8 && q8_fmt == 0) LN_FWD_H(1);
-      else if (q8) LN_FWD_H(2);
-      else LN_FWD_H(0);
-#undef LN_FWD_H
-      return check_launch("layernorm_fwd");
-    }
-  }
-#define LN_FWD(NV_)                                                                                          \
-  if (q8 && q8_fmt == 0)                                                                                     \
-    hipLaunchKernelGGL((layernorm_fwd_kernel<T, NV_, 1>), grid, 256, 0, st, rows, D, (const T*)x, ldx, (const T*)gamma, (const T*)beta, \
-                       eps, (T*)y, ldy, mean, rstd, (uint8_t*)q8, ldq, q8_scale, q8_amax);                   \
-  else if (q8)                                                                                               \
-    hipLaunchKernelGGL((layernorm_fwd_kernel<T, NV_, 2>), grid, 256, 0, st, rows, D, (const T*)x, ldx, (const T*)gamma, (const T*)beta, \
-                       eps, (T*)y, ldy, mean, rstd, (uint8_t*)q8, ldq, q8_scale, q8_amax);                   \
-  else                                                                                                       \
-    hipLaunchKernelGGL((layernorm_fwd_kernel<T, NV_>), grid, 256, 0, st, rows, D, (const T*)x, ldx,        \
-                       (const T*)gamma, (const T*)beta, eps, (T*)y, ldy, mean, rstd, (uint8_t*)nullptr, (int64_t)0, (const float*)nullptr, (float*)nullptr)
-  switch (nv) {
-    case 1: LN_FWD(1); break;
-    case 2: LN_FWD(2); break;
-    case 3: LN_FWD(3); break;
-    case 4: LN_FWD(4); break;
-    case 6: LN_FWD(6); break;
-    case 8: LN_FWD(8); break;
-    default: MDT_UNSUPPORTED("layernorm: D=%d not supported (vectors per lane %d)", D, nv);
-  }
-#undef LN_FWD
+  const bool ok = ln_row_layout<T>(D, [&](auto nv, auto vec) {
+    auto launch = [&](auto q8_form) {
+      ln_launch(layernorm_fwd_kernel<T, decltype(nv)::value, decltype(q8_form)::value, decltype(vec)>, ln_fwd_grid(rows), 0, st,
+                rows, D, x, ldx, gamma, beta, eps, y, ldy, mean, rstd, q8, ldq, q8_scale, q8_amax);
+    };
+    // the fp8 copy exists for bf16 rows only (mdt_layernorm_fwd_q8 lets nothing else through): 1 = e4m3, 2 = e5m2
+    if constexpr (std::is_same<T, bf16_t>::value) ln_pick<0, 1, 2>(q8 ? (q8_fmt == 0 ? 1 : 2) : 0, launch);
+    else launch(std::integral_constant<int, 0>{});
+  });
+  if (!ok) MDT_UNSUPPORTED("layernorm: D=%d not supported (vectors per lane %d)", D, ln_vectors_per_lane<T>(D));
   return check_launch("layernorm_fwd");
+}
+
+template <typename T>
+static int embed_ln_dispatch(hipStream_t st, int64_t rows, int D, const int32_t* ids, const int32_t* types, const int32_t* pos_ids,
+                             const void* word, const void* pos, const void* typ, const void* gamma, const void* beta, float eps,
+                             void* xs, int64_t ldxs, void* y, int64_t ldy, float* mean, float* rstd) {
+  const bool ok = ln_row_layout<T>(D, [&](auto nv, auto vec) {
+    ln_launch(bert_embed_ln_rows_kernel<T, decltype(nv)::value, decltype(vec)>, ln_fwd_grid(rows), 0, st,
+              rows, D, ids, types, pos_ids, word, pos, typ, gamma, beta, eps, xs, ldxs, y, ldy, mean, rstd);
+  });
+  if (!ok) MDT_UNSUPPORTED("bert_embed_ln_rows: D=%d not supported (vectors per lane %d)", D, ln_vectors_per_lane<T>(D));
+  return check_launch("bert_embed_ln_rows");
 }
 
 template <typename T>
@@ -542,72 +570,37 @@ static int ln_bwd_dispatch(hipStream_t st, int64_t rows, int D, const void* dy, 
                            const void* gamma, const float* mean, const float* rstd, const void* add, int64_t ldadd,
                            void* dx, int64_t lddx, float* dgamma, float* dbeta, void* dxd, int64_t lddxd, DropCfg drop,
                            float* colsum) {
-  constexpr int VN = Vec<T>::N;
-  const int nv = (D + 64 * VN - 1) / (64 * VN);
   // ~2048 workgroups x 4 waves, at least 4 rows per wave so the column atomics stay few
   const int64_t want = switches().ln_bwd_wgs > 0 ? switches().ln_bwd_wgs : 2048;
   int rpw = (int)((rows + want * 4 - 1) / (want * 4));
   if (rpw < 4) rpw = 4;
   const unsigned grid = (unsigned)((rows + 4 * rpw - 1) / (4 * rpw));
-  const bool tail = dxd != nullptr || colsum != nullptr;
-  if constexpr (std::is_same<T, bf16_t>::value) {
-    // row offsets inside a wave's block of rows are 32-bit scalars: rows_per_wave * row stride stays far below 2^31
-    const int64_t ldmax = std::max(std::max(lddy, ldx), std::max(std::max(ldadd, lddx), lddxd));
-    if ((D == 768 || D == 1024 || D == 512 || D == 256) && !switches().ln_generic && (int64_t)rpw * ldmax * 2 < (1ll << 31)) {
-#define LN_BWD_S(NV_, DR_, CS_, ADD_) hipLaunchKernelGGL((layernorm_bwd_rows_kernel<NV_, DR_, CS_, ADD_>), grid, 256, (size_t)(4 * 256 * NV_ * 4), st, rows, \
-                       (const T*)dy, lddy, (const T*)x, ldx, (const T*)gamma, mean, rstd, (const T*)add, ldadd,  \
-                       (T*)dx, lddx, dgamma, dbeta, rpw, (T*)dxd, lddxd, drop, colsum)
-#define LN_BWD_F(NV_)                                          \
-      switch (form) {                                          \
-        case 0: LN_BWD_S(NV_, false, false, false); break;     \
-        case 1: LN_BWD_S(NV_, false, false, true); break;      \
-        case 2: LN_BWD_S(NV_, false, true, false); break;      \
-        case 3: LN_BWD_S(NV_, false, true, true); break;       \
-        case 4: LN_BWD_S(NV_, true, false, false); break;      \
-        case 5: LN_BWD_S(NV_, true, false, true); break;       \
-        case 6: LN_BWD_S(NV_, true, true, false); break;       \
-        default: LN_BWD_S(NV_, true, true, true); break;       \
+  // both kernels end in the same parameters; lead is (rows) or (rows, D); LDS: [4 waves][row as the lanes hold it] floats
+  auto launch = [&](auto kernel, int row_elems, auto... lead) {
+    ln_launch(kernel, grid, (size_t)(4 * row_elems * 4), st, lead..., dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx,
+              dgamma, dbeta, rpw, dxd, lddxd, drop, colsum);
+  };
+  // the form: which optional tensors take part (bit 2: the dropped copy, bit 1: the column sums, bit 0: the residual gradient)
+  const int form = (dxd ? 4 : 0) | (colsum ? 2 : 0) | (add ? 1 : 0);
+  bool ok = false;
+  ln_pick<0, 1, 2, 3, 4, 5, 6, 7>(form, [&](auto f) {
+    constexpr bool DROPPED = (decltype(f)::value & 4) != 0, CS = (decltype(f)::value & 2) != 0, ADD = (decltype(f)::value & 1) != 0;
+    if constexpr (std::is_same<T, bf16_t>::value) {
+      // row offsets inside a wave's block of rows are 32-bit scalars: rows_per_wave * row stride stays far below 2^31
+      const int64_t ldmax = std::max(std::max(lddy, ldx), std::max(std::max(ldadd, lddx), lddxd));
+      if ((D == 768 || D == 1024 || D == 512 || D == 256) && !switches().ln_generic && (int64_t)rpw * ldmax * 2 < (1ll << 31)) {
+        ok = ln_pick<1, 2, 3, 4>(D / 256, [&](auto nv) {
+          launch(layernorm_bwd_rows_kernel<decltype(nv)::value, DROPPED, CS, ADD>, D, rows);
+        });
+        return;
       }
-      const int form = (dxd ? 4 : 0) | (colsum ? 2 : 0) | (add ? 1 : 0);
-      if (D == 768) { LN_BWD_F(3) } else if (D == 1024) { LN_BWD_F(4) } else if (D == 512) { LN_BWD_F(2) } else { LN_BWD_F(1) }
-#undef LN_BWD_F
-#undef LN_BWD_S
-      return check_launch("layernorm_bwd");
     }
-    if (D == 768) {
-#define LN_BWD_H(TAIL_, CS_) hipLaunchKernelGGL((layernorm_bwd_kernel<T, 3, TAIL_, CS_, VecH<T>>), grid, 256, (size_t)(4 * 768 * 4), st, rows, D, \
-                       (const T*)dy, lddy, (const T*)x, ldx, (const T*)gamma, mean, rstd, (const T*)add, ldadd,  \
-                       (T*)dx, lddx, dgamma, dbeta, rpw, (T*)dxd, lddxd, drop, colsum)
-      if (tail && !colsum) LN_BWD_H(true, false);
-      else if (tail) LN_BWD_H(true, true);
-      else LN_BWD_H(false, false);
-#undef LN_BWD_H
-      return check_launch("layernorm_bwd");
-    }
-  }
-#define LN_BWD(NV_)                                                                                              \
-  if (tail && !colsum)                                                                                           \
-    hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV_, true, false>), grid, 256, (size_t)(4 * NV_ * 64 * VN * 4), st, rows, D, \
-                       (const T*)dy, lddy, (const T*)x, ldx, (const T*)gamma, mean, rstd, (const T*)add, ldadd,  \
-                       (T*)dx, lddx, dgamma, dbeta, rpw, (T*)dxd, lddxd, drop, colsum);                          \
-  else if (tail)                                                                                                 \
-    hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV_, true>), grid, 256, (size_t)(4 * NV_ * 64 * VN * 4), st, rows, D, \
-                       (const T*)dy, lddy, (const T*)x, ldx, (const T*)gamma, mean, rstd, (const T*)add, ldadd,  \
-                       (T*)dx, lddx, dgamma, dbeta, rpw, (T*)dxd, lddxd, drop, colsum);                          \
-  else                                                                                                           \
-    hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV_, false>), grid, 256, (size_t)(4 * NV_ * 64 * VN * 4), st, rows, D, \
-                       (const T*)dy, lddy, (const T*)x, ldx, (const T*)gamma, mean, rstd, (const T*)add, ldadd,  \
-                       (T*)dx, lddx, dgamma, dbeta, rpw, (T*)dxd, lddxd, drop, colsum)
-  switch (nv) {
-    case 1: LN_BWD(1); break;
-    case 2: LN_BWD(2); break;
-    case 3: LN_BWD(3); break;
-    case 4: LN_BWD(4); break;
-    case 6: LN_BWD(6); break;
-    case 8: LN_BWD(8); break;
-    default: MDT_UNSUPPORTED("layernorm: D=%d not supported (vectors per lane %d)", D, nv);
-  }
-#undef LN_BWD
+    ok = ln_row_layout<T>(D, [&](auto nv, auto vec) {
+      constexpr int NV = decltype(nv)::value;
+      launch(layernorm_bwd_kernel<T, NV, DROPPED || CS, CS, decltype(vec)>, NV * 64 * decltype(vec)::N, rows, D);
+    });
+  });
+  if (!ok) MDT_UNSUPPORTED("layernorm: D=%d not supported (vectors per lane %d)", D, ln_vectors_per_lane<T>(D));
   return check_launch("layernorm_bwd");
 }
 
@@ -649,32 +642,6 @@ extern "C" int mdt_layernorm_fwd_q8(void* stream, int dtype, int64_t rows, int D
   if (int e = ln_check(dtype, D, ldx, ldy, x, y)) return e;
   MDT_CHECK_ARG((((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0, "layernorm_fwd_q8: gamma/beta must be 16-byte aligned");
   return ln_fwd_dispatch<bf16_t>((hipStream_t)stream, rows, D, x, ldx, gamma, beta, eps, y, ldy, mean, rstd, q8_out, ld_q8, q8_format, q8_scale, q8_amax);
-}
-
-template <typename T>
-static int embed_ln_dispatch(hipStream_t st, int64_t rows, int D, const int32_t* ids, const int32_t* types, const int32_t* pos_ids,
-                             const void* word, const void* pos, const void* typ, const void* gamma, const void* beta, float eps,
-                             void* xs, int64_t ldxs, void* y, int64_t ldy, float* mean, float* rstd) {
-  constexpr int VN = Vec<T>::N;
-  const int nv = (D + 64 * VN - 1) / (64 * VN);
-  const int64_t wgs = (rows + 3) / 4;
-  const unsigned grid = (unsigned)(wgs < 2048 ? wgs : 2048);
-#define EL_(NV_, V_) hipLaunchKernelGGL((bert_embed_ln_rows_kernel<T, NV_, V_>), grid, 256, 0, st, rows, D, ids, types, pos_ids, (const T*)word, \
-                                        (const T*)pos, (const T*)typ, (const T*)gamma, (const T*)beta, eps, (T*)xs, ldxs, (T*)y, ldy, mean, rstd)
-  if constexpr (std::is_same<T, bf16_t>::value) {
-    if (D == 768) { EL_(3, VecH<T>); return check_launch("bert_embed_ln_rows"); }
-  }
-  switch (nv) {
-    case 1: EL_(1, Vec<T>); break;
-    case 2: EL_(2, Vec<T>); break;
-    case 3: EL_(3, Vec<T>); break;
-    case 4: EL_(4, Vec<T>); break;
-    case 6: EL_(6, Vec<T>); break;
-    case 8: EL_(8, Vec<T>); break;
-    default: MDT_UNSUPPORTED("bert_embed_ln_rows: D=%d not supported (vectors per lane %d)", D, nv);
-  }
-#undef EL_
-  return check_launch("bert_embed_ln_rows");
 }
 
 extern "C" int mdt_bert_embed_ln_rows(void* stream, int dtype, int64_t rows, const int32_t* ids, const int32_t* types,
