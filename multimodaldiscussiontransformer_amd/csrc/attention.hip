@@ -6,7 +6,8 @@
 // whole key range of a 16-query tile lives in MFMA accumulators (NT tiles of 16 keys)
 // and softmax is a single exact pass — no online rescaling.
 //   bf16: v_mfma_f32_16x16x32_bf16; K / V (fwd), then K,V / Q,dO (bwd) staged in LDS
-//         (144-B padded rows); k-major operands (V in P@V, K in dS@K, dO / Q in the
+//         (head_dim 64: 144-B padded rows; head_dim 16: 32-B rows, and the upper half of
+//         the K = 32 contraction over the head is fed zeros); k-major operands (V in P@V, K in dS@K, dO / Q in the
 //         key-tile pass) are fetched with ds_read_b64_tr_b16.
 //   fp32: v_mfma_f32_16x16x4_f32 straight from global memory (parity path, exact fp32).
 // The Graphormer structural bias (modules/graphormer_layers.py:86-110) is evaluated on
@@ -46,16 +47,26 @@ template <typename T> struct Src {
 
 // fragment of a 16 x KS block whose rows are the MFMA row (A) or column (B) index and
 // whose k runs along the contiguous axis:  element(rc, k) = p[rc*ld + k]
-template <typename T, bool LDS>
+// KW (bf16): the k columns that exist from k0 on, 32 or 16 (a 16-wide head).  With 16, lanes 32-63 hold k = 16 .. 31:
+// columns of the next head or the next row, which they never read — they re-read chunk lane >> 4 & 1 of their own row;
+// the fragment from global memory becomes zeros there, the LDS one keeps the (finite) values it re-read: every
+// contraction over a head pairs one of each.
+template <typename T, bool LDS, int KW = 32>
 __device__ __forceinline__ typename MM<T>::frag frag_kc(const Src<T>& s, int rc0, int k0, int lane) {
   int rc = rc0 + (lane & 15);
   if (rc > s.rows - 1) rc = s.rows - 1;
   if constexpr (std::is_same<T, float>::value) {
     return s.p[rc * s.ld + k0 + (lane >> 4)];
   } else {
-    const bf16_t* a = s.p + rc * s.ld + k0 + 8 * (lane >> 4);
+    static_assert(KW == 32 || KW == 16, "a whole K = 32 step, or half of one");
+    const int g = lane >> 4;
+    const bf16_t* a = s.p + rc * s.ld + k0 + 8 * (KW == 32 ? g : g & 1);
     if constexpr (LDS) return *(const __attribute__((address_space(3))) bf16x8*)LDS_PTR(a);
-    else return *(const bf16x8*)a;
+    else if constexpr (KW == 32) return *(const bf16x8*)a;
+    else {
+      const bf16x8 v = *(const bf16x8*)a;      // every lane loads (its own row): the zeros are a select, not a lane mask
+      return g < 2 ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
   }
 }
 
@@ -75,7 +86,10 @@ __device__ __forceinline__ typename MM<T>::frag frag_km(const Src<T>& s, int c0,
   }
 }
 
-constexpr int IMG_LD = 72;  // bf16 LDS image row stride (64 + 8 elements = 144 B)
+// bf16 LDS image row stride in elements: 64 + 8 (144 B), or 16 unpadded (32 B: the row reads of a ds_read_b128 lane group
+// fall on sixteen different 16-byte slots as they are — attention_v2.hip v2_ld; the k-major reads of frag_km, rows
+// k0 .. k0 + 3 and k0 + 8 .. k0 + 11 per half wave, are 2-way there, on images of 1-3 KiB that these tiny rows hardly read)
+template <int HD> constexpr int IMG_LD = HD >= 32 ? HD + 8 : HD;
 
 // Stage a [S][HD] bf16 operand (rows = sequence positions) into an LDS image, zero padded
 // to rows_pad rows.
@@ -86,7 +100,7 @@ __device__ __forceinline__ void stage_image(bf16_t* img, const bf16_t* g, int64_
     const int r = e / CH, c = e - r * CH;
     bf16x8 v = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     if (r < S) v = *(const bf16x8*)(g + r * g_ld + c * 8);
-    *(bf16x8*)(img + r * IMG_LD + c * 8) = v;
+    *(bf16x8*)(img + r * IMG_LD<HD> + c * 8) = v;
   }
 }
 
@@ -98,6 +112,7 @@ template <typename T, int HD, int NT, bool STRUCT, bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams P) {
   constexpr bool BF = !std::is_same<T, float>::value;
   constexpr int KS = MM<T>::KS;
+  constexpr int KW = (BF && HD < KS) ? HD : 32;          // bf16, 16-wide head: half a contraction step (frag_kc)
   constexpr int ND = HD / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mdt_attn_fwd_args& a = P.f;
@@ -114,12 +129,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams P) {
   T* scratch;
   if constexpr (BF) {
     bf16_t* imgK = (bf16_t*)smem;
-    bf16_t* imgV = imgK + s_pad32 * IMG_LD;
+    bf16_t* imgV = imgK + s_pad32 * IMG_LD<HD>;
     stage_image<HD>(imgK, qkv + D, tld, S, s_pad32, tid);
     stage_image<HD>(imgV, qkv + 2 * D, tld, S, s_pad32, tid);
-    srcK = Src<T>{imgK, IMG_LD, s_pad32};
-    srcV = Src<T>{imgV, IMG_LD, s_pad32};
-    scratch = (T*)(imgV + s_pad32 * IMG_LD) + wave * 16 * scratch_ld<T>(s_pad32);
+    srcK = Src<T>{imgK, IMG_LD<HD>, s_pad32};
+    srcV = Src<T>{imgV, IMG_LD<HD>, s_pad32};
+    scratch = (T*)(imgV + s_pad32 * IMG_LD<HD>) + wave * 16 * scratch_ld<T>(s_pad32);
     __syncthreads();
   } else {
     srcK = Src<T>{qkv + D, tld, S};
@@ -150,9 +165,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams P) {
     for (int t = 0; t < NT; ++t) sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k0 = 0; k0 < HD; k0 += KS) {
-      const typename MM<T>::frag fa = frag_kc<T, false>(srcQ, q0, k0, lane);
+      const typename MM<T>::frag fa = frag_kc<T, false, KW>(srcQ, q0, k0, lane);
 #pragma unroll
-      for (int t = 0; t < NT; ++t) sc[t] = MM<T>::mma(fa, frag_kc<T, BF>(srcK, t * 16, k0, lane), sc[t]);
+      for (int t = 0; t < NT; ++t) sc[t] = MM<T>::mma(fa, frag_kc<T, BF, KW>(srcK, t * 16, k0, lane), sc[t]);
     }
     // bias + softmax (rows = (lane>>4)*4 + r, cols = t*16 + (lane&15))
     float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
@@ -233,6 +248,7 @@ template <typename T, int HD, int NT, bool STRUCT, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
   constexpr bool BF = !std::is_same<T, float>::value;
   constexpr int KS = MM<T>::KS;
+  constexpr int KW = (BF && HD < KS) ? HD : 32;          // bf16, 16-wide head: half a contraction step (frag_kc)
   constexpr int ND = HD / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mdt_attn_fwd_args& a = P.f;
@@ -256,8 +272,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
   const int nhist = STRUCT ? ((a.num_spatial + 1 + 3) & ~3) : 0;
   char* after = (char*)(s_hist + nhist);
   bf16_t* img0 = (bf16_t*)after;
-  bf16_t* img1 = img0 + (BF ? s_pad32 * IMG_LD : 0);
-  T* scratch = (T*)(img1 + (BF ? s_pad32 * IMG_LD : 0)) + wave * 16 * sld;
+  bf16_t* img1 = img0 + (BF ? s_pad32 * IMG_LD<HD> : 0);
+  T* scratch = (T*)(img1 + (BF ? s_pad32 * IMG_LD<HD> : 0)) + wave * 16 * sld;
   const Src<T> srcX{scratch, sld, 16};
 
   for (int i = tid; i < s_pad32; i += 256) {
@@ -270,8 +286,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
   if constexpr (BF) {
     stage_image<HD>(img0, qkv + D, tld, S, s_pad32, tid);
     stage_image<HD>(img1, qkv + 2 * D, tld, S, s_pad32, tid);
-    srcK = Src<T>{img0, IMG_LD, s_pad32};
-    srcV = Src<T>{img1, IMG_LD, s_pad32};
+    srcK = Src<T>{img0, IMG_LD<HD>, s_pad32};
+    srcV = Src<T>{img1, IMG_LD<HD>, s_pad32};
   } else {
     srcK = Src<T>{qkv + D, tld, S};
     srcV = Src<T>{qkv + 2 * D, tld, S};
@@ -303,12 +319,12 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
       for (int t = 0; t < NT; ++t) { sc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
       for (int k0 = 0; k0 < HD; k0 += KS) {
-        const typename MM<T>::frag fq = frag_kc<T, false>(gQ, q0, k0, lane);
-        const typename MM<T>::frag fo = frag_kc<T, false>(gDO, q0, k0, lane);
+        const typename MM<T>::frag fq = frag_kc<T, false, KW>(gQ, q0, k0, lane);
+        const typename MM<T>::frag fo = frag_kc<T, false, KW>(gDO, q0, k0, lane);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-          sc[t] = MM<T>::mma(fq, frag_kc<T, BF>(srcK, t * 16, k0, lane), sc[t]);
-          dp[t] = MM<T>::mma(fo, frag_kc<T, BF>(srcV, t * 16, k0, lane), dp[t]);
+          sc[t] = MM<T>::mma(fq, frag_kc<T, BF, KW>(srcK, t * 16, k0, lane), sc[t]);
+          dp[t] = MM<T>::mma(fo, frag_kc<T, BF, KW>(srcV, t * 16, k0, lane), dp[t]);
           if (t & 1) __builtin_amdgcn_sched_barrier(0);   // bound operand prefetch depth (registers -> occupancy)
         }
       }
@@ -383,8 +399,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
   if constexpr (BF) {
     stage_image<HD>(img0, qkv, tld, S, s_pad32, tid);
     stage_image<HD>(img1, dout, dld, S, s_pad32, tid);
-    srcQ = Src<T>{img0, IMG_LD, s_pad32};
-    srcDO = Src<T>{img1, IMG_LD, s_pad32};
+    srcQ = Src<T>{img0, IMG_LD<HD>, s_pad32};
+    srcDO = Src<T>{img1, IMG_LD<HD>, s_pad32};
     __syncthreads();
   } else {
     srcQ = gQ;
@@ -412,12 +428,12 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
       for (int t = 0; t < NT; ++t) { sc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
       for (int k0 = 0; k0 < HD; k0 += KS) {
-        const typename MM<T>::frag fk = frag_kc<T, false>(gK, key0, k0, lane);
-        const typename MM<T>::frag fv = frag_kc<T, false>(gV, key0, k0, lane);
+        const typename MM<T>::frag fk = frag_kc<T, false, KW>(gK, key0, k0, lane);
+        const typename MM<T>::frag fv = frag_kc<T, false, KW>(gV, key0, k0, lane);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-          sc[t] = MM<T>::mma(fk, frag_kc<T, BF>(srcQ, t * 16, k0, lane), sc[t]);
-          dp[t] = MM<T>::mma(fv, frag_kc<T, BF>(srcDO, t * 16, k0, lane), dp[t]);
+          sc[t] = MM<T>::mma(fk, frag_kc<T, BF, KW>(srcQ, t * 16, k0, lane), sc[t]);
+          dp[t] = MM<T>::mma(fv, frag_kc<T, BF, KW>(srcDO, t * 16, k0, lane), dp[t]);
           if (t & 1) __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -542,7 +558,7 @@ static int launch_fwd(hipStream_t st, const AttnParams& p) {
   constexpr int s_pad32 = (NT * 16 + 31) & ~31;
   constexpr bool BF = !std::is_same<T, float>::value;
   const int sld = s_pad32 + (BF ? 8 : 1);
-  const size_t lds = (size_t)4 * 16 * sld * sizeof(T) + (BF ? (size_t)2 * s_pad32 * IMG_LD * 2 : 0);
+  const size_t lds = (size_t)4 * 16 * sld * sizeof(T) + (BF ? (size_t)2 * s_pad32 * IMG_LD<HD> * 2 : 0);
   return launch_route<attn_fwd_kernel<T, HD, NT, STRUCT, DROP>>("v1", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
 }
 
@@ -553,7 +569,7 @@ static int launch_bwd(hipStream_t st, const AttnParams& p) {
   const int sld = s_pad32 + (BF ? 8 : 1);
   const int nhist = STRUCT ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
   const size_t lds = (size_t)(2 * s_pad32 + nhist) * 4 + (size_t)4 * 16 * sld * sizeof(T) +
-               (BF ? (size_t)2 * s_pad32 * IMG_LD * 2 : 0);
+               (BF ? (size_t)2 * s_pad32 * IMG_LD<HD> * 2 : 0);
   return launch_route<attn_bwd_kernel<T, HD, NT, STRUCT, DROP>>("v1", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
 }
 
@@ -571,6 +587,11 @@ static int dispatch_nt(hipStream_t st, const AttnParams& p) {
   return MDT_ERR_UNSUPPORTED;
 }
 
+template <typename T, int HD, bool BWD>
+static int dispatch_hd(hipStream_t st, const AttnParams& p) {
+  return p.f.attn_bias ? dispatch_nt<T, HD, true, BWD>(st, p) : dispatch_nt<T, HD, false, BWD>(st, p);
+}
+
 template <bool BWD>
 static int dispatch(hipStream_t st, const AttnParams& p) {
   const mdt_attn_fwd_args& a = p.f;
@@ -582,8 +603,8 @@ static int dispatch(hipStream_t st, const AttnParams& p) {
     }
   } else if (a.S > 272) return attention_long_dispatch(st, p, BWD);      // discussion trees with more than 271 comments
   if (a.dtype == MDT_BF16) {
-    if (a.hd != 64) {
-      set_error("attention(bf16): head_dim %d unsupported (64 only)", a.hd);
+    if (a.hd != 64 && a.hd != 16) {
+      set_error("attention(bf16): head_dim %d unsupported (16 or 64)", a.hd);
       return MDT_ERR_UNSUPPORTED;
     }
     // forward: register-resident P (v2) unless a plain dense bias (no structural terms), which only the kernels in this file
@@ -592,10 +613,10 @@ static int dispatch(hipStream_t st, const AttnParams& p) {
     const AttnRoute r = BWD ? attn_bwd_route(p) : dense_only ? AttnRoute::v1 : AttnRoute::v2;
     if (r == AttnRoute::v2) return attention_v2_dispatch(st, p, BWD);
     if (r != AttnRoute::v1) return attention_v3_bwd_dispatch(st, p, r);
-    return st_bias ? dispatch_nt<bf16_t, 64, true, BWD>(st, p) : dispatch_nt<bf16_t, 64, false, BWD>(st, p);
+    return a.hd == 64 ? dispatch_hd<bf16_t, 64, BWD>(st, p) : dispatch_hd<bf16_t, 16, BWD>(st, p);
   }
-  if (a.hd == 64) return st_bias ? dispatch_nt<float, 64, true, BWD>(st, p) : dispatch_nt<float, 64, false, BWD>(st, p);
-  if (a.hd == 16) return st_bias ? dispatch_nt<float, 16, true, BWD>(st, p) : dispatch_nt<float, 16, false, BWD>(st, p);
+  if (a.hd == 64) return dispatch_hd<float, 64, BWD>(st, p);
+  if (a.hd == 16) return dispatch_hd<float, 16, BWD>(st, p);
   set_error("attention(fp32): head_dim %d unsupported (16 or 64)", a.hd);
   return MDT_ERR_UNSUPPORTED;
 }

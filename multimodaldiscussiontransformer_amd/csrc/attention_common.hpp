@@ -67,7 +67,7 @@ __device__ __forceinline__ float attn_drop_scale(const DropCfg& d, int bh, int S
 }
 
 int attention_v2_dispatch(hipStream_t st, const AttnParams& p, bool bwd);
-AttnRoute attn_bwd_route(const AttnParams& p);                                   // bf16, head_dim 64: attention_v2.hip
+AttnRoute attn_bwd_route(const AttnParams& p);                                   // bf16, head_dim 16 | 64: attention_v2.hip
 int attention_v3_bwd_dispatch(hipStream_t st, const AttnParams& p, AttnRoute r);   // r: v3 | v4 | v4x | v5
 int attention_long_dispatch(hipStream_t st, const AttnParams& p, bool bwd);     // S > 272: attention_long.hip
 

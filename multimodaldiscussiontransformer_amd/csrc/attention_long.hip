@@ -252,12 +252,12 @@ int attention_long_dispatch(hipStream_t st, const AttnParams& p, bool bwd) {
               "ragged sequences nor q_limit (text / image sequences are always shorter)", a.S);
     return MDT_ERR_UNSUPPORTED;
   }
-  if (a.hd != 64) {
-    set_error("attention (long sequences): head_dim %d unsupported (64 only)", a.hd);
+  if (a.hd != 64 && a.hd != 16) {
+    set_error("attention (long sequences): head_dim %d unsupported (16 or 64)", a.hd);
     return MDT_ERR_UNSUPPORTED;
   }
-  if (a.dtype == MDT_BF16) return long_launch<bf16_t, 64>(st, p, bwd);
-  return long_launch<float, 64>(st, p, bwd);
+  if (a.dtype == MDT_BF16) return a.hd == 64 ? long_launch<bf16_t, 64>(st, p, bwd) : long_launch<bf16_t, 16>(st, p, bwd);
+  return a.hd == 64 ? long_launch<float, 64>(st, p, bwd) : long_launch<float, 16>(st, p, bwd);
 }
 
 }  // namespace mdt

@@ -15,11 +15,23 @@
 // and reduces the softmax reductions from four shuffles to two.
 // Same C ABI, same masks / structural bias / dropout semantics; attention.hip keeps the fp32
 // parity path and the bf16 kernels for a dense bias (and the backward of short structural-bias rows).
+// Head widths: 64 (BERT, ViT, the graph heads of the larger models) and 16 (the graph heads of Tiny mDT: D 128,
+// 8 heads).  The forward and the two-pass backward kernels (v2, v3) take both — a 16-wide head is half a K = 32
+// contraction step (v2_ks) and one 16-row output tile of the transposed products; the one-pass backward kernels
+// (v4, v4x, v5) are written for 64.  32 would need a launch line only (v2_ld / v2_ks cover it); it is not instantiated.
 #include "attention_common.hpp"
 
 namespace mdt {
 
-constexpr int V2_LD = 72;  // LDS image row stride in elements (144 B)
+// LDS image row stride in elements.  64-wide heads: 64 + 8 (144 B).  16-wide heads: 16, no padding — a 32-byte row is two
+// 16-byte slots, and with the lane groups of the hardware both kinds of read are conflict-free as they are: a
+// ds_read_b128 group holds rows 0-3 and 12-15 with chunk 0 and rows 4-11 with chunk 1 (slots 2 row + chunk: sixteen
+// different ones), and a 32-lane half of ds_read_b64_tr_b16 reads eight consecutive rows = 256 contiguous bytes.  Any
+// padding (48-byte rows: five slots shared by two rows of a b128 group) is worse, and the images are 4.5 x smaller than
+// with the 144-byte rows (S = 17: 2 KiB instead of 9 KiB for K and V).
+template <int HD> constexpr int v2_ld = HD >= 32 ? HD + 8 : HD;
+// K = 32 contraction steps over a head.  A 16-wide head is half a step: lanes with lane >> 4 >= 2 (k = 16 .. 31) feed zeros.
+template <int HD> constexpr int v2_ks = (HD + 31) / 32;
 
 template <int HD>
 __device__ __forceinline__ void v2_stage(bf16_t* img, const bf16_t* g, int64_t g_ld, int S, int rows_pad, int tid, int nthr = 256) {
@@ -28,7 +40,7 @@ __device__ __forceinline__ void v2_stage(bf16_t* img, const bf16_t* g, int64_t g
     const int r = e / CH, c = e - r * CH;
     bf16x8 v = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     if (r < S) v = *(const bf16x8*)(g + r * g_ld + c * 8);
-    *(bf16x8*)(img + r * V2_LD + c * 8) = v;
+    *(bf16x8*)(img + r * v2_ld<HD> + c * 8) = v;
   }
 }
 
@@ -56,7 +68,7 @@ __device__ __forceinline__ void v2_stage_put(bf16_t* img, const bf16x8 (&v)[NCH]
 #pragma unroll
   for (int j = 0; j < NCH; ++j) {
     const int e = tid + j * nthr, r = e / CH, c = e - r * CH;
-    bf16_t* dst = e < rows_pad * CH ? img + r * V2_LD + c * 8 : spare;
+    bf16_t* dst = e < rows_pad * CH ? img + r * v2_ld<HD> + c * 8 : spare;
     *(bf16x8*)dst = r < S ? v[j] : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
   }
 }
@@ -79,22 +91,38 @@ __device__ __forceinline__ float key_only_bias_of(const BiasCtx& b, int key, Key
 }
 
 // A / B fragment with k along the contiguous axis: element(rc, k) = p[rc*ld + k]
+// Heads narrower than a K = 32 step: the columns past the head belong to the next head (or the next row), so no lane
+// reads them — lanes whose chunk lies past the head re-read a chunk of their own row instead (v2_chunk).  Every product
+// pairs an image fragment with a fragment from global memory; the latter carries the zeros for those lanes, the image
+// side keeps the re-read values (finite wherever the head is) and skips the select.
+template <int HD>
+__device__ __forceinline__ int v2_chunk(int lane) {
+  static_assert(HD % 32 == 0 || HD == 16, "a head is whole K = 32 steps, or half of one");
+  return HD % 32 == 0 ? lane >> 4 : (lane >> 4) & (HD / 8 - 1);
+}
+template <int HD>
 __device__ __forceinline__ bf16x8 v2_frag_lds(const bf16_t* img, int rc0, int k0, int lane) {
-  const bf16_t* a = img + (rc0 + (lane & 15)) * V2_LD + k0 + 8 * (lane >> 4);
+  const bf16_t* a = img + (rc0 + (lane & 15)) * v2_ld<HD> + k0 + 8 * v2_chunk<HD>(lane);
   return *(const __attribute__((address_space(3))) bf16x8*)LDS_PTR(a);
 }
+template <int HD>
 __device__ __forceinline__ bf16x8 v2_frag_glb(const bf16_t* p, int64_t ld, int rows, int rc0, int k0, int lane) {
   int rc = rc0 + (lane & 15);
   if (rc > rows - 1) rc = rows - 1;
-  return *(const bf16x8*)(p + rc * ld + k0 + 8 * (lane >> 4));
+  bf16x8 v = *(const bf16x8*)(p + rc * ld + k0 + 8 * v2_chunk<HD>(lane));
+  if constexpr (HD % 32 != 0) {
+    if (k0 + 8 * (lane >> 4) >= HD) v = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+  }
+  return v;
 }
 // A operand X^T[d][k] for a K = 32 step whose k index runs over rows {t0*16 + 4g + j} (j < 4)
-// and {(t0+1)*16 + 4g + j - 4} of the row-major image X[row][d]
+// and {(t0+1)*16 + 4g + j - 4} of the row-major image X[row][d]; d0 + 16 <= HD (a 16-wide head has the one tile d0 = 0)
+template <int HD>
 __device__ __forceinline__ bf16x8 v2_frag_tr(const bf16_t* img, int t0, int d0, int lane) {
   const int g = lane >> 4, q4 = (lane >> 2) & 3, pp = lane & 3;
-  const bf16_t* a = img + (t0 * 16 + 4 * g + q4) * V2_LD + d0 + pp * 4;
+  const bf16_t* a = img + (t0 * 16 + 4 * g + q4) * v2_ld<HD> + d0 + pp * 4;
   const bf16x4 lo = lds_read_tr16(a);
-  const bf16x4 hi = lds_read_tr16(a + 16 * V2_LD);
+  const bf16x4 hi = lds_read_tr16(a + 16 * v2_ld<HD>);
   return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 // B operand from two accumulator tiles (rows = k index)
@@ -161,8 +189,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
   const bf16_t* qkv = (const bf16_t*)a.qkv + row0 * a.ld_qkv + h * HD;
   const int64_t tld = a.pos_stride * a.ld_qkv;
   bf16_t* imgK = (bf16_t*)smem;
-  bf16_t* imgV = imgK + S_PAD * V2_LD;
-  float* s_kb = (float*)(imgV + S_PAD * V2_LD);   // key-only bias (0 / -inf), [S_PAD]
+  bf16_t* imgV = imgK + S_PAD * v2_ld<HD>;
+  float* s_kb = (float*)(imgV + S_PAD * v2_ld<HD>);   // key-only bias (0 / -inf), [S_PAD]
   BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
   // Ragged sequences: key tiles past this sequence's length are staged as zeros, their scores come out of the
   // (unguarded: a guard there costs the compiler 80 registers) MFMA loop as exact zeros and every later
@@ -174,13 +202,13 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
   constexpr int MAXT = (NT + NW - 1) / NW;
   int n_qt = (S + 15) >> 4;
   if (a.q_limit > 0 && ((a.q_limit + 15) >> 4) < n_qt) n_qt = (a.q_limit + 15) >> 4;   // only these query tiles are needed
-  bf16x8 fq_all[MAXT][HD / 32];
+  bf16x8 fq_all[MAXT][v2_ks<HD>];
 #pragma unroll
   for (int k = 0; k < MAXT; ++k) {
     const int qt_k = wave + NW * k;
     if (qt_k < n_qt) {
 #pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) fq_all[k][ks] = v2_frag_glb(qkv, tld, S, qt_k * 16, ks * 32, lane);
+      for (int ks = 0; ks < v2_ks<HD>; ++ks) fq_all[k][ks] = v2_frag_glb<HD>(qkv, tld, S, qt_k * 16, ks * 32, lane);
     }
   }
   // ... and so are all K / V chunks and mask bytes of this thread (v2_stage_req): one global latency before the barrier
@@ -209,18 +237,18 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
     const int q0 = qt * 16;
     const int q = q0 + c;
     const int qc = q < S ? q : S - 1;
-    bf16x8 fq[HD / 32];
+    bf16x8 fq[v2_ks<HD>];
 #pragma unroll
-    for (int ks = 0; ks < HD / 32; ++ks) fq[ks] = fq_all[k][ks];
+    for (int ks = 0; ks < v2_ks<HD>; ++ks) fq[ks] = fq_all[k][ks];
     f32x4 sc[2 * NP];
 #pragma unroll
     for (int t = 0; t < 2 * NP; ++t) sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) {
-        sc[t] = mfma_bf16(v2_frag_lds(imgK, t * 16, ks * 32, lane), fq[ks], sc[t]);
-        if (ks == HD / 32 - 1 && (t & 1)) __builtin_amdgcn_sched_barrier(0);   // bound operand prefetch depth (registers)
+      for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+        sc[t] = mfma_bf16(v2_frag_lds<HD>(imgK, t * 16, ks * 32, lane), fq[ks], sc[t]);
+        if (ks == v2_ks<HD> - 1 && (t & 1)) __builtin_amdgcn_sched_barrier(0);   // bound operand prefetch depth (registers)
       }
     }
     float mx = -INFINITY;
@@ -276,15 +304,23 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
       if (2 * pi >= ntk) continue;
       const bf16x8 fp = v2_pack(sc[2 * pi], sc[2 * pi + 1]);
 #pragma unroll
-      for (int d = 0; d < ND; ++d) o[d] = mfma_bf16(v2_frag_tr(imgV, 2 * pi, d * 16, lane), fp, o[d]);
+      for (int d = 0; d < ND; ++d) o[d] = mfma_bf16(v2_frag_tr<HD>(imgV, 2 * pi, d * 16, lane), fp, o[d]);
       __builtin_amdgcn_sched_barrier(0);
     }
-    static_assert(ND == 4, "rows4_exchange: 64-column rows");
-    const Row32 ov = rows4_exchange(o, inv);      // inv is per query = per lane column c: the same in the four lanes that trade
-    if (q < S) {
-      bf16_t* orow = (bf16_t*)a.out + (row0 + (int64_t)q * a.pos_stride) * a.ld_out + h * HD + rows4_off(g);
-      *(bf16x8*)orow = ov.a;
-      *(bf16x8*)(orow + 32) = ov.b;
+    if constexpr (ND == 4) {
+      const Row32 ov = rows4_exchange(o, inv);      // inv is per query = per lane column c: the same in the four lanes that trade
+      if (q < S) {
+        bf16_t* orow = (bf16_t*)a.out + (row0 + (int64_t)q * a.pos_stride) * a.ld_out + h * HD + rows4_off(g);
+        *(bf16x8*)orow = ov.a;
+        *(bf16x8*)(orow + 32) = ov.b;
+      }
+    } else {
+      // one 16-column tile: lane (g, c) holds columns 4 g ... + 3 of row c — the four lanes of a row write its 32 bytes
+      static_assert(ND == 1, "16- or 64-column rows");
+      if (q < S) {
+        bf16_t* orow = (bf16_t*)a.out + (row0 + (int64_t)q * a.pos_stride) * a.ld_out + h * HD + 4 * g;
+        *(bf16x4*)orow = bf16x4{(bf16_t)(o[0][0] * inv), (bf16_t)(o[0][1] * inv), (bf16_t)(o[0][2] * inv), (bf16_t)(o[0][3] * inv)};
+      }
     }
   }
 }
@@ -308,8 +344,8 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
   bf16_t* dqkv = (bf16_t*)P.dqkv + row0 * P.ld_dqkv + h * HD;
   const int64_t tld = a.pos_stride * a.ld_qkv, dld = a.pos_stride * P.ld_dout, gld = a.pos_stride * P.ld_dqkv;
   bf16_t* img0 = (bf16_t*)smem;
-  bf16_t* img1 = img0 + S_PAD * V2_LD;
-  float* s_kb = (float*)(img1 + S_PAD * V2_LD);
+  bf16_t* img1 = img0 + S_PAD * v2_ld<HD>;
+  float* s_kb = (float*)(img1 + S_PAD * v2_ld<HD>);
   float* s_lse = s_kb + S_PAD;
   float* s_delta = s_lse + S_PAD;
   float* s_hist = s_delta + S_PAD;
@@ -334,11 +370,11 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
     const int q = q0 + c;
     const bool qok = q < S;
     const int qc = qok ? q : S - 1;
-    bf16x8 fq[HD / 32], fo[HD / 32];
+    bf16x8 fq[v2_ks<HD>], fo[v2_ks<HD>];
 #pragma unroll
-    for (int ks = 0; ks < HD / 32; ++ks) {
-      fq[ks] = v2_frag_glb(qkv, tld, S, q0, ks * 32, lane);
-      fo[ks] = v2_frag_glb(dout, dld, S, q0, ks * 32, lane);
+    for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+      fq[ks] = v2_frag_glb<HD>(qkv, tld, S, q0, ks * 32, lane);
+      fo[ks] = v2_frag_glb<HD>(dout, dld, S, q0, ks * 32, lane);
     }
     f32x4 sc[2 * NP], dp[2 * NP];
 #pragma unroll
@@ -346,10 +382,10 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) {
-        sc[t] = mfma_bf16(v2_frag_lds(img0, t * 16, ks * 32, lane), fq[ks], sc[t]);
-        dp[t] = mfma_bf16(v2_frag_lds(img1, t * 16, ks * 32, lane), fo[ks], dp[t]);
-        if (ks == HD / 32 - 1) __builtin_amdgcn_sched_barrier(0);
+      for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+        sc[t] = mfma_bf16(v2_frag_lds<HD>(img0, t * 16, ks * 32, lane), fq[ks], sc[t]);
+        dp[t] = mfma_bf16(v2_frag_lds<HD>(img1, t * 16, ks * 32, lane), fo[ks], dp[t]);
+        if (ks == v2_ks<HD> - 1) __builtin_amdgcn_sched_barrier(0);
       }
     const float l = s_lse[qc];
     float del = 0.f;
@@ -395,7 +431,7 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
     for (int pi = 0; pi < NP; ++pi) {
       const bf16x8 fs = v2_pack(sc[2 * pi], sc[2 * pi + 1]);
 #pragma unroll
-      for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr(img0, 2 * pi, d * 16, lane), fs, dq[d]);
+      for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr<HD>(img0, 2 * pi, d * 16, lane), fs, dq[d]);
       __builtin_amdgcn_sched_barrier(0);
     }
     if (qok) {
@@ -427,11 +463,11 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
     const int key = key0 + c;
     const bool kok = key < S;
     const float kb = s_kb[key];
-    bf16x8 fk[HD / 32], fv[HD / 32];
+    bf16x8 fk[v2_ks<HD>], fv[v2_ks<HD>];
 #pragma unroll
-    for (int ks = 0; ks < HD / 32; ++ks) {
-      fk[ks] = v2_frag_glb(qkv + D, tld, S, key0, ks * 32, lane);
-      fv[ks] = v2_frag_glb(qkv + 2 * D, tld, S, key0, ks * 32, lane);
+    for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+      fk[ks] = v2_frag_glb<HD>(qkv + D, tld, S, key0, ks * 32, lane);
+      fv[ks] = v2_frag_glb<HD>(qkv + 2 * D, tld, S, key0, ks * 32, lane);
     }
     f32x4 sc[2 * NP], dp[2 * NP];
 #pragma unroll
@@ -439,10 +475,10 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) {
-        sc[t] = mfma_bf16(v2_frag_lds(img0, t * 16, ks * 32, lane), fk[ks], sc[t]);   // S[q][key]
-        dp[t] = mfma_bf16(v2_frag_lds(img1, t * 16, ks * 32, lane), fv[ks], dp[t]);   // dP[q][key] = dO V^T
-        if (ks == HD / 32 - 1) __builtin_amdgcn_sched_barrier(0);
+      for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+        sc[t] = mfma_bf16(v2_frag_lds<HD>(img0, t * 16, ks * 32, lane), fk[ks], sc[t]);   // S[q][key]
+        dp[t] = mfma_bf16(v2_frag_lds<HD>(img1, t * 16, ks * 32, lane), fv[ks], dp[t]);   // dP[q][key] = dO V^T
+        if (ks == v2_ks<HD> - 1) __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -474,8 +510,8 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
       const bf16x8 fs = v2_pack(dp[2 * pi], dp[2 * pi + 1]);
 #pragma unroll
       for (int d = 0; d < ND; ++d) {
-        dv[d] = mfma_bf16(v2_frag_tr(img1, 2 * pi, d * 16, lane), fp, dv[d]);   // dO^T P
-        dk[d] = mfma_bf16(v2_frag_tr(img0, 2 * pi, d * 16, lane), fs, dk[d]);   // Q^T dS
+        dv[d] = mfma_bf16(v2_frag_tr<HD>(img1, 2 * pi, d * 16, lane), fp, dv[d]);   // dO^T P
+        dk[d] = mfma_bf16(v2_frag_tr<HD>(img0, 2 * pi, d * 16, lane), fs, dk[d]);   // Q^T dS
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -519,8 +555,8 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
   const int64_t tld = a.pos_stride * a.ld_qkv, dld = a.pos_stride * P.ld_dout, old_ = a.pos_stride * a.ld_out,
                 gld = a.pos_stride * P.ld_dqkv;
   bf16_t* img0 = (bf16_t*)smem;
-  bf16_t* img1 = img0 + s_pad * V2_LD;
-  float* s_kb = (float*)(img1 + s_pad * V2_LD);
+  bf16_t* img1 = img0 + s_pad * v2_ld<HD>;
+  float* s_kb = (float*)(img1 + s_pad * v2_ld<HD>);
   float* s_lse = s_kb + s_pad;
   float* s_delta = s_lse + s_pad;
   float* s_hist = s_delta + s_pad;
@@ -531,12 +567,12 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
   // Latency hiding (the waves of this kernel sat in s_waitcnt / s_barrier for half to two thirds of their cycles):
   // the Q / dO fragments of a wave's first query tile are requested before K / V are staged, and every later
   // tile's fragments while the previous tile is being computed; pass B treats its K / V fragments the same way.
-  bf16x8 fq_n[HD / 32], fo_n[HD / 32];
+  bf16x8 fq_n[v2_ks<HD>], fo_n[v2_ks<HD>];
   if constexpr (PF) {
 #pragma unroll
-    for (int ks = 0; ks < HD / 32; ++ks) {
-      fq_n[ks] = v2_frag_glb(qkv, tld, S, wave * 16, ks * 32, lane);
-      fo_n[ks] = v2_frag_glb(dout, dld, S, wave * 16, ks * 32, lane);
+    for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+      fq_n[ks] = v2_frag_glb<HD>(qkv, tld, S, wave * 16, ks * 32, lane);
+      fo_n[ks] = v2_frag_glb<HD>(dout, dld, S, wave * 16, ks * 32, lane);
     }
   }
   v2_stage<HD>(img0, qkv + D, tld, S, s_live, tid, nthr);      // K
@@ -582,17 +618,17 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
     const int q = q0 + c;
     const bool qok = q < S;
     const int qc = qok ? q : S - 1;
-    bf16x8 fq[HD / 32], fo[HD / 32];
+    bf16x8 fq[v2_ks<HD>], fo[v2_ks<HD>];
 #pragma unroll
-    for (int ks = 0; ks < HD / 32; ++ks) {
+    for (int ks = 0; ks < v2_ks<HD>; ++ks) {
       if constexpr (PF) { fq[ks] = fq_n[ks]; fo[ks] = fo_n[ks]; }
-      else { fq[ks] = v2_frag_glb(qkv, tld, S, q0, ks * 32, lane); fo[ks] = v2_frag_glb(dout, dld, S, q0, ks * 32, lane); }
+      else { fq[ks] = v2_frag_glb<HD>(qkv, tld, S, q0, ks * 32, lane); fo[ks] = v2_frag_glb<HD>(dout, dld, S, q0, ks * 32, lane); }
     }
     if (PF && qt + nw < n_tq) {
 #pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) {
-        fq_n[ks] = v2_frag_glb(qkv, tld, S, q0 + 16 * nw, ks * 32, lane);
-        fo_n[ks] = v2_frag_glb(dout, dld, S, q0 + 16 * nw, ks * 32, lane);
+      for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+        fq_n[ks] = v2_frag_glb<HD>(qkv, tld, S, q0 + 16 * nw, ks * 32, lane);
+        fo_n[ks] = v2_frag_glb<HD>(dout, dld, S, q0 + 16 * nw, ks * 32, lane);
       }
     }
     const float l2 = s_lse[qc], del = s_delta[qc];
@@ -608,10 +644,10 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int ks = 0; ks < HD / 32; ++ks) {
-          sc[t] = mfma_bf16(v2_frag_lds(img0, (t0 + t) * 16, ks * 32, lane), fq[ks], sc[t]);
-          dp[t] = mfma_bf16(v2_frag_lds(img1, (t0 + t) * 16, ks * 32, lane), fo[ks], dp[t]);
-          if (ks == HD / 32 - 1 && (t & 1)) __builtin_amdgcn_sched_barrier(0);
+        for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+          sc[t] = mfma_bf16(v2_frag_lds<HD>(img0, (t0 + t) * 16, ks * 32, lane), fq[ks], sc[t]);
+          dp[t] = mfma_bf16(v2_frag_lds<HD>(img1, (t0 + t) * 16, ks * 32, lane), fo[ks], dp[t]);
+          if (ks == v2_ks<HD> - 1 && (t & 1)) __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -653,7 +689,7 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
       for (int pi = 0; pi < 2; ++pi) {
         const bf16x8 fs = v2_pack(sc[2 * pi], sc[2 * pi + 1]);
 #pragma unroll
-        for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr(img0, t0 + 2 * pi, d * 16, lane), fs, dq[d]);
+        for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr<HD>(img0, t0 + 2 * pi, d * 16, lane), fs, dq[d]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -665,12 +701,12 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
         *(bf16x4*)(orow + d * 16) = bf16x4{(bf16_t)(dq[d][0] * os), (bf16_t)(dq[d][1] * os), (bf16_t)(dq[d][2] * os), (bf16_t)(dq[d][3] * os)};
     }
   }
-  bf16x8 fk_n[HD / 32], fv_n[HD / 32];
+  bf16x8 fk_n[v2_ks<HD>], fv_n[v2_ks<HD>];
   if constexpr (PF) {
 #pragma unroll
-    for (int ks = 0; ks < HD / 32; ++ks) {
-      fk_n[ks] = v2_frag_glb(qkv + D, tld, S, wave * 16, ks * 32, lane);
-      fv_n[ks] = v2_frag_glb(qkv + 2 * D, tld, S, wave * 16, ks * 32, lane);
+    for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+      fk_n[ks] = v2_frag_glb<HD>(qkv + D, tld, S, wave * 16, ks * 32, lane);
+      fv_n[ks] = v2_frag_glb<HD>(qkv + 2 * D, tld, S, wave * 16, ks * 32, lane);
     }
   }
   __syncthreads();   // K / V images are free
@@ -699,17 +735,17 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
     const int key = key0 + c;
     const bool kok = key < S;
     const float kb = s_kb[key];
-    bf16x8 fk[HD / 32], fv[HD / 32];
+    bf16x8 fk[v2_ks<HD>], fv[v2_ks<HD>];
 #pragma unroll
-    for (int ks = 0; ks < HD / 32; ++ks) {
+    for (int ks = 0; ks < v2_ks<HD>; ++ks) {
       if constexpr (PF) { fk[ks] = fk_n[ks]; fv[ks] = fv_n[ks]; }
-      else { fk[ks] = v2_frag_glb(qkv + D, tld, S, key0, ks * 32, lane); fv[ks] = v2_frag_glb(qkv + 2 * D, tld, S, key0, ks * 32, lane); }
+      else { fk[ks] = v2_frag_glb<HD>(qkv + D, tld, S, key0, ks * 32, lane); fv[ks] = v2_frag_glb<HD>(qkv + 2 * D, tld, S, key0, ks * 32, lane); }
     }
     if (PF && kt + nw < n_t) {
 #pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) {
-        fk_n[ks] = v2_frag_glb(qkv + D, tld, S, key0 + 16 * nw, ks * 32, lane);
-        fv_n[ks] = v2_frag_glb(qkv + 2 * D, tld, S, key0 + 16 * nw, ks * 32, lane);
+      for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+        fk_n[ks] = v2_frag_glb<HD>(qkv + D, tld, S, key0 + 16 * nw, ks * 32, lane);
+        fv_n[ks] = v2_frag_glb<HD>(qkv + 2 * D, tld, S, key0 + 16 * nw, ks * 32, lane);
       }
     }
     const uint32_t kh = base_rp + (uint32_t)(key >> 1);
@@ -724,10 +760,10 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int ks = 0; ks < HD / 32; ++ks) {
-          sc[t] = mfma_bf16(v2_frag_lds(img0, (t0 + t) * 16, ks * 32, lane), fk[ks], sc[t]);   // S[q][key]
-          dp[t] = mfma_bf16(v2_frag_lds(img1, (t0 + t) * 16, ks * 32, lane), fv[ks], dp[t]);   // dP[q][key]
-          if (ks == HD / 32 - 1 && (t & 1)) __builtin_amdgcn_sched_barrier(0);
+        for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+          sc[t] = mfma_bf16(v2_frag_lds<HD>(img0, (t0 + t) * 16, ks * 32, lane), fk[ks], sc[t]);   // S[q][key]
+          dp[t] = mfma_bf16(v2_frag_lds<HD>(img1, (t0 + t) * 16, ks * 32, lane), fv[ks], dp[t]);   // dP[q][key]
+          if (ks == v2_ks<HD> - 1 && (t & 1)) __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -763,8 +799,8 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
         const bf16x8 fs = v2_pack(dp[2 * pi], dp[2 * pi + 1]);
 #pragma unroll
         for (int d = 0; d < ND; ++d) {
-          dv[d] = mfma_bf16(v2_frag_tr(img1, t0 + 2 * pi, d * 16, lane), fp, dv[d]);
-          dk[d] = mfma_bf16(v2_frag_tr(img0, t0 + 2 * pi, d * 16, lane), fs, dk[d]);
+          dv[d] = mfma_bf16(v2_frag_tr<HD>(img1, t0 + 2 * pi, d * 16, lane), fp, dv[d]);
+          dk[d] = mfma_bf16(v2_frag_tr<HD>(img0, t0 + 2 * pi, d * 16, lane), fs, dk[d]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -845,8 +881,8 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
   const int64_t tld = a.pos_stride * a.ld_qkv, dld = a.pos_stride * P.ld_dout, old_ = a.pos_stride * a.ld_out,
                 gld = a.pos_stride * P.ld_dqkv;
   bf16_t* img0 = (bf16_t*)smem;                       // Q, then K
-  bf16_t* img1 = img0 + rows_img * V2_LD;              // dO
-  float* s_kb = (float*)(img1 + rows_img * V2_LD);
+  bf16_t* img1 = img0 + rows_img * v2_ld<HD>;              // dO
+  float* s_kb = (float*)(img1 + rows_img * v2_ld<HD>);
   float* s_lse = s_kb + rows_img;
   float* s_delta = s_lse + rows_img;                   // EXACT: [8 key tiles][rows_img] partial row sums, one slab per wave
   bf16_t* dsT = (bf16_t*)(s_delta + rows_img * (EXACT ? 8 : 1));   // [16 * tiles][ldq]: dS^T, key-major
@@ -862,12 +898,12 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
   // staging loops this replaces waited for every load inside its own iteration — nine global latencies one after the
   // other per (sequence, head), which was most of the 22 us such an item lived (5-6 us of it arithmetic).
   const int kt = wave, key0 = kt * 16;
-  bf16x8 fk[HD / 32], fv[HD / 32];
+  bf16x8 fk[v2_ks<HD>], fv[v2_ks<HD>];
   if (kt < n_t) {
 #pragma unroll
-    for (int ks = 0; ks < HD / 32; ++ks) {
-      fk[ks] = v2_frag_glb(qkv + D, tld, S, key0, ks * 32, lane);
-      fv[ks] = v2_frag_glb(qkv + 2 * D, tld, S, key0, ks * 32, lane);
+    for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+      fk[ks] = v2_frag_glb<HD>(qkv + D, tld, S, key0, ks * 32, lane);
+      fv[ks] = v2_frag_glb<HD>(qkv + 2 * D, tld, S, key0, ks * 32, lane);
     }
   }
   {
@@ -894,8 +930,8 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
       if (e < rows_live * 8) {
         const bf16x8 z = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
         const bf16x8 gv = r < S ? cg[j] : z;
-        *(bf16x8*)(img0 + r * V2_LD + c8 * 8) = r < S ? cq[j] : z;
-        *(bf16x8*)(img1 + r * V2_LD + c8 * 8) = gv;
+        *(bf16x8*)(img0 + r * v2_ld<HD> + c8 * 8) = r < S ? cq[j] : z;
+        *(bf16x8*)(img1 + r * v2_ld<HD> + c8 * 8) = gv;
         float de = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) de += (float)co[j][k] * (float)gv[k];
@@ -943,9 +979,9 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
 #pragma unroll
           for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int ks = 0; ks < HD / 32; ++ks) {
-              pA[pr][t] = mfma_bf16(v2_frag_lds(img0, (t0 + t) * 16, ks * 32, lane), fk[ks], pA[pr][t]);   // S[q][key]
-              dA[pr][t] = mfma_bf16(v2_frag_lds(img1, (t0 + t) * 16, ks * 32, lane), fv[ks], dA[pr][t]);   // dP[q][key]
+            for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+              pA[pr][t] = mfma_bf16(v2_frag_lds<HD>(img0, (t0 + t) * 16, ks * 32, lane), fk[ks], pA[pr][t]);   // S[q][key]
+              dA[pr][t] = mfma_bf16(v2_frag_lds<HD>(img1, (t0 + t) * 16, ks * 32, lane), fv[ks], dA[pr][t]);   // dP[q][key]
             }
 #pragma unroll
           for (int t = 0; t < 2; ++t) {
@@ -1004,8 +1040,8 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
           if (t0 + 1 < n_tq) *(bf16x4*)(ds_row + t0 * 16 + 16) = bf16x4{fs[4], fs[5], fs[6], fs[7]};
 #pragma unroll
           for (int d = 0; d < ND; ++d) {
-            dv[d] = mfma_bf16(v2_frag_tr(img1, t0, d * 16, lane), fp, dv[d]);
-            dk[d] = mfma_bf16(v2_frag_tr(img0, t0, d * 16, lane), fs, dk[d]);
+            dv[d] = mfma_bf16(v2_frag_tr<HD>(img1, t0, d * 16, lane), fp, dv[d]);
+            dk[d] = mfma_bf16(v2_frag_tr<HD>(img0, t0, d * 16, lane), fs, dk[d]);
           }
         }
       }
@@ -1018,9 +1054,9 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int ks = 0; ks < HD / 32; ++ks) {
-          sc[t] = mfma_bf16(v2_frag_lds(img0, (t0 + t) * 16, ks * 32, lane), fk[ks], sc[t]);   // S[q][key]
-          dp[t] = mfma_bf16(v2_frag_lds(img1, (t0 + t) * 16, ks * 32, lane), fv[ks], dp[t]);   // dP[q][key]
+        for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+          sc[t] = mfma_bf16(v2_frag_lds<HD>(img0, (t0 + t) * 16, ks * 32, lane), fk[ks], sc[t]);   // S[q][key]
+          dp[t] = mfma_bf16(v2_frag_lds<HD>(img1, (t0 + t) * 16, ks * 32, lane), fv[ks], dp[t]);   // dP[q][key]
         }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1054,8 +1090,8 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
       if (t0 + 1 < n_tq) *(bf16x4*)(ds_row + t0 * 16 + 16) = bf16x4{fs[4], fs[5], fs[6], fs[7]};
 #pragma unroll
       for (int d = 0; d < ND; ++d) {
-        dv[d] = mfma_bf16(v2_frag_tr(img1, t0, d * 16, lane), fp, dv[d]);
-        dk[d] = mfma_bf16(v2_frag_tr(img0, t0, d * 16, lane), fs, dk[d]);
+        dv[d] = mfma_bf16(v2_frag_tr<HD>(img1, t0, d * 16, lane), fp, dv[d]);
+        dk[d] = mfma_bf16(v2_frag_tr<HD>(img0, t0, d * 16, lane), fs, dk[d]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -1079,7 +1115,7 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
   __syncthreads();   // every dS^T tile is in LDS; the Q / dO images are free
   if (kt < n_t) {
 #pragma unroll
-    for (int ks = 0; ks < HD / 32; ++ks) *(bf16x8*)(img0 + (key0 + c) * V2_LD + ks * 32 + 8 * g) = fk[ks];
+    for (int ks = 0; ks < v2_ks<HD>; ++ks) *(bf16x8*)(img0 + (key0 + c) * v2_ld<HD> + ks * 32 + 8 * g) = fk[ks];
   }
   __syncthreads();
   // ------------------------------------------------------------------ phase 2 (queries on lanes): dQ^T = K^T dS^T
@@ -1091,7 +1127,7 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
     for (int pk = 0; pk < n_pair_k; ++pk) {
       const bf16x8 fs = v2_frag_tr_ld(dsT, ldq, 2 * pk, qt * 16, lane, 2 * pk + 1 < n_t);
 #pragma unroll
-      for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr(img0, 2 * pk, d * 16, lane), fs, dq[d]);
+      for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr<HD>(img0, 2 * pk, d * 16, lane), fs, dq[d]);
     }
     const Row32 qv = rows4_exchange(dq, a.scale * ik);
     if (q < S) {
@@ -1134,7 +1170,7 @@ __global__ __launch_bounds__(512) void attn_bwd_v4x_kernel(AttnParams P, int row
 // / K 67, requests exposed 105.
 template <int HD, bool DROP, int NU>
 __device__ __forceinline__ void v5_phase1(const AttnParams& P, const bf16_t* img0, const bf16_t* img1, const float* s_kb, const float* s_lse,
-                                          const float* s_delta, bf16_t* dsT, int ldq, const bf16x8 (&wk)[2][HD / 32], const bf16x8 (&wv)[2][HD / 32],
+                                          const float* s_delta, bf16_t* dsT, int ldq, const bf16x8 (&wk)[2][v2_ks<HD>], const bf16x8 (&wv)[2][v2_ks<HD>],
                                           int wave, int lane, int S, int SL, int drop_bh, int n_tq, bf16_t* dqkv, int64_t gld, int D, float ik) {
   constexpr int ND = HD / 16;
   const mdt_attn_fwd_args& a = P.f;
@@ -1167,8 +1203,8 @@ __device__ __forceinline__ void v5_phase1(const AttnParams& P, const bf16_t* img
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) {
-        const bf16x8 aq = v2_frag_lds(img0, (t0 + t) * 16, ks * 32, lane), ao = v2_frag_lds(img1, (t0 + t) * 16, ks * 32, lane);
+      for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+        const bf16x8 aq = v2_frag_lds<HD>(img0, (t0 + t) * 16, ks * 32, lane), ao = v2_frag_lds<HD>(img1, (t0 + t) * 16, ks * 32, lane);
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
           sc[u][t] = mfma_bf16(aq, wk[u][ks], sc[u][t]);   // S[q][key]
@@ -1217,7 +1253,7 @@ __device__ __forceinline__ void v5_phase1(const AttnParams& P, const bf16_t* img
     }
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
-      const bf16x8 to = v2_frag_tr(img1, t0, d * 16, lane), tq = v2_frag_tr(img0, t0, d * 16, lane);
+      const bf16x8 to = v2_frag_tr<HD>(img1, t0, d * 16, lane), tq = v2_frag_tr<HD>(img0, t0, d * 16, lane);
 #pragma unroll
       for (int u = 0; u < NU; ++u) {
         dv[u][d] = mfma_bf16(to, fp[u], dv[u][d]);
@@ -1266,8 +1302,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int SL = a.S, D = a.H * HD;
   const int64_t tld = a.pos_stride * a.ld_qkv, dld = a.pos_stride * P.ld_dout, old_ = a.pos_stride * a.ld_out, gld = a.pos_stride * P.ld_dqkv;
   bf16_t* img0 = (bf16_t*)smem;                       // Q, then K
-  bf16_t* img1 = img0 + rows_img * V2_LD;              // dO
-  float* s_kb = (float*)(img1 + rows_img * V2_LD);
+  bf16_t* img1 = img0 + rows_img * v2_ld<HD>;              // dO
+  float* s_kb = (float*)(img1 + rows_img * v2_ld<HD>);
   float* s_lse = s_kb + rows_img;
   float* s_delta = s_lse + rows_img;
   bf16_t* dsT = (bf16_t*)(s_delta + rows_img);         // [16 * tiles][ldq]: dS^T, key-major
@@ -1298,7 +1334,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   bf16x8 cq[NCH], cg[NCH], co[NCH];
   float lv = 0.f;
   KeyBytes kbv{1, 0};
-  bf16x8 wk[2][HD / 32], wv[2][HD / 32];
+  bf16x8 wk[2][v2_ks<HD>], wv[2][v2_ks<HD>];
   auto request_rows = [&](int tid) {           // unconditional, clamped: see v2_stage_req
     if (S > 0) {
       const bf16_t* qkv = (const bf16_t*)a.qkv + row0 * a.ld_qkv + h * HD;
@@ -1326,9 +1362,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int ks = 0; ks < HD / 32; ++ks) {
-          wk[u][ks] = v2_frag_glb(qkv + D, tld, S, (wave + 8 * u) * 16, ks * 32, lane);      // rows clamp to S - 1: a tile past n_t reads valid memory
-          wv[u][ks] = v2_frag_glb(qkv + 2 * D, tld, S, (wave + 8 * u) * 16, ks * 32, lane);
+        for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+          wk[u][ks] = v2_frag_glb<HD>(qkv + D, tld, S, (wave + 8 * u) * 16, ks * 32, lane);      // rows clamp to S - 1: a tile past n_t reads valid memory
+          wv[u][ks] = v2_frag_glb<HD>(qkv + 2 * D, tld, S, (wave + 8 * u) * 16, ks * 32, lane);
         }
     }
   };
@@ -1349,8 +1385,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if (e < c_rows * 8) {        // whole waves (c_rows * 8 is a multiple of 256)
         const bf16x8 z = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
         const bf16x8 gv = r < cS ? cg[j] : z;
-        *(bf16x8*)(img0 + r * V2_LD + c8 * 8) = r < cS ? cq[j] : z;
-        *(bf16x8*)(img1 + r * V2_LD + c8 * 8) = gv;
+        *(bf16x8*)(img0 + r * v2_ld<HD> + c8 * 8) = r < cS ? cq[j] : z;
+        *(bf16x8*)(img1 + r * v2_ld<HD> + c8 * 8) = gv;
         float de = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) de += (float)co[j][k] * (float)gv[k];
@@ -1371,7 +1407,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) asm volatile("" ::"v"(wk[u][ks]), "v"(wv[u][ks]));
+      for (int ks = 0; ks < v2_ks<HD>; ++ks) asm volatile("" ::"v"(wk[u][ks]), "v"(wv[u][ks]));
     __syncthreads();
     const int nxt = it + (int)gridDim.x;
     const bool more = nxt < n_items;
@@ -1389,7 +1425,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int u = 0; u < 2; ++u)
       if (wave + 8 * u < c_nt) {
 #pragma unroll
-        for (int ks = 0; ks < HD / 32; ++ks) *(bf16x8*)(img0 + ((wave + 8 * u) * 16 + (lane2 & 15)) * V2_LD + ks * 32 + 8 * (lane2 >> 4)) = wk[u][ks];
+        for (int ks = 0; ks < v2_ks<HD>; ++ks) *(bf16x8*)(img0 + ((wave + 8 * u) * 16 + (lane2 & 15)) * v2_ld<HD> + ks * 32 + 8 * (lane2 >> 4)) = wk[u][ks];
       }
     // ---- the next item's K / V fragments, into the registers just written out: they arrive under phase 2
     if (more) request_frags(tid2);
@@ -1405,7 +1441,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int pk = 0; pk < n_pair_k; ++pk) {
         const bf16x8 fs = v2_frag_tr_ld(dsT, ldq, 2 * pk, qt * 16, lane3, 2 * pk + 1 < c_nt);
 #pragma unroll
-        for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr(img0, 2 * pk, d * 16, lane3), fs, dq[d]);
+        for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr<HD>(img0, 2 * pk, d * 16, lane3), fs, dq[d]);
       }
       const Row32 qv = rows4_exchange(dq, a.scale * ik);
       if (q < cS) {
@@ -1426,11 +1462,12 @@ static size_t v4_lds_bytes(int S, int* rows_img, int* ldq) {
   *rows_img = ((n_t + 1) / 2) * 32;
   *ldq = (n_t & 1) ? 16 * n_t : 16 * n_t + 16;        // ldq / 2 = 8 (mod 16) banks: rows 0-7 of a transposed read fall on distinct 8-bank groups
   const size_t slabs = n_t <= 2 * V4_EXACT_PAIRS ? 7 : 0;      // attn_bwd_v4x: seven more slabs of per-key-tile row sums
-  const size_t b = (size_t)2 * *rows_img * V2_LD * 2 + (size_t)(3 + slabs) * *rows_img * 4 + (size_t)16 * n_t * *ldq * 2;
+  const size_t b = (size_t)2 * *rows_img * v2_ld<64> * 2 + (size_t)(3 + slabs) * *rows_img * 4 + (size_t)16 * n_t * *ldq * 2;
   return b <= 160 * 1024 ? b : 0;
 }
 
-// The backward kernel of a bf16 launch with head_dim 64 (S <= 272; length-binned launches: s_cap <= 272).  Default, in order:
+// The backward kernel of a bf16 launch with head_dim 64 or 16 (S <= 272; length-binned launches, 64 only: s_cap <= 272).
+// Default, in order:
 //   length-binned launches (seq_ids / s_cap)              -> the family below
 //   a dense bias without structural terms                -> v1 (attention.hip: the only kernels that take one)
 //   S > 256 (ViT-L/14: 4 + 257 tokens)                   -> family
@@ -1440,6 +1477,7 @@ static size_t v4_lds_bytes(int S, int* rows_img, int* ldq) {
 // The family, without a structural bias, where the one-pass dS image fits LDS (S <= 208): v5 (9-13 key tiles, persistent),
 // v4x (<= 6 key tiles: delta = sum P o dP summed in the kernel, in fp32), v4 (7-8 key tiles); past that, and with a
 // structural bias: the two-pass v3.  Measured at C2 shapes: profiles/round1_attention_v2.txt, tools/attn_onepass_ab.py.
+// The one-pass kernels are written for 64-wide heads: with head_dim 16 the family is always v3.
 // MDT_ATTN_BWD=<kernel> takes that kernel wherever its preconditions (ok() below) hold.  v1 and v2 never see q_limit or
 // length bins (they would read the out / lse rows the v2 forward skipped — unwritten memory; tests:
 // ..._never_reads_what_forward_did_not_write), v2 takes S <= 112 only, the one-pass kernels take no structural bias.
@@ -1450,7 +1488,7 @@ AttnRoute attn_bwd_route(const AttnParams& p) {
   const int cap = a.s_cap > 0 ? a.s_cap : a.S;                   // longest sequence of this launch
   const int n_t = (cap + 15) / 16;
   int rows_img = 0, ldq = 0;
-  const bool one_pass = !st_bias && !dense_only && v4_lds_bytes(cap, &rows_img, &ldq) != 0 && n_t <= 16;
+  const bool one_pass = a.hd == 64 && !st_bias && !dense_only && v4_lds_bytes(cap, &rows_img, &ldq) != 0 && n_t <= 16;
   auto ok = [&](AttnRoute r) {
     switch (r) {
       case AttnRoute::v1: return !binned && a.q_limit == 0;
@@ -1474,81 +1512,97 @@ AttnRoute attn_bwd_route(const AttnParams& p) {
   return forced != AttnRoute::none && ok(forced) ? forced : r;
 }
 
-template <bool STRUCT, bool DROP>
+// the one-pass kernels (64-wide heads, no structural bias): r is v4 | v4x | v5
+template <bool DROP>
+static int launch_one_pass(hipStream_t st, const AttnParams& p, AttnRoute r) {
+  // In-call A/B with dropout 0.1 (tools/attn_onepass_ab.py): ViT rows (512 x 201) 755 -> 525 us, padded BERT rows
+  // (2048 x 104) 993 -> 792 us, ragged BERT rows (8-100 tokens) 592 -> 493 us; gradients equal to bf16 rounding of delta.
+  const int cap = p.f.s_cap > 0 ? p.f.s_cap : p.f.S;          // longest sequence of this launch
+  const dim3 grid(p.f.H, p.f.nseq);
+  int rows_img = 0, ldq = 0;
+  const size_t lds4 = v4_lds_bytes(cap, &rows_img, &ldq);
+  const int n_t = (cap + 15) / 16;
+  if (r == AttnRoute::v5) {
+    const int64_t n_items = (int64_t)p.f.H * p.f.nseq;
+    const int cus = device_cus();
+    return launch_route<attn_bwd_v5_kernel<64, DROP>>("v5", dim3((unsigned)(n_items < cus ? n_items : cus)), 512, lds4, st, p,
+                                                      rows_img, ldq, (int)n_items);
+  }
+  const int waves = n_t <= 4 ? 4 : n_t <= 8 ? 8 : 16;          // two 16-byte chunks per thread and image, one key tile per wave
+  if (r == AttnRoute::v4x) return launch_route<attn_bwd_v4x_kernel<64, DROP>>("v4x", grid, waves * 64, lds4, st, p, rows_img, ldq);
+  return launch_route<attn_bwd_v4_kernel<64, DROP>>("v4", grid, waves * 64, lds4, st, p, rows_img, ldq);
+}
+
+template <int HD, bool STRUCT, bool DROP>
 static int launch_v3(hipStream_t st, const AttnParams& p, AttnRoute r) {
+  if constexpr (HD == 64 && !STRUCT) {
+    if (r != AttnRoute::v3) return launch_one_pass<DROP>(st, p, r);
+  }
   const int cap = p.f.s_cap > 0 ? p.f.s_cap : p.f.S;          // longest sequence of this launch
   const int s_pad = (cap + 63) & ~63;
   const int nhist = STRUCT ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
-  const size_t lds = (size_t)2 * s_pad * V2_LD * 2 + (size_t)3 * s_pad * 4 + (size_t)nhist * 4;
+  const size_t lds = (size_t)2 * s_pad * v2_ld<HD> * 2 + (size_t)3 * s_pad * 4 + (size_t)nhist * 4;
   if (lds > 160 * 1024) { set_error("attention_bwd_v3: S=%d needs %zu bytes of LDS", cap, lds); return MDT_ERR_UNSUPPORTED; }
   const dim3 grid(p.f.H, p.f.nseq);
-  if constexpr (STRUCT) {
-    return launch_route<attn_bwd_v3_kernel<64, true, DROP>>("v3", grid, 256, lds, st, p, s_pad);
-  } else {
-    if (r == AttnRoute::v3) {
-      // long sequences (ViT: 13 tiles): LDS allows two workgroups per CU; 8 waves each in the 128-register build = 4 waves
-      // per SIMD instead of 2 (in-call A/B at the ViT shape: +0.7 % on the step)
-      return launch_route<attn_bwd_v3_occ4_kernel<64, DROP>>("v3", grid, s_pad <= 128 ? 256 : 512, lds, st, p, s_pad);
-    }
-    // one pass.  In-call A/B with dropout 0.1 (tools/attn_onepass_ab.py): ViT rows (512 x 201) 755 -> 525 us, padded BERT rows
-    // (2048 x 104) 993 -> 792 us, ragged BERT rows (8-100 tokens) 592 -> 493 us; gradients equal to bf16 rounding of delta.
-    int rows_img = 0, ldq = 0;
-    const size_t lds4 = v4_lds_bytes(cap, &rows_img, &ldq);
-    const int n_t = (cap + 15) / 16;
-    if (r == AttnRoute::v5) {
-      const int64_t n_items = (int64_t)p.f.H * p.f.nseq;
-      const int cus = device_cus();
-      return launch_route<attn_bwd_v5_kernel<64, DROP>>("v5", dim3((unsigned)(n_items < cus ? n_items : cus)), 512, lds4, st, p,
-                                                        rows_img, ldq, (int)n_items);
-    }
-    const int waves = n_t <= 4 ? 4 : n_t <= 8 ? 8 : 16;          // two 16-byte chunks per thread and image, one key tile per wave
-    if (r == AttnRoute::v4x) return launch_route<attn_bwd_v4x_kernel<64, DROP>>("v4x", grid, waves * 64, lds4, st, p, rows_img, ldq);
-    return launch_route<attn_bwd_v4_kernel<64, DROP>>("v4", grid, waves * 64, lds4, st, p, rows_img, ldq);
-  }
+  if constexpr (STRUCT) return launch_route<attn_bwd_v3_kernel<HD, true, DROP>>("v3", grid, 256, lds, st, p, s_pad);
+  // long sequences (ViT: 13 tiles): LDS allows two workgroups per CU; 8 waves each in the 128-register build = 4 waves
+  // per SIMD instead of 2 (in-call A/B at the ViT shape: +0.7 % on the step)
+  else return launch_route<attn_bwd_v3_occ4_kernel<HD, DROP>>("v3", grid, s_pad <= 128 ? 256 : 512, lds, st, p, s_pad);
 }
 
-int attention_v3_bwd_dispatch(hipStream_t st, const AttnParams& p, AttnRoute r) {
+template <int HD>
+static int dispatch_v3(hipStream_t st, const AttnParams& p, AttnRoute r) {
   const bool s = p.f.attn_bias != nullptr, d = p.f.drop_p > 0.f;
-  if (s && d) return launch_v3<true, true>(st, p, r);
-  if (s) return launch_v3<true, false>(st, p, r);
-  if (d) return launch_v3<false, true>(st, p, r);
-  return launch_v3<false, false>(st, p, r);
+  if (s && d) return launch_v3<HD, true, true>(st, p, r);
+  if (s) return launch_v3<HD, true, false>(st, p, r);
+  if (d) return launch_v3<HD, false, true>(st, p, r);
+  return launch_v3<HD, false, false>(st, p, r);
 }
 
-template <int NT, bool STRUCT, bool DROP, bool BWD>
+// head_dim: 64 or 16 (dispatch() in attention.hip refuses every other width before it gets here)
+int attention_v3_bwd_dispatch(hipStream_t st, const AttnParams& p, AttnRoute r) {
+  return p.f.hd == 16 ? dispatch_v3<16>(st, p, r) : dispatch_v3<64>(st, p, r);
+}
+
+template <int HD, int NT, bool STRUCT, bool DROP, bool BWD>
 static int launch_v2(hipStream_t st, const AttnParams& p) {
   constexpr int S_PAD = ((NT + 1) / 2) * 32;
   const int nhist = (STRUCT && BWD) ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
-  const size_t lds = (size_t)2 * S_PAD * V2_LD * 2 + (size_t)(BWD ? 3 : 1) * S_PAD * 4 + (size_t)nhist * 4 + (BWD ? 0 : 16);   // forward: + the staging's spare chunk
+  const size_t lds = (size_t)2 * S_PAD * v2_ld<HD> * 2 + (size_t)(BWD ? 3 : 1) * S_PAD * 4 + (size_t)nhist * 4 + (BWD ? 0 : 16);   // forward: + the staging's spare chunk
   if constexpr (BWD && NT > 7) {
     // the whole-row backward runs out of registers past 112 keys; attn_bwd_route sends those to the v3 family
     set_error("attention_v2: backward supports S <= 112 (got %d)", p.f.S);
     return MDT_ERR_UNSUPPORTED;
   } else {
     constexpr int NWF = (NT >= 13 && !STRUCT) ? 8 : 4;     // forward: 8 waves for the long (ViT) rows, 4 waves per SIMD
-    if constexpr (BWD) return launch_route<attn_bwd_v2_kernel<64, NT, STRUCT, DROP>>("v2", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
-    else return launch_route<attn_fwd_v2_kernel<64, NT, STRUCT, DROP, NWF>>("v2", dim3(p.f.H, p.f.nseq), NWF * 64, lds, st, p);
+    if constexpr (BWD) return launch_route<attn_bwd_v2_kernel<HD, NT, STRUCT, DROP>>("v2", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
+    else return launch_route<attn_fwd_v2_kernel<HD, NT, STRUCT, DROP, NWF>>("v2", dim3(p.f.H, p.f.nseq), NWF * 64, lds, st, p);
   }
 }
 
-template <bool STRUCT, bool DROP, bool BWD>
+template <int HD, bool STRUCT, bool DROP, bool BWD>
 static int dispatch_v2_nt(hipStream_t st, const AttnParams& p) {
   const int nt = ((p.f.s_cap > 0 ? p.f.s_cap : p.f.S) + 15) / 16;
-#define V2_CASE(N_) if (nt <= N_) return launch_v2<N_, STRUCT, DROP, BWD>(st, p);
+#define V2_CASE(N_) if (nt <= N_) return launch_v2<HD, N_, STRUCT, DROP, BWD>(st, p);
   V2_CASE(2) V2_CASE(4) V2_CASE(5) V2_CASE(7) V2_CASE(9) V2_CASE(13) V2_CASE(17)
 #undef V2_CASE
   set_error("attention_v2: S=%d exceeds 272", p.f.S);
   return MDT_ERR_UNSUPPORTED;
 }
 
-int attention_v2_dispatch(hipStream_t st, const AttnParams& p, bool bwd) {
+template <int HD>
+static int dispatch_v2(hipStream_t st, const AttnParams& p, bool bwd) {
   const bool s = p.f.attn_bias != nullptr, d = p.f.drop_p > 0.f;
-#define V2_GO(S_, D_) return bwd ? dispatch_v2_nt<S_, D_, true>(st, p) : dispatch_v2_nt<S_, D_, false>(st, p);
+#define V2_GO(S_, D_) return bwd ? dispatch_v2_nt<HD, S_, D_, true>(st, p) : dispatch_v2_nt<HD, S_, D_, false>(st, p);
   if (s && d) V2_GO(true, true)
   if (s) V2_GO(true, false)
   if (d) V2_GO(false, true)
   V2_GO(false, false)
 #undef V2_GO
+}
+
+int attention_v2_dispatch(hipStream_t st, const AttnParams& p, bool bwd) {
+  return p.f.hd == 16 ? dispatch_v2<16>(st, p, bwd) : dispatch_v2<64>(st, p, bwd);
 }
 
 }  // namespace mdt

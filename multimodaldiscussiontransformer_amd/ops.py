@@ -157,7 +157,7 @@ def attention_fwd(qkv, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None,
     the kernels that fit its cap; results are identical to the single launch."""
     D = qkv.shape[1] // 3
     hd = D // H
-    # No fill, also with q_limit: the kernels that honour it (bf16, head dim 64) write whole 16-row query tiles, and the backward
+    # No fill, also with q_limit: the kernels that honour it (bf16) write whole 16-row query tiles, and the backward
     # kernels dispatched for such a launch read exactly those rows of out / lse and nothing past them
     # (tests/test_kernels_gpu.py::test_attention_backward_never_reads_what_forward_did_not_write); every other kernel family ignores
     # q_limit and writes all rows.  Positions of lse past a ragged sequence's length are never read either.
