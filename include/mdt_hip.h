@@ -365,6 +365,46 @@ int mdt_adam_step_multi(void* stream, int dtype, int n_tensors, const mdt_adam_t
                         const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, const float* grad_scale);
 
+/* Global gradient norm, clipping and the non-finite guard (FairSeq --clip-norm, the gnorm meter, its skipped / refused
+ * non-finite update), without a host synchronisation.  Three steps on one stream:
+ *   1. sum of squares: every 4096-element chunk of every gradient tensor writes ONE fp32 partial, partials[chunk], to a
+ *      caller-owned buffer (multi: total_chunks of them, walking the table of the Adam step; single tensor:
+ *      (n + 4095) / 4096).  No atomics and a fixed order inside a chunk: the same bits on every call, for any grid.
+ *      Views need only 4-byte alignment; 16-byte aligned ones are read 16 bytes at a time.
+ *   2. finalize: one block adds the n_partials partials in index order in fp64 and writes the guard state:
+ *        gnorm = s_in * sqrt(sum g^2)          s_in = *grad_scale, or 1 when grad_scale is NULL
+ *        scale = s_in * min(1, max_norm / (gnorm + 1e-6))      max_norm <= 0: scale = s_in, bit for bit
+ *        skip  = gnorm is not finite (Inf / NaN in a gradient, or a sum beyond fp32): this update is skipped
+ *      and the running counters: skipped, clipped (gnorm > max_norm > 0, update not skipped), applied = step - skipped.
+ *      `step` is the host's count of attempted updates (>= 1), as handed to the Adam step.  Once skipped > 0 step_size
+ *      holds (float)(lr * sqrt(1 - beta2^applied) / (1 - beta1^applied)): Adam's bias correction follows the updates
+ *      applied.  reset != 0: the counters start from zero at this call — nothing of *guard is read.
+ *   3. the guarded Adam steps: as mdt_adam_step / mdt_adam_step_multi with `scale` of the guard state in place of
+ *      *grad_scale; a skipped update stores nothing (param, master, m, v keep their bits); the host's step size is used
+ *      verbatim while skipped == 0, the guard state's afterwards. */
+typedef struct {
+  float scale;          /* effective gradient scale of this update */
+  float gnorm;          /* norm of the scaled gradient of this update */
+  float step_size;      /* bias-corrected step size for `applied` updates; meaningful once skipped > 0 */
+  int32_t skip;         /* 1: this update is skipped */
+  int32_t applied;      /* running: updates applied */
+  int32_t clipped;      /* running: updates clipped */
+  int32_t skipped;      /* running: updates skipped */
+  int32_t reserved;
+} mdt_adam_guard;
+int mdt_grad_sumsq_multi(void* stream, int n_tensors, const mdt_adam_tensor* table_dev, const int64_t* chunk_first_dev,
+                         int64_t total_chunks, float* partials);
+int mdt_grad_sumsq(void* stream, int64_t n, const float* grad, float* partials);
+int mdt_grad_norm_finalize(void* stream, const float* partials, int64_t n_partials, float max_norm,
+                           const float* grad_scale, float lr, float beta1, float beta2, int step, int reset,
+                           mdt_adam_guard* guard);
+int mdt_adam_step_guarded(void* stream, int dtype, int64_t n, void* param, float* master, const float* grad, float* m,
+                          float* v, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                          const mdt_adam_guard* guard);
+int mdt_adam_step_multi_guarded(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
+                                const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2,
+                                float eps, float weight_decay, int step, const mdt_adam_guard* guard);
+
 /* ------------------------------------------------------------------ packer (host, C++)
  * Native replacement of preprocess_item + collator (data/pyg_datasets/pre_processing.py:18-69,
  * data/collator.py:69-179): integer tensors are bit-exact with the reference.

@@ -88,6 +88,11 @@ _SIGS = {
     "mdt_cast": ([_vp, _i, _i, _i64, _vp, _vp], _i),
     "mdt_transpose2d": ([_vp, _i, _i, _i64, _i64, _vp, _i64, _vp, _i64], _i),
     "mdt_adam_step": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp], _i),
+    "mdt_grad_sumsq_multi": ([_vp, _i, _vp, _vp, _i64, _vp], _i),
+    "mdt_grad_sumsq": ([_vp, _i64, _vp, _vp], _i),
+    "mdt_grad_norm_finalize": ([_vp, _vp, _i64, _f, _vp, _f, _f, _f, _i, _i, _vp], _i),
+    "mdt_adam_step_guarded": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp], _i),
+    "mdt_adam_step_multi_guarded": ([_vp, _i, _i, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp], _i),
     "mdt_resize_plan_ksize": ([_i, _i], _i),
     "mdt_resize_plan": ([_i, _i, _vp, _vp, _i], _i),
     "mdt_image_norm_lut": ([C.c_double, _vp, _vp, _vp], _i),

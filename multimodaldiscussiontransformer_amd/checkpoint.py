@@ -76,10 +76,13 @@ def optimizer_state_dict(optimizer, model, criterion=None) -> dict:
     params = _trainable(model, criterion)
     index = {id(p): i for i, p in enumerate(params)}
     state = {}
+    # Adam's step is the number of updates APPLIED (FairSeq does not advance it over a skipped update); with the
+    # optimiser's non-finite guard on this reads the device counter — the one synchronisation, at save time only
+    step = optimizer.applied_steps_host() if hasattr(optimizer, "applied_steps_host") else optimizer.step_count
     for p in optimizer.params:
         i = index[id(p)]
         st = optimizer.state[id(p)]
-        state[i] = {"step": optimizer.step_count, "exp_avg": st["m"].detach().cpu(), "exp_avg_sq": st["v"].detach().cpu()}
+        state[i] = {"step": step, "exp_avg": st["m"].detach().cpu(), "exp_avg_sq": st["v"].detach().cpu()}
     group = {"lr": optimizer.lr, "betas": tuple(optimizer.betas), "eps": optimizer.eps, "weight_decay": optimizer.weight_decay,
              "amsgrad": False, "params": list(range(len(params)))}
     return {"state": state, "param_groups": [group]}
@@ -132,6 +135,8 @@ def load_optimizer_state_dict(optimizer, model, osd: dict, criterion=None):
         if len(steps) > 1:
             raise ValueError(f"per-parameter step counts differ: {sorted(steps)}")
         optimizer.step_count = steps.pop() if steps else 0
+    if hasattr(optimizer, "reset_guard"):
+        optimizer.reset_guard()                 # the restored count is of applied updates: nothing skipped since
     g = osd["param_groups"][0]
     optimizer.lr, optimizer.betas, optimizer.eps, optimizer.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
 

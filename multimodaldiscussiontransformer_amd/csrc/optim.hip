@@ -8,12 +8,32 @@
 
 namespace mdt {
 
-template <typename T>
+// The guard state the norm finaliser writes and the guarded kernels read (include/mdt_hip.h: mdt_adam_guard).
+// GUARD = false is the plain step: `grad_scale` is the optional device scalar, the host's step size is used as given.
+// GUARD = true reads the effective scale from the guard state, stores NOTHING when the update is skipped, and takes the
+// step size of the updates actually applied once any update has been skipped (until then the host's count is the
+// applied count, and the arithmetic is the plain step's bit for bit).
+template <bool GUARD>
+__device__ __forceinline__ bool adam_scale_and_step(const float* __restrict__ grad_scale, const mdt_adam_guard* __restrict__ guard,
+                                                    float& gs, float& step_size) {
+  if constexpr (GUARD) {
+    if (guard->skip) return false;
+    gs = guard->scale;
+    if (guard->skipped) step_size = guard->step_size;
+  } else {
+    gs = grad_scale ? grad_scale[0] : 1.0f;
+  }
+  return true;
+}
+
+template <typename T, bool GUARD>
 __global__ __launch_bounds__(256) void adam_kernel(int64_t n, T* __restrict__ param, float* __restrict__ master,
                                                    const float* __restrict__ grad, float* __restrict__ m,
                                                    float* __restrict__ v, float lr, float beta1, float beta2, float eps,
-                                                   float wd, float step_size, const float* __restrict__ grad_scale) {
-  const float gs = grad_scale ? grad_scale[0] : 1.0f;
+                                                   float wd, float step_size, const float* __restrict__ grad_scale,
+                                                   const mdt_adam_guard* __restrict__ guard) {
+  float gs;
+  if (!adam_scale_and_step<GUARD>(grad_scale, guard, gs, step_size)) return;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float g = grad[i] * gs;
     const float mi = beta1 * m[i] + (1.0f - beta1) * g;
@@ -28,22 +48,30 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, T* __restrict__ pa
   }
 }
 
+// Tensor of chunk `chunk` in a table whose tensor t starts at chunk chunk_first[t] (monotone, chunk_first[n] = total).
+__device__ __forceinline__ int tensor_of_chunk(const int64_t* __restrict__ chunk_first, int n_tensors, int64_t chunk) {
+  int lo = 0, hi = n_tensors - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (chunk_first[mid] <= chunk) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 // Multi-tensor form: one launch walks a device table of tensors (the ~400 parameter tensors of mDT would otherwise
 // cost ~400 launches of 10-20 us each).  Block b works on chunk b of 4096 elements; `chunk_first[t]` is the first
 // chunk of tensor t (monotone, chunk_first[n] = total), found by binary search.
-template <typename T>
+template <typename T, bool GUARD>
 __global__ __launch_bounds__(256) void adam_multi_kernel(int n_tensors, const mdt_adam_tensor* __restrict__ tab,
                                                          const int64_t* __restrict__ chunk_first, float lr, float beta1,
                                                          float beta2, float eps, float wd, float step_size,
-                                                         const float* __restrict__ grad_scale) {
-  const float gs = grad_scale ? grad_scale[0] : 1.0f;
+                                                         const float* __restrict__ grad_scale,
+                                                         const mdt_adam_guard* __restrict__ guard) {
+  float gs;
+  if (!adam_scale_and_step<GUARD>(grad_scale, guard, gs, step_size)) return;
   const int64_t total = chunk_first[n_tensors];
   for (int64_t chunk = blockIdx.x; chunk < total; chunk += gridDim.x) {
-    int lo = 0, hi = n_tensors - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (chunk_first[mid] <= chunk) lo = mid; else hi = mid - 1;
-    }
+    const int lo = tensor_of_chunk(chunk_first, n_tensors, chunk);
     const mdt_adam_tensor t = tab[lo];
     const int64_t base = (chunk - chunk_first[lo]) * 4096;
     T* param = (T*)t.param;
@@ -65,36 +93,196 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(int n_tensors, const md
   }
 }
 
+// ---------------------------------------------------------------- global gradient norm (--clip-norm, gnorm, non-finite guard)
+// Sum of squares of one 4096-element chunk, the same bits whatever the grid: thread t owns the four float4 groups
+// (k * 256 + t) of the chunk and adds its 16 squares in index order, the wave sums its 64 lanes with the DPP tree
+// LayerNorm uses, wave 0's lane 0 adds the four wave totals as (w0 + w1) + (w2 + w3).  No atomics; elements past the
+// end of the tensor count as +0.  The groups are loaded 16 bytes at a time where the chunk starts on a 16-byte
+// boundary (arena slots do) and element by element, same ownership and order, where a view starts elsewhere.
+__device__ __forceinline__ float chunk_sumsq(const float* __restrict__ g, int64_t left, float* red) {
+  const int tid = threadIdx.x;
+  const bool vec = ((uintptr_t)g & 15) == 0;
+  float acc = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t i = (int64_t)(k * 256 + tid) * 4;
+    float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f, x3 = 0.0f;
+    if (vec && i + 3 < left) {
+      const f32x4 q = *(const f32x4*)(g + i);
+      x0 = q[0]; x1 = q[1]; x2 = q[2]; x3 = q[3];
+    } else {
+      if (i < left) x0 = g[i];
+      if (i + 1 < left) x1 = g[i + 1];
+      if (i + 2 < left) x2 = g[i + 2];
+      if (i + 3 < left) x3 = g[i + 3];
+    }
+    acc += x0 * x0;
+    acc += x1 * x1;
+    acc += x2 * x2;
+    acc += x3 * x3;
+  }
+  acc = wave_sum_dpp(acc);
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  const float total = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();          // `red` is written again by the block's next chunk
+  return total;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(int n_tensors, const mdt_adam_tensor* __restrict__ tab,
+                                                               const int64_t* __restrict__ chunk_first,
+                                                               float* __restrict__ partials) {
+  __shared__ float red[4];
+  const int64_t total = chunk_first[n_tensors];
+  for (int64_t chunk = blockIdx.x; chunk < total; chunk += gridDim.x) {
+    const int lo = tensor_of_chunk(chunk_first, n_tensors, chunk);
+    const int64_t base = (chunk - chunk_first[lo]) * 4096;
+    const float s = chunk_sumsq(tab[lo].grad + base, tab[lo].numel - base, red);
+    if (threadIdx.x == 0) partials[chunk] = s;
+  }
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(int64_t n, const float* __restrict__ grad, float* __restrict__ partials) {
+  __shared__ float red[4];
+  const int64_t total = (n + 4095) / 4096;
+  for (int64_t chunk = blockIdx.x; chunk < total; chunk += gridDim.x) {
+    const float s = chunk_sumsq(grad + chunk * 4096, n - chunk * 4096, red);
+    if (threadIdx.x == 0) partials[chunk] = s;
+  }
+}
+
+// One block: thread t adds partials t, t + 256, ... in index order in fp64, the 256 sums are folded by a fixed
+// halving tree, thread 0 derives the guard state (FairSeq's order: the norm of the gradient AFTER multiply_grads,
+// then clip_grad_norm_'s coefficient).  `reset`: the running counters start from zero at this call, whatever the
+// buffer held (nothing of the guard state is read before it is written).
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const float* __restrict__ partials, int64_t n_partials,
+                                                                 float max_norm, const float* __restrict__ grad_scale,
+                                                                 float lr, float beta1, float beta2, int step, int reset,
+                                                                 mdt_adam_guard* __restrict__ guard) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int64_t i = tid; i < n_partials; i += 256) acc += (double)partials[i];
+  red[tid] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const float s_in = grad_scale ? grad_scale[0] : 1.0f;
+  const float gnorm = (float)((double)s_in * sqrt(red[0]));
+  const bool finite = isfinite(gnorm);
+  const bool clip = finite && max_norm > 0.0f && gnorm > max_norm;
+  int clipped = reset ? 0 : guard->clipped, skipped = reset ? 0 : guard->skipped;
+  float scale = s_in;                                   // max_norm <= 0 or no clipping: the incoming scale, bit for bit
+  if (clip) scale = (float)((double)s_in * ((double)max_norm / ((double)gnorm + 1e-6)));
+  skipped += finite ? 0 : 1;
+  clipped += clip ? 1 : 0;
+  const int applied = step - skipped;
+  float step_size = 0.0f;
+  if (skipped > 0 && applied > 0)
+    step_size = (float)((double)lr * sqrt(1.0 - pow((double)beta2, (double)applied)) / (1.0 - pow((double)beta1, (double)applied)));
+  guard->scale = scale;
+  guard->gnorm = gnorm;
+  guard->step_size = step_size;
+  guard->skip = finite ? 0 : 1;
+  guard->applied = applied;
+  guard->clipped = clipped;
+  guard->skipped = skipped;
+  guard->reserved = 0;
+}
+
 }  // namespace mdt
 
 using namespace mdt;
 
+static float adam_step_size(float lr, float beta1, float beta2, int step) {
+  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  return (float)(lr * sqrt(bc2) / bc1);
+}
+
+template <bool GUARD>
+static int adam_step_multi(const char* what, void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
+                           const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, int step, const float* grad_scale, const mdt_adam_guard* guard) {
+  if (n_tensors == 0 || total_chunks == 0) return MDT_OK;
+  MDT_CHECK_ARG(table_dev && chunk_first_dev && step >= 1 && (!GUARD || guard), "%s: bad arguments", what);
+  const float step_size = adam_step_size(lr, beta1, beta2, step);
+  const unsigned grid = (unsigned)(total_chunks > 65536 ? 65536 : total_chunks);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MDT_F32) hipLaunchKernelGGL((adam_multi_kernel<float, GUARD>), grid, 256, 0, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale, guard);
+  else if (dtype == MDT_BF16) hipLaunchKernelGGL((adam_multi_kernel<bf16_t, GUARD>), grid, 256, 0, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale, guard);
+  else MDT_UNSUPPORTED("%s: dtype %d", what, dtype);
+  return check_launch(what);
+}
+
+template <bool GUARD>
+static int adam_step_one(const char* what, void* stream, int dtype, int64_t n, void* param, float* master, const float* grad,
+                         float* m, float* v, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                         const float* grad_scale, const mdt_adam_guard* guard) {
+  if (n == 0) return MDT_OK;
+  MDT_CHECK_ARG(param && grad && m && v && step >= 1 && (!GUARD || guard), "%s: bad arguments", what);
+  const float step_size = adam_step_size(lr, beta1, beta2, step);
+  const unsigned grid = (unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MDT_F32) hipLaunchKernelGGL((adam_kernel<float, GUARD>), grid, 256, 0, st, n, (float*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale, guard);
+  else if (dtype == MDT_BF16) hipLaunchKernelGGL((adam_kernel<bf16_t, GUARD>), grid, 256, 0, st, n, (bf16_t*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale, guard);
+  else MDT_UNSUPPORTED("%s: dtype %d", what, dtype);
+  return check_launch(what);
+}
+
 extern "C" int mdt_adam_step_multi(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
                                    const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2,
                                    float eps, float weight_decay, int step, const float* grad_scale) {
-  if (n_tensors == 0 || total_chunks == 0) return MDT_OK;
-  MDT_CHECK_ARG(table_dev && chunk_first_dev && step >= 1, "adam_step_multi: bad arguments");
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  const float step_size = (float)(lr * sqrt(bc2) / bc1);
-  const unsigned grid = (unsigned)(total_chunks > 65536 ? 65536 : total_chunks);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDT_F32) hipLaunchKernelGGL((adam_multi_kernel<float>), grid, 256, 0, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale);
-  else if (dtype == MDT_BF16) hipLaunchKernelGGL((adam_multi_kernel<bf16_t>), grid, 256, 0, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale);
-  else MDT_UNSUPPORTED("adam_step_multi: dtype %d", dtype);
-  return check_launch("adam_step_multi");
+  return adam_step_multi<false>("adam_step_multi", stream, dtype, n_tensors, table_dev, chunk_first_dev, total_chunks, lr, beta1,
+                                beta2, eps, weight_decay, step, grad_scale, nullptr);
 }
 
 extern "C" int mdt_adam_step(void* stream, int dtype, int64_t n, void* param, float* master, const float* grad, float* m,
                              float* v, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                              const float* grad_scale) {
+  return adam_step_one<false>("adam_step", stream, dtype, n, param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step,
+                              grad_scale, nullptr);
+}
+
+extern "C" int mdt_adam_step_multi_guarded(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
+                                           const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1,
+                                           float beta2, float eps, float weight_decay, int step, const mdt_adam_guard* guard) {
+  return adam_step_multi<true>("adam_step_multi_guarded", stream, dtype, n_tensors, table_dev, chunk_first_dev, total_chunks, lr,
+                               beta1, beta2, eps, weight_decay, step, nullptr, guard);
+}
+
+extern "C" int mdt_adam_step_guarded(void* stream, int dtype, int64_t n, void* param, float* master, const float* grad, float* m,
+                                     float* v, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                     const mdt_adam_guard* guard) {
+  return adam_step_one<true>("adam_step_guarded", stream, dtype, n, param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay,
+                             step, nullptr, guard);
+}
+
+extern "C" int mdt_grad_sumsq_multi(void* stream, int n_tensors, const mdt_adam_tensor* table_dev, const int64_t* chunk_first_dev,
+                                    int64_t total_chunks, float* partials) {
+  if (n_tensors == 0 || total_chunks == 0) return MDT_OK;
+  MDT_CHECK_ARG(table_dev && chunk_first_dev && partials, "grad_sumsq_multi: bad arguments");
+  const unsigned grid = (unsigned)(total_chunks > 65536 ? 65536 : total_chunks);
+  hipLaunchKernelGGL(grad_sumsq_multi_kernel, grid, 256, 0, (hipStream_t)stream, n_tensors, table_dev, chunk_first_dev, partials);
+  return check_launch("grad_sumsq_multi");
+}
+
+extern "C" int mdt_grad_sumsq(void* stream, int64_t n, const float* grad, float* partials) {
   if (n == 0) return MDT_OK;
-  MDT_CHECK_ARG(param && grad && m && v && step >= 1, "adam_step: bad arguments");
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  const float step_size = (float)(lr * sqrt(bc2) / bc1);
-  const unsigned grid = (unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDT_F32) hipLaunchKernelGGL((adam_kernel<float>), grid, 256, 0, st, n, (float*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale);
-  else if (dtype == MDT_BF16) hipLaunchKernelGGL((adam_kernel<bf16_t>), grid, 256, 0, st, n, (bf16_t*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale);
-  else MDT_UNSUPPORTED("adam_step: dtype %d", dtype);
-  return check_launch("adam_step");
+  MDT_CHECK_ARG(n > 0 && grad && partials, "grad_sumsq: bad arguments");
+  const int64_t chunks = (n + 4095) / 4096;
+  const unsigned grid = (unsigned)(chunks > 65536 ? 65536 : chunks);
+  hipLaunchKernelGGL(grad_sumsq_kernel, grid, 256, 0, (hipStream_t)stream, n, grad, partials);
+  return check_launch("grad_sumsq");
+}
+
+extern "C" int mdt_grad_norm_finalize(void* stream, const float* partials, int64_t n_partials, float max_norm,
+                                      const float* grad_scale, float lr, float beta1, float beta2, int step, int reset,
+                                      mdt_adam_guard* guard) {
+  MDT_CHECK_ARG(guard && n_partials >= 0 && (partials || n_partials == 0) && step >= 1, "grad_norm_finalize: bad arguments");
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, 1, 256, 0, (hipStream_t)stream, partials, n_partials, max_norm, grad_scale, lr,
+                     beta1, beta2, step, reset, guard);
+  return check_launch("grad_norm_finalize");
 }

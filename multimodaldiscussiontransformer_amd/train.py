@@ -5,7 +5,8 @@ spellings (flags it does not implement are refused; the few it accepts without e
 --wandb-project, --num-workers, --required-batch-size-multiple — say so on stderr), resolves --task / --arch / --criterion / --dataset-name through
 ``registry.py``, and runs the reference recipe: Adam(0.9, 0.999, eps 1e-8, wd 0.01),
 polynomial-decay LR with warm-up, --update-freq gradient accumulation, gradient scaling by
-1 / (global) sample size, bf16 (``--fp16`` in the reference) with fp32 master weights, RCCL
+1 / (global) sample size, ``--clip-norm`` / the ``gnorm`` meter / the non-finite-update guard computed on the
+device (optim.py), bf16 (``--fp16`` in the reference) with fp32 master weights, RCCL
 data parallelism when launched under ``torch.distributed.run``.
 
 Without a registered dataset (the HatefulDiscussions graphs are private) ``--dataset-name
@@ -133,8 +134,11 @@ def main(argv=None):
         # a flag this launcher does not know may change what is trained: refuse instead of training something else
         raise SystemExit(f"[mdt-train] unsupported FairSeq flag(s): {' '.join(unknown)} — this launcher implements the flags of "
                          "mDT/experiments/hateful_discussions/run_train.sh; run fairseq-train --user-dir <repo>/src for the rest")
-    if args.clip_norm and args.clip_norm > 0:
-        raise SystemExit("[mdt-train] --clip-norm is not implemented (the reference launch does not use it)")
+    if args.clip_norm < 0:
+        raise SystemExit("[mdt-train] --clip-norm must be >= 0 (0: measure gnorm and guard against non-finite updates, no clipping)")
+    if args.fp16:
+        print("[mdt-train] --fp16: runs as bf16 with fp32 master weights and NO loss scaling; an update whose gradient norm is "
+              "not finite is skipped and counted (skipped_updates), there is no scale to lower", file=sys.stderr)
     if args.wandb_project:
         print("[mdt-train] --wandb-project: metrics are printed as JSON lines, nothing is sent to wandb", file=sys.stderr)
     # accepted for launch-script compatibility, without effect here — said, not silent
@@ -181,7 +185,7 @@ def main(argv=None):
     crit = crit_cls.build_criterion(args, task)      # constructor arguments by name from the flags, as FairSeq does
     betas = ast.literal_eval(args.adam_betas) if isinstance(args.adam_betas, str) else args.adam_betas
     opt = FusedAdam([p for p in model.parameters() if hasattr(p, "main_grad")], lr=args.lr, betas=betas, eps=args.adam_eps,
-                    weight_decay=args.weight_decay)
+                    weight_decay=args.weight_decay, clip_norm=args.clip_norm)     # the norm pass and the guard are always on, as in FairSeq
     sched = PolynomialDecayLR(args.lr, args.end_learning_rate, args.warmup_updates, args.total_num_update, args.power)
     from . import checkpoint as ckpt
     start_update, epoch0 = 0, 1
@@ -281,8 +285,22 @@ def main(argv=None):
     lr_for = sched.for_update        # FairSeq's timing: update k runs with the rate of num_updates = k - 1
 
     best = {"value": None}
+    meter = {"upd": start_update, "clipped": 0, "checked": start_update}      # state of the clip meter / guard at the last log line
+
+    def check_guard(upd, g=None):
+        """FairSeq's answer to a non-finite gradient: under --fp16 the update is skipped and counted (its overflow skip,
+        without a scale to lower); in every other precision the run stops.  The optimiser has skipped the update on the
+        device — weights and moments are intact — and the host learns of it here, at a synchronisation it makes anyway."""
+        g = opt.guard_host() if g is None else g
+        if g["skipped"] > 0 and not args.fp16:
+            raise FloatingPointError(f"[mdt-train] non-finite gradient norm in an update between {meter['checked'] + 1} and {upd} "
+                                     f"({g['skipped']} skipped; weights and optimiser moments are those before it): "
+                                     "lower the learning rate or pass --clip-norm")
+        meter["checked"] = upd
+        return g
 
     def save(path, upd):
+        check_guard(upd)
         done = skip_batches + it                     # batches consumed since the restored epoch began
         ckpt.save_checkpoint(path, model, args, optimizer=opt, num_updates=upd, criterion_name=crit_cls.__name__,
                              lr_scheduler_state={"best": best["value"]}, epoch=epoch0 + done // max(1, n_batches),
@@ -300,6 +318,7 @@ def main(argv=None):
         precision, recall, F1 with its zero guards)."""
         if valid_batches is None:
             return None
+        check_guard(upd)
         was = model.training
         model.eval()
         tot = torch.zeros(6, dtype=torch.float32, device="cuda")
@@ -346,9 +365,13 @@ def main(argv=None):
         gscale = dp.finish_backward(scal, fold_scale=True)     # all-reduce (world > 1); 1 / global sample size is applied by the optimiser
         opt.step(lr=lr_for(upd), grad_scale=gscale)
         if upd % args.log_interval == 0 or upd == max_update:
-            s = scal.tolist()                    # the only host sync, once per log interval
+            s = torch.cat([scal.double(), opt.guard_log_vector()]).tolist()     # the only host sync, once per log interval
+            g = check_guard(upd, dict(gnorm=s[6], applied=int(s[7]), clipped=int(s[8]), skipped=int(s[9])))
             m = crit_cls.compute_metrics([dict(loss=s[0], sample_size=s[1], **dict(zip(counter_keys, s[2:6])))])
-            m.update(num_updates=upd, lr=lr_for(upd), wall=round(time.time() - t0, 2))
+            # FairSeq's meters: gnorm of this update, clip = per cent of the updates since the previous line that were clipped
+            m.update(num_updates=upd, lr=lr_for(upd), gnorm=g["gnorm"], clip=100.0 * (g["clipped"] - meter["clipped"]) / (upd - meter["upd"]),
+                     skipped_updates=g["skipped"], wall=round(time.time() - t0, 2))
+            meter.update(upd=upd, clipped=g["clipped"])
             history.append(m)
             if rank == 0:
                 print(json.dumps(m), flush=True)
