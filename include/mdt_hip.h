@@ -66,9 +66,10 @@ enum {
 
 int mdt_abi_version(void);
 const char* mdt_last_error_string(void);
-/* The route of the calling thread's last successful GEMM or attention launch ("" before the first): mdt_gemm "generic",
+/* The route of the calling thread's last successful GEMM, attention or LayerNorm launch ("" before the first): mdt_gemm "generic",
  * "tile128", "tile256x128", "pp256", "pp256p", "w4p", "w4s"; mdt_gemm_fp8 "f8_w4", "f8_pp256p"; attention "v1" ... "v5", "v4x",
- * "long".  What MDT_GEMM_ROUTE / MDT_ATTN_BWD force is checked against it (a forced route whose preconditions fail runs the default). */
+ * "long"; mdt_layernorm_fwd "ln_fwd", mdt_layernorm_fwd_q8 with an fp8 copy "ln_fwd_q8", mdt_layernorm_bwd "ln_rows" (the
+ * scalar-address kernel) or "ln_generic".  What MDT_GEMM_ROUTE / MDT_ATTN_BWD force is checked against it (a forced route whose preconditions fail runs the default). */
 const char* mdt_last_route(void);
 /* sha256 (hex) over csrc/ and this header at the time the library was linked (build.py source_hash()): the Python side
  * refuses a libmdt_hip.so that was not built from the sources next to it. */

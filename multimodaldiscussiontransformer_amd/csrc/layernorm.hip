@@ -550,7 +550,9 @@ static int ln_fwd_dispatch(hipStream_t st, int64_t rows, int D, const void* x, i
     else launch(std::integral_constant<int, 0>{});
   });
   if (!ok) MDT_UNSUPPORTED("layernorm: D=%d not supported (vectors per lane %d)", D, ln_vectors_per_lane<T>(D));
-  return check_launch("layernorm_fwd");
+  if (int e = check_launch("layernorm_fwd")) return e;
+  set_last_route(q8 ? "ln_fwd_q8" : "ln_fwd");
+  return MDT_OK;
 }
 
 template <typename T>
@@ -583,12 +585,14 @@ static int ln_bwd_dispatch(hipStream_t st, int64_t rows, int D, const void* dy, 
   // the form: which optional tensors take part (bit 2: the dropped copy, bit 1: the column sums, bit 0: the residual gradient)
   const int form = (dxd ? 4 : 0) | (colsum ? 2 : 0) | (add ? 1 : 0);
   bool ok = false;
+  const char* route = "ln_generic";
   ln_pick<0, 1, 2, 3, 4, 5, 6, 7>(form, [&](auto f) {
     constexpr bool DROPPED = (decltype(f)::value & 4) != 0, CS = (decltype(f)::value & 2) != 0, ADD = (decltype(f)::value & 1) != 0;
     if constexpr (std::is_same<T, bf16_t>::value) {
       // row offsets inside a wave's block of rows are 32-bit scalars: rows_per_wave * row stride stays far below 2^31
       const int64_t ldmax = std::max(std::max(lddy, ldx), std::max(std::max(ldadd, lddx), lddxd));
       if ((D == 768 || D == 1024 || D == 512 || D == 256) && !switches().ln_generic && (int64_t)rpw * ldmax * 2 < (1ll << 31)) {
+        route = "ln_rows";
         ok = ln_pick<1, 2, 3, 4>(D / 256, [&](auto nv) {
           launch(layernorm_bwd_rows_kernel<decltype(nv)::value, DROPPED, CS, ADD>, D, rows);
         });
@@ -601,7 +605,9 @@ static int ln_bwd_dispatch(hipStream_t st, int64_t rows, int D, const void* dy, 
     });
   });
   if (!ok) MDT_UNSUPPORTED("layernorm: D=%d not supported (vectors per lane %d)", D, ln_vectors_per_lane<T>(D));
-  return check_launch("layernorm_bwd");
+  if (int e = check_launch("layernorm_bwd")) return e;
+  set_last_route(route);
+  return MDT_OK;
 }
 
 }  // namespace mdt
