@@ -145,7 +145,7 @@ int mdt_layernorm_bwd(void* stream, int dtype, int64_t rows, int D, const void* 
  * sequence s = s*seq_stride + p*pos_stride (so batch-major and fairseq's time-major
  * [T,B,C] layouts need no copy).  scores = scale * q.k + bias, softmax in fp32,
  * out[row, h*hd:(h+1)*hd] = P @ v.  lse[s,h,p] (fp32) is saved for backward.
- * Head widths: hd = 16 or 64, in fp32 and in bf16 (any S; seq_ids / s_cap launches: bf16, hd = 64 only).
+ * Head widths: hd = 16, 64, 96 or 128, in fp32 and in bf16 (any S; seq_ids / s_cap launches: bf16, hd = 64 only).
  *
  * Bias / mask sources, all optional (NULL):
  *   key_mask   u8[nseq,S]   1 = key may be attended (HF additive mask, quirk 9 of

@@ -6,7 +6,7 @@
 // whole key range of a 16-query tile lives in MFMA accumulators (NT tiles of 16 keys)
 // and softmax is a single exact pass — no online rescaling.
 //   bf16: v_mfma_f32_16x16x32_bf16; K / V (fwd), then K,V / Q,dO (bwd) staged in LDS
-//         (head_dim 64: 144-B padded rows; head_dim 16: 32-B rows, and the upper half of
+//         (head_dim 64 / 96 / 128: rows padded by 16 B; head_dim 16: 32-B rows, and the upper half of
 //         the K = 32 contraction over the head is fed zeros); k-major operands (V in P@V, K in dS@K, dO / Q in the
 //         key-tile pass) are fetched with ds_read_b64_tr_b16.
 //   fp32: v_mfma_f32_16x16x4_f32 straight from global memory (parity path, exact fp32).
@@ -89,6 +89,9 @@ __device__ __forceinline__ typename MM<T>::frag frag_km(const Src<T>& s, int c0,
 // bf16 LDS image row stride in elements: 64 + 8 (144 B), or 16 unpadded (32 B: the row reads of a ds_read_b128 lane group
 // fall on sixteen different 16-byte slots as they are — attention_v2.hip v2_ld; the k-major reads of frag_km, rows
 // k0 .. k0 + 3 and k0 + 8 .. k0 + 11 per half wave, are 2-way there, on images of 1-3 KiB that these tiny rows hardly read)
+// 96 / 128: 208- and 272-byte rows.  frag_km's rows k0 .. k0 + 3 and k0 + 8 .. k0 + 11 are 2-way at every stride that is a
+// multiple of 16 bytes (8 rows apart is 0 or 128 bytes mod 256), so no padding makes these kernels conflict-free; + 8 is the
+// one with which the 17-tile rung of 96-wide heads still fits LDS (attn_v1_fits, attention_common.hpp).
 template <int HD> constexpr int IMG_LD = HD >= 32 ? HD + 8 : HD;
 
 // Stage a [S][HD] bf16 operand (rows = sequence positions) into an LDS image, zero padded
@@ -559,6 +562,7 @@ static int launch_fwd(hipStream_t st, const AttnParams& p) {
   constexpr bool BF = !std::is_same<T, float>::value;
   const int sld = s_pad32 + (BF ? 8 : 1);
   const size_t lds = (size_t)4 * 16 * sld * sizeof(T) + (BF ? (size_t)2 * s_pad32 * IMG_LD<HD> * 2 : 0);
+  if (lds > 160 * 1024) { set_error("attention (v1): S=%d with head_dim %d needs %zu bytes of LDS", p.f.S, HD, lds); return MDT_ERR_UNSUPPORTED; }
   return launch_route<attn_fwd_kernel<T, HD, NT, STRUCT, DROP>>("v1", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
 }
 
@@ -570,6 +574,12 @@ static int launch_bwd(hipStream_t st, const AttnParams& p) {
   const int nhist = STRUCT ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
   const size_t lds = (size_t)(2 * s_pad32 + nhist) * 4 + (size_t)4 * 16 * sld * sizeof(T) +
                (BF ? (size_t)2 * s_pad32 * IMG_LD<HD> * 2 : 0);
+  if (lds > 160 * 1024) { set_error("attention_bwd (v1): S=%d with head_dim %d needs %zu bytes of LDS", p.f.S, HD, lds); return MDT_ERR_UNSUPPORTED; }
+  if constexpr (!BF && HD > 64 && NT == 17 && STRUCT && DROP) {
+    // fp32, wide heads, 17 key tiles with structural bias and dropout: 512 registers and 15-17 more in scratch memory (as the
+    // 16- and 64-wide instantiations have) — not instantiated; the key-chunked path instead (a structural bias is never ragged)
+    return attention_long_dispatch(st, p, true);
+  } else
   return launch_route<attn_bwd_kernel<T, HD, NT, STRUCT, DROP>>("v1", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
 }
 
@@ -592,6 +602,18 @@ static int dispatch_hd(hipStream_t st, const AttnParams& p) {
   return p.f.attn_bias ? dispatch_nt<T, HD, true, BWD>(st, p) : dispatch_nt<T, HD, false, BWD>(st, p);
 }
 
+template <typename T, bool BWD>
+static int dispatch_width(hipStream_t st, const AttnParams& p) {
+  switch (p.f.hd) {
+    case 16: return dispatch_hd<T, 16, BWD>(st, p);
+    case 64: return dispatch_hd<T, 64, BWD>(st, p);
+    case 96: return dispatch_hd<T, 96, BWD>(st, p);
+    case 128: return dispatch_hd<T, 128, BWD>(st, p);
+  }
+  set_error("attention: head_dim %d unsupported (16, 64, 96 or 128)", p.f.hd);
+  return MDT_ERR_UNSUPPORTED;
+}
+
 template <bool BWD>
 static int dispatch(hipStream_t st, const AttnParams& p) {
   const mdt_attn_fwd_args& a = p.f;
@@ -603,22 +625,21 @@ static int dispatch(hipStream_t st, const AttnParams& p) {
     }
   } else if (a.S > 272) return attention_long_dispatch(st, p, BWD);      // discussion trees with more than 271 comments
   if (a.dtype == MDT_BF16) {
-    if (a.hd != 64 && a.hd != 16) {
-      set_error("attention(bf16): head_dim %d unsupported (16 or 64)", a.hd);
+    if (a.hd != 64 && a.hd != 16 && a.hd != 96 && a.hd != 128) {
+      set_error("attention(bf16): head_dim %d unsupported (16, 64, 96 or 128)", a.hd);
       return MDT_ERR_UNSUPPORTED;
     }
     // forward: register-resident P (v2) unless a plain dense bias (no structural terms), which only the kernels in this file
     // take; backward: attn_bwd_route (attention_v2.hip)
     const bool dense_only = (a.dense_bias != nullptr || p.d_dense_bias != nullptr) && !st_bias;
+    // ... whose images do not fit LDS for 128-wide heads of more than 208 tokens: the key-chunked path, forward and backward
+    if (dense_only && !attn_v1_fits(a.hd, a.S)) return attention_long_dispatch(st, p, BWD);
     const AttnRoute r = BWD ? attn_bwd_route(p) : dense_only ? AttnRoute::v1 : AttnRoute::v2;
     if (r == AttnRoute::v2) return attention_v2_dispatch(st, p, BWD);
     if (r != AttnRoute::v1) return attention_v3_bwd_dispatch(st, p, r);
-    return a.hd == 64 ? dispatch_hd<bf16_t, 64, BWD>(st, p) : dispatch_hd<bf16_t, 16, BWD>(st, p);
+    return dispatch_width<bf16_t, BWD>(st, p);
   }
-  if (a.hd == 64) return dispatch_hd<float, 64, BWD>(st, p);
-  if (a.hd == 16) return dispatch_hd<float, 16, BWD>(st, p);
-  set_error("attention(fp32): head_dim %d unsupported (16 or 64)", a.hd);
-  return MDT_ERR_UNSUPPORTED;
+  return dispatch_width<float, BWD>(st, p);
 }
 
 static int check_args(const mdt_attn_fwd_args& a) {

@@ -67,8 +67,12 @@ __device__ __forceinline__ float attn_drop_scale(const DropCfg& d, int bh, int S
 }
 
 int attention_v2_dispatch(hipStream_t st, const AttnParams& p, bool bwd);
-AttnRoute attn_bwd_route(const AttnParams& p);                                   // bf16, head_dim 16 | 64: attention_v2.hip
+AttnRoute attn_bwd_route(const AttnParams& p);                                   // bf16, head_dim 16 | 64 | 96 | 128: attention_v2.hip
 int attention_v3_bwd_dispatch(hipStream_t st, const AttnParams& p, AttnRoute r);   // r: v3 | v4 | v4x | v5
 int attention_long_dispatch(hipStream_t st, const AttnParams& p, bool bwd);     // S > 272: attention_long.hip
+// The bf16 kernels of attention.hip hold two [s_pad32][hd + 8] images and four score strips in LDS: with 128-wide heads the
+// 17-tile rung (S 209 .. 272: 2 x 288 x 136 x 2 + 4 x 16 x 296 x 2 = 194560 bytes) is past the 160 KiB of a workgroup; every
+// other (width, rung) fits.  A plain dense bias there takes the key-chunked long path in both directions.
+inline bool attn_v1_fits(int hd, int S) { return hd < 128 || S <= 208; }
 
 }  // namespace mdt

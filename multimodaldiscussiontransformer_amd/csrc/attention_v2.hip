@@ -15,10 +15,11 @@
 // and reduces the softmax reductions from four shuffles to two.
 // Same C ABI, same masks / structural bias / dropout semantics; attention.hip keeps the fp32
 // parity path and the bf16 kernels for a dense bias (and the backward of short structural-bias rows).
-// Head widths: 64 (BERT, ViT, the graph heads of the larger models) and 16 (the graph heads of Tiny mDT: D 128,
-// 8 heads).  The forward and the two-pass backward kernels (v2, v3) take both — a 16-wide head is half a K = 32
-// contraction step (v2_ks) and one 16-row output tile of the transposed products; the one-pass backward kernels
-// (v4, v4x, v5) are written for 64.  32 would need a launch line only (v2_ld / v2_ks cover it); it is not instantiated.
+// Head widths: 64 (BERT, ViT, the graph heads of the larger models), 16 (the graph heads of Tiny mDT: D 128,
+// 8 heads), 96 and 128 (graph heads of D 768 / 1024 with 8 heads, the registered architecture's default).  The forward
+// and the two-pass backward kernels (v2, v3) take all four — a 16-wide head is half a K = 32 contraction step (v2_ks)
+// and one 16-row output tile of the transposed products, the wide ones are three / four steps and six / eight tiles; the
+// one-pass backward kernels (v4, v4x, v5) are written for 64.  32 would need a launch line only (v2_ld / v2_ks cover it); it is not instantiated.
 #include "attention_common.hpp"
 
 namespace mdt {
@@ -29,18 +30,25 @@ namespace mdt {
 // different ones), and a 32-lane half of ds_read_b64_tr_b16 reads eight consecutive rows = 256 contiguous bytes.  Any
 // padding (48-byte rows: five slots shared by two rows of a b128 group) is worse, and the images are 4.5 x smaller than
 // with the 144-byte rows (S = 17: 2 KiB instead of 9 KiB for K and V).
-template <int HD> constexpr int v2_ld = HD >= 32 ? HD + 8 : HD;
+// 96- and 128-wide heads: HD + 16 (224- and 288-byte rows).  With HD + 8 (208 / 272 B) neither read kind is conflict-free:
+// eight consecutive rows of a ds_read_b64_tr_b16 half start 208 r or 16 r (mod 256) bytes into the 64 banks, so two 32-byte
+// pieces overlap (2-way), and a ds_read_b128 group finds 13 r + chunk or 17 r + chunk (mod 16) twice among its sixteen slots.
+// With an odd number of 32-byte units per row (7 and 9) the eight rows of a transposed read fall on eight different 8-bank
+// groups, and the b128 slots are 14 r + chunk and 2 r + chunk: sixteen different ones, as for the 32-byte rows above.
+// TIGHT: the 272-byte rows all the same — two 288-row images of 128-wide heads (S 257 .. 272) fit 160 KiB with nothing wider.
+template <int HD, bool TIGHT = false> constexpr int v2_ld = HD < 32 ? HD : (HD <= 64 || TIGHT) ? HD + 8 : HD + 16;
+template <int HD, int NT> constexpr int v2_ld_nt = v2_ld<HD, (HD == 128 && NT > 16)>;      // a whole-row kernel's stride
 // K = 32 contraction steps over a head.  A 16-wide head is half a step: lanes with lane >> 4 >= 2 (k = 16 .. 31) feed zeros.
 template <int HD> constexpr int v2_ks = (HD + 31) / 32;
 
-template <int HD>
+template <int HD, int LD = v2_ld<HD>>
 __device__ __forceinline__ void v2_stage(bf16_t* img, const bf16_t* g, int64_t g_ld, int S, int rows_pad, int tid, int nthr = 256) {
   constexpr int CH = HD / 8;
   for (int e = tid; e < rows_pad * CH; e += nthr) {
     const int r = e / CH, c = e - r * CH;
     bf16x8 v = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     if (r < S) v = *(const bf16x8*)(g + r * g_ld + c * 8);
-    *(bf16x8*)(img + r * v2_ld<HD> + c * 8) = v;
+    *(bf16x8*)(img + r * LD + c * 8) = v;
   }
 }
 
@@ -62,13 +70,13 @@ __device__ __forceinline__ void v2_stage_req(bf16x8 (&v)[NCH], const bf16_t* g, 
 }
 // `spare`: 16 bytes of LDS that chunks past the image land in — with the write under a lane mask instead, the compiler
 // sinks the chunk's load into the masked block and waits for it there (one more latency)
-template <int HD, int NCH>
+template <int HD, int NCH, int LD = v2_ld<HD>>
 __device__ __forceinline__ void v2_stage_put(bf16_t* img, const bf16x8 (&v)[NCH], int S, int rows_pad, int tid, int nthr, bf16_t* spare) {
   constexpr int CH = HD / 8;
 #pragma unroll
   for (int j = 0; j < NCH; ++j) {
     const int e = tid + j * nthr, r = e / CH, c = e - r * CH;
-    bf16_t* dst = e < rows_pad * CH ? img + r * v2_ld<HD> + c * 8 : spare;
+    bf16_t* dst = e < rows_pad * CH ? img + r * LD + c * 8 : spare;
     *(bf16x8*)dst = r < S ? v[j] : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
   }
 }
@@ -100,9 +108,9 @@ __device__ __forceinline__ int v2_chunk(int lane) {
   static_assert(HD % 32 == 0 || HD == 16, "a head is whole K = 32 steps, or half of one");
   return HD % 32 == 0 ? lane >> 4 : (lane >> 4) & (HD / 8 - 1);
 }
-template <int HD>
+template <int HD, int LD = v2_ld<HD>>
 __device__ __forceinline__ bf16x8 v2_frag_lds(const bf16_t* img, int rc0, int k0, int lane) {
-  const bf16_t* a = img + (rc0 + (lane & 15)) * v2_ld<HD> + k0 + 8 * v2_chunk<HD>(lane);
+  const bf16_t* a = img + (rc0 + (lane & 15)) * LD + k0 + 8 * v2_chunk<HD>(lane);
   return *(const __attribute__((address_space(3))) bf16x8*)LDS_PTR(a);
 }
 template <int HD>
@@ -117,12 +125,12 @@ __device__ __forceinline__ bf16x8 v2_frag_glb(const bf16_t* p, int64_t ld, int r
 }
 // A operand X^T[d][k] for a K = 32 step whose k index runs over rows {t0*16 + 4g + j} (j < 4)
 // and {(t0+1)*16 + 4g + j - 4} of the row-major image X[row][d]; d0 + 16 <= HD (a 16-wide head has the one tile d0 = 0)
-template <int HD>
+template <int HD, int LD = v2_ld<HD>>
 __device__ __forceinline__ bf16x8 v2_frag_tr(const bf16_t* img, int t0, int d0, int lane) {
   const int g = lane >> 4, q4 = (lane >> 2) & 3, pp = lane & 3;
-  const bf16_t* a = img + (t0 * 16 + 4 * g + q4) * v2_ld<HD> + d0 + pp * 4;
+  const bf16_t* a = img + (t0 * 16 + 4 * g + q4) * LD + d0 + pp * 4;
   const bf16x4 lo = lds_read_tr16(a);
-  const bf16x4 hi = lds_read_tr16(a + 16 * v2_ld<HD>);
+  const bf16x4 hi = lds_read_tr16(a + 16 * LD);
   return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 // B operand from two accumulator tiles (rows = k index)
@@ -177,7 +185,7 @@ __device__ __forceinline__ Row32 rows4_exchange(const f32x4 (&x)[4], float scale
 // dense bias is served by attention.hip (see the dispatch there).
 template <int HD, int NT, bool STRUCT, bool DROP, int NW>     // NW waves: 4, or 8 for long sequences (two workgroups per CU by LDS)
 __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
-  constexpr int ND = HD / 16, NP = (NT + 1) / 2, S_PAD = NP * 32;
+  constexpr int ND = HD / 16, NP = (NT + 1) / 2, S_PAD = NP * 32, LD = v2_ld_nt<HD, NT>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mdt_attn_fwd_args& a = P.f;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -189,8 +197,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
   const bf16_t* qkv = (const bf16_t*)a.qkv + row0 * a.ld_qkv + h * HD;
   const int64_t tld = a.pos_stride * a.ld_qkv;
   bf16_t* imgK = (bf16_t*)smem;
-  bf16_t* imgV = imgK + S_PAD * v2_ld<HD>;
-  float* s_kb = (float*)(imgV + S_PAD * v2_ld<HD>);   // key-only bias (0 / -inf), [S_PAD]
+  bf16_t* imgV = imgK + S_PAD * LD;
+  float* s_kb = (float*)(imgV + S_PAD * LD);   // key-only bias (0 / -inf), [S_PAD]
   BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
   // Ragged sequences: key tiles past this sequence's length are staged as zeros, their scores come out of the
   // (unguarded: a guard there costs the compiler 80 registers) MFMA loop as exact zeros and every later
@@ -202,9 +210,13 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
   constexpr int MAXT = (NT + NW - 1) / NW;
   int n_qt = (S + 15) >> 4;
   if (a.q_limit > 0 && ((a.q_limit + 15) >> 4) < n_qt) n_qt = (a.q_limit + 15) >> 4;   // only these query tiles are needed
-  bf16x8 fq_all[MAXT][v2_ks<HD>];
+  // Wide heads on the long structural rows (4-wave form, up to five tiles of 3-4 fragments): the tile loop below is past
+  // what the compiler unrolls in full, and an fq_all indexed by a loop counter lives in scratch memory — those fetch each
+  // tile's fragments at its turn instead.
+  constexpr bool PFQ = !(HD > 64 && STRUCT && NT >= 13);
+  bf16x8 fq_all[PFQ ? MAXT : 1][v2_ks<HD>];
 #pragma unroll
-  for (int k = 0; k < MAXT; ++k) {
+  for (int k = 0; k < (PFQ ? MAXT : 0); ++k) {
     const int qt_k = wave + NW * k;
     if (qt_k < n_qt) {
 #pragma unroll
@@ -220,8 +232,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
     v2_stage_req<HD, NCH>(cv, qkv + 2 * D, tld, S, tid, NW * 64);
 #pragma unroll
     for (int j = 0; j < NKB; ++j) kbv[j] = key_only_bias_req(bc, tid + j * NW * 64, qkv);
-    v2_stage_put<HD, NCH>(imgK, ck, S, S_PAD, tid, NW * 64, (bf16_t*)(s_kb + S_PAD));
-    v2_stage_put<HD, NCH>(imgV, cv, S, S_PAD, tid, NW * 64, (bf16_t*)(s_kb + S_PAD));
+    v2_stage_put<HD, NCH, LD>(imgK, ck, S, S_PAD, tid, NW * 64, (bf16_t*)(s_kb + S_PAD));
+    v2_stage_put<HD, NCH, LD>(imgV, cv, S, S_PAD, tid, NW * 64, (bf16_t*)(s_kb + S_PAD));
 #pragma unroll
     for (int j = 0; j < NKB; ++j)
       if (tid + j * NW * 64 < S_PAD) s_kb[tid + j * NW * 64] = key_only_bias_of(bc, tid + j * NW * 64, kbv[j]);
@@ -239,7 +251,10 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
     const int qc = q < S ? q : S - 1;
     bf16x8 fq[v2_ks<HD>];
 #pragma unroll
-    for (int ks = 0; ks < v2_ks<HD>; ++ks) fq[ks] = fq_all[k][ks];
+    for (int ks = 0; ks < v2_ks<HD>; ++ks) {
+      if constexpr (PFQ) fq[ks] = fq_all[k][ks];
+      else fq[ks] = v2_frag_glb<HD>(qkv, tld, S, q0, ks * 32, lane);
+    }
     f32x4 sc[2 * NP];
 #pragma unroll
     for (int t = 0; t < 2 * NP; ++t) sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -247,7 +262,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
       for (int ks = 0; ks < v2_ks<HD>; ++ks) {
-        sc[t] = mfma_bf16(v2_frag_lds<HD>(imgK, t * 16, ks * 32, lane), fq[ks], sc[t]);
+        sc[t] = mfma_bf16(v2_frag_lds<HD, LD>(imgK, t * 16, ks * 32, lane), fq[ks], sc[t]);
         if (ks == v2_ks<HD> - 1 && (t & 1)) __builtin_amdgcn_sched_barrier(0);   // bound operand prefetch depth (registers)
       }
     }
@@ -304,7 +319,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
       if (2 * pi >= ntk) continue;
       const bf16x8 fp = v2_pack(sc[2 * pi], sc[2 * pi + 1]);
 #pragma unroll
-      for (int d = 0; d < ND; ++d) o[d] = mfma_bf16(v2_frag_tr<HD>(imgV, 2 * pi, d * 16, lane), fp, o[d]);
+      for (int d = 0; d < ND; ++d) o[d] = mfma_bf16(v2_frag_tr<HD, LD>(imgV, 2 * pi, d * 16, lane), fp, o[d]);
       __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (ND == 4) {
@@ -314,12 +329,29 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
         *(bf16x8*)orow = ov.a;
         *(bf16x8*)(orow + 32) = ov.b;
       }
-    } else {
+    } else if constexpr (ND == 1) {
       // one 16-column tile: lane (g, c) holds columns 4 g ... + 3 of row c — the four lanes of a row write its 32 bytes
-      static_assert(ND == 1, "16- or 64-column rows");
       if (q < S) {
         bf16_t* orow = (bf16_t*)a.out + (row0 + (int64_t)q * a.pos_stride) * a.ld_out + h * HD + 4 * g;
         *(bf16x4*)orow = bf16x4{(bf16_t)(o[0][0] * inv), (bf16_t)(o[0][1] * inv), (bf16_t)(o[0][2] * inv), (bf16_t)(o[0][3] * inv)};
+      }
+    } else {
+      // 96 / 128 columns: 64-column groups leave as above, the two tiles left over of a 96-wide head like the single tile
+      static_assert(ND == 6 || ND == 8, "16-, 64-, 96- or 128-column rows");
+      bf16_t* orow = (bf16_t*)a.out + (row0 + (int64_t)q * a.pos_stride) * a.ld_out + h * HD;
+#pragma unroll
+      for (int d4 = 0; d4 + 4 <= ND; d4 += 4) {
+        const f32x4 x[4] = {o[d4], o[d4 + 1], o[d4 + 2], o[d4 + 3]};
+        const Row32 ov = rows4_exchange(x, inv);
+        if (q < S) {
+          *(bf16x8*)(orow + d4 * 16 + rows4_off(g)) = ov.a;
+          *(bf16x8*)(orow + d4 * 16 + rows4_off(g) + 32) = ov.b;
+        }
+      }
+      if (q < S) {
+#pragma unroll
+        for (int d = ND & ~3; d < ND; ++d)
+          *(bf16x4*)(orow + d * 16 + 4 * g) = bf16x4{(bf16_t)(o[d][0] * inv), (bf16_t)(o[d][1] * inv), (bf16_t)(o[d][2] * inv), (bf16_t)(o[d][3] * inv)};
       }
     }
   }
@@ -537,9 +569,12 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
 // kernel from 1 to 3-4 waves per SIMD — these sequences are short and the kernel is latency-bound.
 //   pass A (queries on lanes): for each key chunk: S^T, dP^T -> dS^T -> dQ^T += K^T dS^T
 //   pass B (keys on lanes):    for each query chunk: S, dP -> P, dS -> dV^T += dO^T P, dK^T += Q^T dS
-template <int HD, bool STRUCT, bool DROP, bool PF>   // PF: fragments of the next tile requested one tile ahead (16 more registers)
+// CT: 16-key tiles per chunk, 4 — or 2 with TIGHT (the 272-byte rows, v2_ld): 128-wide heads of 257 .. 272 tokens, whose images
+// fit 160 KiB as 288 rows and not as 320
+template <int HD, bool STRUCT, bool DROP, bool PF, int CT = 4, bool TIGHT = false>   // PF: fragments of the next tile requested one tile ahead (16 more registers)
 __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad) {
-  constexpr int ND = HD / 16;
+  constexpr int ND = HD / 16, LD = v2_ld<HD, TIGHT>, CW = 16 * CT, CSH = CT == 4 ? 6 : 5;
+  static_assert(CT == 4 || CT == 2, "chunks of 64 or 32 keys");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mdt_attn_fwd_args& a = P.f;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -555,14 +590,14 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
   const int64_t tld = a.pos_stride * a.ld_qkv, dld = a.pos_stride * P.ld_dout, old_ = a.pos_stride * a.ld_out,
                 gld = a.pos_stride * P.ld_dqkv;
   bf16_t* img0 = (bf16_t*)smem;
-  bf16_t* img1 = img0 + s_pad * v2_ld<HD>;
-  float* s_kb = (float*)(img1 + s_pad * v2_ld<HD>);
+  bf16_t* img1 = img0 + s_pad * LD;
+  float* s_kb = (float*)(img1 + s_pad * LD);
   float* s_lse = s_kb + s_pad;
   float* s_delta = s_lse + s_pad;
   float* s_hist = s_delta + s_pad;
   const int nhist = STRUCT ? ((a.num_spatial + 1 + 3) & ~3) : 0;
   BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
-  const int s_live = (S + 63) & ~63;                    // rows this (possibly ragged) sequence really uses, in 64-key chunks
+  const int s_live = (S + CW - 1) & ~(CW - 1);                    // rows this (possibly ragged) sequence really uses, in 64-key chunks
   if (s_live > s_pad) return;                           // longer than this launch's bound (s_cap)
   // Latency hiding (the waves of this kernel sat in s_waitcnt / s_barrier for half to two thirds of their cycles):
   // the Q / dO fragments of a wave's first query tile are requested before K / V are staged, and every later
@@ -575,8 +610,8 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
       fo_n[ks] = v2_frag_glb<HD>(dout, dld, S, wave * 16, ks * 32, lane);
     }
   }
-  v2_stage<HD>(img0, qkv + D, tld, S, s_live, tid, nthr);      // K
-  v2_stage<HD>(img1, qkv + 2 * D, tld, S, s_live, tid, nthr);  // V
+  v2_stage<HD, LD>(img0, qkv + D, tld, S, s_live, tid, nthr);      // K
+  v2_stage<HD, LD>(img1, qkv + 2 * D, tld, S, s_live, tid, nthr);  // V
   // s_lse holds lse * log2(e) (+inf for rows without a finite lse, so every p of such a row is exp2(-inf) = 0);
   // s_delta holds delta * (1 - p_drop): the 1 / (1 - p_drop) factor of the dropout mask is folded out of
   // dS and dV and applied once to the outputs.
@@ -606,11 +641,11 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
   const float scale2 = a.scale * LOG2E;
   const int g = lane >> 4, c = lane & 15;
   const int n_t = (S + 15) >> 4;
-  const int n_chunk = s_live >> 6;          // 64-wide chunks
+  const int n_chunk = s_live >> CSH;        // 64-wide chunks (CT 2: 32-wide)
   // q_limit: queries beyond it carry no gradient (dout = 0, dQ = 0): pass A visits only the needed query tiles, pass B
   // sums over the query chunks that contain them
   const int n_tq = (a.q_limit > 0 && ((a.q_limit + 15) >> 4) < n_t) ? (a.q_limit + 15) >> 4 : n_t;
-  const int n_chunk_q = (a.q_limit > 0 && ((a.q_limit + 63) >> 6) < n_chunk) ? (a.q_limit + 63) >> 6 : n_chunk;
+  const int n_chunk_q = (a.q_limit > 0 && ((a.q_limit + CW - 1) >> CSH) < n_chunk) ? (a.q_limit + CW - 1) >> CSH : n_chunk;
 
   // ------------------------------------------------------------------ pass A (queries on lanes)
   for (int qt = wave; qt < n_tq; qt += nw) {
@@ -637,20 +672,20 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
 #pragma unroll
     for (int d = 0; d < ND; ++d) dq[d] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int ch = 0; ch < n_chunk; ++ch) {
-      const int t0 = ch * 4;
-      f32x4 sc[4], dp[4];
+      const int t0 = ch * CT;
+      f32x4 sc[CT], dp[CT];
 #pragma unroll
-      for (int t = 0; t < 4; ++t) { sc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      for (int t = 0; t < CT; ++t) { sc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+      for (int t = 0; t < CT; ++t)
 #pragma unroll
         for (int ks = 0; ks < v2_ks<HD>; ++ks) {
-          sc[t] = mfma_bf16(v2_frag_lds<HD>(img0, (t0 + t) * 16, ks * 32, lane), fq[ks], sc[t]);
-          dp[t] = mfma_bf16(v2_frag_lds<HD>(img1, (t0 + t) * 16, ks * 32, lane), fo[ks], dp[t]);
+          sc[t] = mfma_bf16(v2_frag_lds<HD, LD>(img0, (t0 + t) * 16, ks * 32, lane), fq[ks], sc[t]);
+          dp[t] = mfma_bf16(v2_frag_lds<HD, LD>(img1, (t0 + t) * 16, ks * 32, lane), fo[ks], dp[t]);
           if (ks == v2_ks<HD> - 1 && (t & 1)) __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
+      for (int t = 0; t < CT; ++t) {
         const f32x4 kb = *(const f32x4*)(s_kb + (t0 + t) * 16 + 4 * g);
         bool keep[4] = {true, true, true, true};
         if constexpr (DROP) {
@@ -686,10 +721,10 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
         }
       }
 #pragma unroll
-      for (int pi = 0; pi < 2; ++pi) {
+      for (int pi = 0; pi < CT / 2; ++pi) {
         const bf16x8 fs = v2_pack(sc[2 * pi], sc[2 * pi + 1]);
 #pragma unroll
-        for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr<HD>(img0, t0 + 2 * pi, d * 16, lane), fs, dq[d]);
+        for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr<HD, LD>(img0, t0 + 2 * pi, d * 16, lane), fs, dq[d]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -710,8 +745,8 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
     }
   }
   __syncthreads();   // K / V images are free
-  v2_stage<HD>(img0, qkv, tld, S, s_live, tid, nthr);    // Q
-  v2_stage<HD>(img1, dout, dld, S, s_live, tid, nthr);   // dO
+  v2_stage<HD, LD>(img0, qkv, tld, S, s_live, tid, nthr);    // Q
+  v2_stage<HD, LD>(img1, dout, dld, S, s_live, tid, nthr);   // dO
   if constexpr (STRUCT) {
     if (P.d_sp_table) {
       for (int i = tid; i <= a.num_spatial; i += nthr) {
@@ -753,20 +788,20 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
 #pragma unroll
     for (int d = 0; d < ND; ++d) { dv[d] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[d] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     for (int ch = 0; ch < n_chunk_q; ++ch) {
-      const int t0 = ch * 4;
-      f32x4 sc[4], dp[4];
+      const int t0 = ch * CT;
+      f32x4 sc[CT], dp[CT];
 #pragma unroll
-      for (int t = 0; t < 4; ++t) { sc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      for (int t = 0; t < CT; ++t) { sc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+      for (int t = 0; t < CT; ++t)
 #pragma unroll
         for (int ks = 0; ks < v2_ks<HD>; ++ks) {
-          sc[t] = mfma_bf16(v2_frag_lds<HD>(img0, (t0 + t) * 16, ks * 32, lane), fk[ks], sc[t]);   // S[q][key]
-          dp[t] = mfma_bf16(v2_frag_lds<HD>(img1, (t0 + t) * 16, ks * 32, lane), fv[ks], dp[t]);   // dP[q][key]
+          sc[t] = mfma_bf16(v2_frag_lds<HD, LD>(img0, (t0 + t) * 16, ks * 32, lane), fk[ks], sc[t]);   // S[q][key]
+          dp[t] = mfma_bf16(v2_frag_lds<HD, LD>(img1, (t0 + t) * 16, ks * 32, lane), fv[ks], dp[t]);   // dP[q][key]
           if (ks == v2_ks<HD> - 1 && (t & 1)) __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
+      for (int t = 0; t < CT; ++t) {
         const int qb = (t0 + t) * 16 + 4 * g;
         const f32x4 l2v = *(const f32x4*)(s_lse + qb);
         const f32x4 dlv = *(const f32x4*)(s_delta + qb);
@@ -794,13 +829,13 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
         }
       }
 #pragma unroll
-      for (int pi = 0; pi < 2; ++pi) {
+      for (int pi = 0; pi < CT / 2; ++pi) {
         const bf16x8 fp = v2_pack(sc[2 * pi], sc[2 * pi + 1]);
         const bf16x8 fs = v2_pack(dp[2 * pi], dp[2 * pi + 1]);
 #pragma unroll
         for (int d = 0; d < ND; ++d) {
-          dv[d] = mfma_bf16(v2_frag_tr<HD>(img1, t0 + 2 * pi, d * 16, lane), fp, dv[d]);
-          dk[d] = mfma_bf16(v2_frag_tr<HD>(img0, t0 + 2 * pi, d * 16, lane), fs, dk[d]);
+          dv[d] = mfma_bf16(v2_frag_tr<HD, LD>(img1, t0 + 2 * pi, d * 16, lane), fp, dv[d]);
+          dk[d] = mfma_bf16(v2_frag_tr<HD, LD>(img0, t0 + 2 * pi, d * 16, lane), fs, dk[d]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -821,6 +856,11 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
 template <int HD, bool STRUCT, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_v3_kernel(AttnParams P, int s_pad) {
   attn_bwd_v3_body<HD, STRUCT, DROP, true>(P, s_pad);
+}
+// 128-wide heads of 257 .. 272 tokens: 288-row images with 272-byte rows, walked in 32-key chunks
+template <int HD, bool STRUCT, bool DROP>
+__global__ __launch_bounds__(256) void attn_bwd_v3_tight_kernel(AttnParams P, int s_pad) {
+  attn_bwd_v3_body<HD, STRUCT, DROP, true, 2, true>(P, s_pad);
 }
 // Short sequences (S <= 128: 38 KB of LDS, four workgroups fit a CU): the same body held to 128 registers (a handful
 // spill) so that four waves per SIMD are resident — the ragged BERT sequences are latency-bound, not register-bound.
@@ -1466,7 +1506,7 @@ static size_t v4_lds_bytes(int S, int* rows_img, int* ldq) {
   return b <= 160 * 1024 ? b : 0;
 }
 
-// The backward kernel of a bf16 launch with head_dim 64 or 16 (S <= 272; length-binned launches, 64 only: s_cap <= 272).
+// The backward kernel of a bf16 launch with head_dim 16, 64, 96 or 128 (S <= 272; length-binned launches, 64 only: s_cap <= 272).
 // Default, in order:
 //   length-binned launches (seq_ids / s_cap)              -> the family below
 //   a dense bias without structural terms                -> v1 (attention.hip: the only kernels that take one)
@@ -1477,7 +1517,9 @@ static size_t v4_lds_bytes(int S, int* rows_img, int* ldq) {
 // The family, without a structural bias, where the one-pass dS image fits LDS (S <= 208): v5 (9-13 key tiles, persistent),
 // v4x (<= 6 key tiles: delta = sum P o dP summed in the kernel, in fp32), v4 (7-8 key tiles); past that, and with a
 // structural bias: the two-pass v3.  Measured at C2 shapes: profiles/round1_attention_v2.txt, tools/attn_onepass_ab.py.
-// The one-pass kernels are written for 64-wide heads: with head_dim 16 the family is always v3.
+// The one-pass kernels are written for 64-wide heads: with head_dim 16, 96 or 128 the family is always v3.
+// A plain dense bias on 128-wide heads of more than 208 tokens never gets here: the v1 images do not fit LDS there and
+// dispatch() in attention.hip takes the key-chunked long path (attn_v1_fits).
 // MDT_ATTN_BWD=<kernel> takes that kernel wherever its preconditions (ok() below) hold.  v1 and v2 never see q_limit or
 // length bins (they would read the out / lse rows the v2 forward skipped — unwritten memory; tests:
 // ..._never_reads_what_forward_did_not_write), v2 takes S <= 112 only, the one-pass kernels take no structural bias.
@@ -1491,7 +1533,7 @@ AttnRoute attn_bwd_route(const AttnParams& p) {
   const bool one_pass = a.hd == 64 && !st_bias && !dense_only && v4_lds_bytes(cap, &rows_img, &ldq) != 0 && n_t <= 16;
   auto ok = [&](AttnRoute r) {
     switch (r) {
-      case AttnRoute::v1: return !binned && a.q_limit == 0;
+      case AttnRoute::v1: return !binned && a.q_limit == 0 && attn_v1_fits(a.hd, a.S);
       case AttnRoute::v2: return !binned && !dense_only && a.q_limit == 0 && a.S <= 112;
       case AttnRoute::v3: return !dense_only;
       case AttnRoute::v4: return one_pass;
@@ -1539,12 +1581,17 @@ static int launch_v3(hipStream_t st, const AttnParams& p, AttnRoute r) {
     if (r != AttnRoute::v3) return launch_one_pass<DROP>(st, p, r);
   }
   const int cap = p.f.s_cap > 0 ? p.f.s_cap : p.f.S;          // longest sequence of this launch
-  const int s_pad = (cap + 63) & ~63;
+  const bool tight = HD == 128 && cap > 256;                  // 320 rows of 128-wide heads do not fit: 288 rows, 32-key chunks
+  const int s_pad = tight ? (cap + 31) & ~31 : (cap + 63) & ~63;
   const int nhist = STRUCT ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
-  const size_t lds = (size_t)2 * s_pad * v2_ld<HD> * 2 + (size_t)3 * s_pad * 4 + (size_t)nhist * 4;
+  const size_t lds = (size_t)2 * s_pad * (tight ? v2_ld<HD, true> : v2_ld<HD>) * 2 + (size_t)3 * s_pad * 4 + (size_t)nhist * 4;
   if (lds > 160 * 1024) { set_error("attention_bwd_v3: S=%d needs %zu bytes of LDS", cap, lds); return MDT_ERR_UNSUPPORTED; }
   const dim3 grid(p.f.H, p.f.nseq);
-  if constexpr (STRUCT) return launch_route<attn_bwd_v3_kernel<HD, true, DROP>>("v3", grid, 256, lds, st, p, s_pad);
+  if constexpr (HD > 64) {
+    // wide heads: dK / dV alone are 2 x HD / 16 accumulator tiles — the 128-register build below would spill them
+    if (tight) return launch_route<attn_bwd_v3_tight_kernel<HD, STRUCT, DROP>>("v3", grid, 256, lds, st, p, s_pad);
+    return launch_route<attn_bwd_v3_kernel<HD, STRUCT, DROP>>("v3", grid, 256, lds, st, p, s_pad);
+  } else if constexpr (STRUCT) return launch_route<attn_bwd_v3_kernel<HD, true, DROP>>("v3", grid, 256, lds, st, p, s_pad);
   // long sequences (ViT: 13 tiles): LDS allows two workgroups per CU; 8 waves each in the 128-register build = 4 waves
   // per SIMD instead of 2 (in-call A/B at the ViT shape: +0.7 % on the step)
   else return launch_route<attn_bwd_v3_occ4_kernel<HD, DROP>>("v3", grid, s_pad <= 128 ? 256 : 512, lds, st, p, s_pad);
@@ -1559,16 +1606,21 @@ static int dispatch_v3(hipStream_t st, const AttnParams& p, AttnRoute r) {
   return launch_v3<HD, false, false>(st, p, r);
 }
 
-// head_dim: 64 or 16 (dispatch() in attention.hip refuses every other width before it gets here)
+// head_dim: 16, 64, 96 or 128 (dispatch() in attention.hip refuses every other width before it gets here)
 int attention_v3_bwd_dispatch(hipStream_t st, const AttnParams& p, AttnRoute r) {
-  return p.f.hd == 16 ? dispatch_v3<16>(st, p, r) : dispatch_v3<64>(st, p, r);
+  switch (p.f.hd) {
+    case 16: return dispatch_v3<16>(st, p, r);
+    case 96: return dispatch_v3<96>(st, p, r);
+    case 128: return dispatch_v3<128>(st, p, r);
+    default: return dispatch_v3<64>(st, p, r);
+  }
 }
 
 template <int HD, int NT, bool STRUCT, bool DROP, bool BWD>
 static int launch_v2(hipStream_t st, const AttnParams& p) {
   constexpr int S_PAD = ((NT + 1) / 2) * 32;
   const int nhist = (STRUCT && BWD) ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
-  const size_t lds = (size_t)2 * S_PAD * v2_ld<HD> * 2 + (size_t)(BWD ? 3 : 1) * S_PAD * 4 + (size_t)nhist * 4 + (BWD ? 0 : 16);   // forward: + the staging's spare chunk
+  const size_t lds = (size_t)2 * S_PAD * (BWD ? v2_ld<HD> : v2_ld_nt<HD, NT>) * 2 + (size_t)(BWD ? 3 : 1) * S_PAD * 4 + (size_t)nhist * 4 + (BWD ? 0 : 16);   // forward: + the staging's spare chunk
   if constexpr (BWD && NT > 7) {
     // the whole-row backward runs out of registers past 112 keys; attn_bwd_route sends those to the v3 family
     set_error("attention_v2: backward supports S <= 112 (got %d)", p.f.S);
@@ -1602,7 +1654,12 @@ static int dispatch_v2(hipStream_t st, const AttnParams& p, bool bwd) {
 }
 
 int attention_v2_dispatch(hipStream_t st, const AttnParams& p, bool bwd) {
-  return p.f.hd == 16 ? dispatch_v2<16>(st, p, bwd) : dispatch_v2<64>(st, p, bwd);
+  switch (p.f.hd) {
+    case 16: return dispatch_v2<16>(st, p, bwd);
+    case 96: return dispatch_v2<96>(st, p, bwd);
+    case 128: return dispatch_v2<128>(st, p, bwd);
+    default: return dispatch_v2<64>(st, p, bwd);
+  }
 }
 
 }  // namespace mdt

@@ -56,7 +56,7 @@ struct Switches {
   bool gemm_stamp;           // MDT_GEMM_STAMP
   int gemm_diag;             // MDT_GEMM_DIAG      (0: none)
   int gemm_f8w;              // MDT_GEMM_F8W       (default 1: 8-bit GEMMs on the 16x16x128 block-MFMA kernel where it has an instantiation; 0: the 8-wave kernel)
-  AttnRoute attn_bwd;        // MDT_ATTN_BWD       (none: the default kernel) v1 | v2 | v3 | v4 | v4x | v5 — bf16 backward (head_dim 16: v1 | v2 | v3)
+  AttnRoute attn_bwd;        // MDT_ATTN_BWD       (none: the default kernel) v1 | v2 | v3 | v4 | v4x | v5 — bf16 backward (head_dim 16 / 96 / 128: v1 | v2 | v3)
   bool ln_generic;           // MDT_LN_GENERIC     (default 0; 1: bf16 rows of 256 / 512 / 768 / 1024 take the generic LayerNorm backward kernel — tests, A/B runs)
   int ln_bwd_wgs;            // MDT_LN_BWD_WGS     (workgroups a LayerNorm backward launch aims for; tuning)
 };

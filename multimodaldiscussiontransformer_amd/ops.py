@@ -150,7 +150,8 @@ def _attn_args(qkv, out, lse, nseq, S, H, hd, seq_stride, pos_stride, scale, key
 def attention_fwd(qkv, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None, key_mask=None, dense_bias=None,
                   attn_bias=None, spatial_pos=None, sp_table=None, virt=None, key_pad=None, drop_p=0.0, drop_seed=0,
                   seq_offsets=None, q_limit=0, bins=None):
-    """qkv [rows, 3*D] → (out [rows, D], lse f32[nseq, H, S]).  ``q_limit`` > 0: only the first q_limit rows of every
+    """qkv [rows, 3*D] → (out [rows, D], lse f32[nseq, H, S]); head widths D // H of 16, 64, 96 and 128, fp32 and bf16.
+    ``q_limit`` > 0: only the first q_limit rows of every
     sequence are needed as queries (other rows of out / lse unspecified).  ``seq_offsets`` i32[nseq+1]: ragged sequences
     (sequence s = rows off[s]..off[s+1], at most S of them), see include/mdt_hip.h.  ``bins``: [(seq_ids i32[n], cap), ...]
     — a partition of the ragged set by length (no sequence of a bin longer than its cap): one launch per bin, each with
