@@ -66,10 +66,11 @@ enum {
 
 int mdt_abi_version(void);
 const char* mdt_last_error_string(void);
-/* The route of the calling thread's last successful GEMM, attention or LayerNorm launch ("" before the first): mdt_gemm "generic",
+/* The route of the calling thread's last successful GEMM, attention, LayerNorm or mdt_row_axpby launch ("" before the first): mdt_gemm "generic",
  * "tile128", "tile256x128", "pp256", "pp256p", "w4p", "w4s"; mdt_gemm_fp8 "f8_w4", "f8_pp256p"; attention "v1" ... "v5", "v4x",
  * "long"; mdt_layernorm_fwd "ln_fwd", mdt_layernorm_fwd_q8 with an fp8 copy "ln_fwd_q8", mdt_layernorm_bwd "ln_rows" (the
- * scalar-address kernel) or "ln_generic".  What MDT_GEMM_ROUTE / MDT_ATTN_BWD force is checked against it (a forced route whose preconditions fail runs the default). */
+ * scalar-address kernel) or "ln_generic"; mdt_row_axpby "row_vec" (16-byte vectors) or "row_scalar" (D, a row stride or a base pointer
+ * of dst / a / b not vectorisable).  What MDT_GEMM_ROUTE / MDT_ATTN_BWD force is checked against it (a forced route whose preconditions fail runs the default). */
 const char* mdt_last_route(void);
 /* sha256 (hex) over csrc/ and this header at the time the library was linked (build.py source_hash()): the Python side
  * refuses a libmdt_hip.so that was not built from the sources next to it. */
@@ -223,7 +224,9 @@ int mdt_graph_attn_bias(void* stream, int dtype, int nseq, int S, int H, const f
  * dst[di(r), :] = alpha * a[ai(r), :] + beta * b[bi(r), :] (+ dst if accumulate)
  * for r in [0, nrows); an index array may be NULL and then a two-level affine map is
  * applied: row = (r / inner) * stride + r % inner + offset (inner = 1: r*stride + offset).
- * A negative index skips the row (dst) or contributes zero (a, b).  This one kernel is the bottleneck-token
+ * A negative index skips the row (dst) or contributes zero (a, b).  Rows of 16-byte vectors (D and every row stride a multiple of
+ * 4 fp32 / 8 bf16 elements, dst / a / b on a 16-byte boundary) take the vector kernel, everything else the scalar one, with the
+ * same arithmetic; mdt_last_route() says which ran ("row_vec" / "row_scalar").  This one kernel is the bottleneck-token
  * exchange between the text, image and graph token spaces
  * (modules/multigraphormer_graph_encoder.py:339,363-371,425,435;
  *  modules/multi_graphormer_fusion_layer.py:37-66) on precomputed CSR indices — the

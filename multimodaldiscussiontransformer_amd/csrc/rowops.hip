@@ -354,7 +354,9 @@ extern "C" int mdt_row_axpby(void* stream, int dtype, int64_t nrows, int D, void
     else hipLaunchKernelGGL((row_axpby_scalar_kernel<bf16_t>), grid, 256, 0, st, ARGS_(bf16_t));
   }
 #undef ARGS_
-  return check_launch("row_axpby");
+  const int e = check_launch("row_axpby");
+  if (e == MDT_OK) set_last_route(vec ? "row_vec" : "row_scalar");
+  return e;
 }
 
 extern "C" int mdt_row_scatter_add_f32(void* stream, int dtype, int64_t nrows, int D, float* table, int64_t ldt,
