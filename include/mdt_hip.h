@@ -70,7 +70,7 @@ const char* mdt_last_error_string(void);
  * "tile128", "tile256x128", "pp256", "pp256p", "w4p", "w4s"; mdt_gemm_fp8 "f8_w4", "f8_pp256p"; attention "v1" ... "v5", "v4x",
  * "long"; mdt_layernorm_fwd "ln_fwd", mdt_layernorm_fwd_q8 with an fp8 copy "ln_fwd_q8", mdt_layernorm_bwd "ln_rows" (the
  * scalar-address kernel) or "ln_generic"; mdt_row_axpby "row_vec" (16-byte vectors) or "row_scalar" (D, a row stride or a base pointer
- * of dst / a / b not vectorisable).  What MDT_GEMM_ROUTE / MDT_ATTN_BWD force is checked against it (a forced route whose preconditions fail runs the default). */
+ * of dst / a / b not vectorisable); mdt_act_fwd "act_vec" or "act_scalar".  What MDT_GEMM_ROUTE / MDT_ATTN_BWD force is checked against it (a forced route whose preconditions fail runs the default). */
 const char* mdt_last_route(void);
 /* sha256 (hex) over csrc/ and this header at the time the library was linked (build.py source_hash()): the Python side
  * refuses a libmdt_hip.so that was not built from the sources next to it. */
@@ -110,6 +110,22 @@ int mdt_dropout(void* stream, int dtype, int64_t rows, int D, const void* x, int
                 float p, uint64_t seed);
 /* Test hook: mask[i] = 1 if counter i of site `seed` is kept. */
 int mdt_dropout_mask(void* stream, int64_t n, float p, uint64_t seed, uint8_t* mask);
+
+/* FFN activation as a launch of its own (fairseq utils.get_activation_fn as used by modules/graphormer_graph_encoder_layer.py:50,135;
+ * the fused fc1 epilogue MDT_EPI_GELU | MDT_EPI_AUX_GRAD knows the erf GELU only): rows x N elements,
+ *   h[r, c] = act(pre[r, c]) * s,  u[r, c] = act'(pre[r, c]) * s,  s = keep(drop_seed, r*N + c) / (1 - drop_p), 1 when drop_p == 0
+ * (the counters of mdt_dropout, so mdt_dropout_mask regenerates the mask).  u is what the backward GEMM multiplies by
+ * (MDT_EPI_MULAUX).  h may be pre; u may be NULL (forward without a tape).  fp32 arithmetic, one rounding per store.
+ *   GELU           0.5 x (1 + erf(x / sqrt 2))   (the fp32 formula of the fused epilogue, for comparison with it)
+ *   RELU           x > 0 ? x : 0, derivative x > 0; a NaN stays a NaN in h
+ *   GELU_ACCURATE  0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3)))   (fairseq gelu_accurate, and its alias gelu_fast)
+ *   TANH           derivative 1 - tanh^2
+ *   LINEAR         h = x s, u = s
+ * 16-byte loads and stores when N, the three row strides (multiples of 4 fp32 / 8 bf16 elements) and the pointers allow it,
+ * else one element per lane; mdt_last_route() says which ran ("act_vec" / "act_scalar"). */
+enum { MDT_ACT_GELU = 0, MDT_ACT_RELU = 1, MDT_ACT_GELU_ACCURATE = 2, MDT_ACT_TANH = 3, MDT_ACT_LINEAR = 4 };
+int mdt_act_fwd(void* stream, int dtype, int kind, int64_t rows, int N, const void* pre, int64_t ld_pre, void* h, int64_t ld_h,
+                void* u, int64_t ld_u, float drop_p, uint64_t drop_seed);
 
 /* Column sums: out[n] (+)= sum_m w[m] * X[m,n]  (bias gradients; w = NULL means 1, otherwise an
  * int32 row weight — token-type embedding gradient).  out is fp32, accumulated with atomics —

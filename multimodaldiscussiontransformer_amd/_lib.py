@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libmdt_hip.so")
 MDT_F32, MDT_BF16 = 0, 1
 EPI_BIAS, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_ACCUM, EPI_ATOMIC, EPI_DROPOUT, EPI_COLSUM = 1, 2, 4, 8, 16, 32, 64, 128
 EPI_AUX_GRAD, EPI_MULAUX, EPI_ASUM = 256, 512, 1024
+ACT_GELU, ACT_RELU, ACT_GELU_ACCURATE, ACT_TANH, ACT_LINEAR = 0, 1, 2, 3, 4
 
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -53,6 +54,7 @@ _SIGS = {
     "mdt_reload_env": ([], None),
     "mdt_dropout": ([_vp, _i, _i64, _i, _vp, _i64, _vp, _i64, _f, C.c_uint64], _i),
     "mdt_dropout_mask": ([_vp, _i64, _f, C.c_uint64, _vp], _i),
+    "mdt_act_fwd": ([_vp, _i, _i, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _f, C.c_uint64], _i),
     "mdt_colsum": ([_vp, _i, _i64, _i64, _vp, _i64, _vp, _vp], _i),
     "mdt_layernorm_fwd": ([_vp, _i, _i64, _i, _vp, _i64, _vp, _vp, _f, _vp, _i64, _vp, _vp], _i),
     "mdt_layernorm_fwd_q8": ([_vp, _i, _i64, _i, _vp, _i64, _vp, _vp, _f, _vp, _i64, _vp, _vp, _vp, _i64, _i, _vp, _vp], _i),

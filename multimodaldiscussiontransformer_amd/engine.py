@@ -357,7 +357,7 @@ def _ln_bwd_dense(tape, dy, x, w, b, mean, rstd, bias_param, p_drop, seed, add=N
 # ------------------------------------------------------------------------------------------
 # ops
 def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre_ln: bool, eps: float,
-                      p_hidden: float = 0.0, p_attn: float = 0.0, p_act: float = 0.0, keep_rows=None) -> Var:
+                      p_hidden: float = 0.0, p_attn: float = 0.0, p_act: float = 0.0, keep_rows=None, act: str = "gelu") -> Var:
     """One encoder block (post-LN: HF BertLayer / Graphormer layer; pre-LN: HF ViTLayer or
     Graphormer with --pre-layernorm).  7 GEMM-class launches + attention + 2 LayerNorms
     forward; the adjoint mirrors it with the residual adds folded into epilogues.  The attention half
@@ -367,7 +367,9 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     ``p_hidden`` on the two dense outputs before their residual adds and ``p_act`` after GELU
     (both in the GEMM epilogue); masks are regenerated in backward from per-site seeds.  The FFN
     saves ``u`` = d h / d pre-activation (GELU' times the activation-dropout scale) rather than
-    the pre-activation itself, so the backward epilogue is a single multiply.
+    the pre-activation itself, so the backward epilogue is a single multiply.  ``act``: the FFN activation, a name of
+    ``ops.ACT_KINDS``.  "gelu" (erf form) is fused into fc1's epilogue; every other kind runs fc1 as a plain bias GEMM and
+    ``ops.act_fwd`` then turns the pre-activation into h (in place) and u — the adjoint is the same for all of them.
 
     ``keep_rows`` (i32[R]): only these token rows of the block's OUTPUT are needed downstream (the last fusion
     layer feeds nothing but bottleneck token 0 and [CLS] of every comment to the graph / the head).  Keys and
@@ -379,6 +381,10 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     kw = dict(spec.kwargs(), drop_p=p_attn, drop_seed=s_attn)
     R = None if keep_rows is None else int(keep_rows.numel())
     f8 = F8.ACTIVE
+    if act not in ops.ACT_KINDS:
+        raise ValueError(f"transformer_block: unknown activation {act!r} (one of {sorted(ops.ACT_KINDS)})")
+    if act != "gelu" and f8 is not None:
+        raise NotImplementedError(f"fp8 GEMMs with the {act} activation: the fused fp8 producer of h is fc1's erf-GELU epilogue")
 
     def gather(src):
         """rows ``keep_rows`` of src (identity when the block keeps everything)"""
@@ -413,6 +419,10 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
 
     def ffn_fwd(src, src8, res):
         """FFN half: fc1 writes h and u (and, 8-bit, the quantised h that fc2 then reads), fc2 adds ``res``"""
+        if act != "gelu":       # fc1 leaves the pre-activation; one more launch makes h (in place) and u of it
+            pre_ = ops.gemm(src, P.fc1_w.data, bias=P.fc1_b.data)
+            h_, u_ = ops.act_fwd(pre_, act, drop_p=p_act, drop_seed=s_act, out=pre_, want_u=not tape.inference)
+            return u_, h_, ops.gemm(h_, P.fc2_w.data, bias=P.fc2_b.data, residual=res, drop_p=p_hidden, drop_seed=s_f2)
         u_ = torch.empty(src.shape[0], P.fc1_w.shape[0], dtype=src.dtype, device=src.device)
         h_, h8 = linear(f8, src, P.fc1_w, "fc1", x8=src8, q8_site=("fc2", id(P.fc2_w)), bias=P.fc1_b.data, aux=u_,
                         epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD, drop_p=p_act, drop_seed=s_act)

@@ -66,7 +66,8 @@ class GraphormerModel(FairseqEncoderModel):
         parser.add_argument("--max-positions", type=int, help="number of positional embeddings to learn")
         parser.add_argument("--apply-graphormer-init", action="store_true",
                             help="use custom param initialization for Graphormer")
-        parser.add_argument("--activation-fn", choices=["relu", "gelu"], help="activation function to use")
+        parser.add_argument("--activation-fn", choices=["relu", "gelu", "gelu_fast", "gelu_accurate", "tanh", "linear"],
+                            help="activation function to use")
         parser.add_argument("--encoder-normalize-before", action="store_true",
                             help="apply layernorm before each encoder block")
         parser.add_argument("--pre-layernorm", action="store_true",
@@ -132,6 +133,10 @@ class GraphormerModel(FairseqEncoderModel):
         scaling) for the encoder blocks' big GEMMs.  ``sites``: a preset of fp8.PRESETS ("all" — the default —, "fast4",
         "grads") or a comma list of site names (fp8.py says which GEMMs and what each choice costs in accuracy)."""
         from .. import fp8
+        act = getattr(self.args, "activation_fn", "gelu")
+        if on and act != "gelu":
+            raise NotImplementedError(f"enable_fp8 with --activation-fn {act}: the fp8 path quantises h inside fc1's fused gelu "
+                                      "epilogue, which the other activations do not go through")
         fp8.ACTIVE = fp8.Fp8State(next(self.parameters()).device, sites=sites) if on else None
         return fp8.ACTIVE
 

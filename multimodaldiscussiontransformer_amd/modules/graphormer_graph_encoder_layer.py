@@ -1,8 +1,9 @@
 """Drop-in for mDT/src/modules/graphormer_graph_encoder_layer.py
 (``GraphormerGraphEncoderLayer``, ``GraphEncoderStack``): one Graphormer block over the
 graph tokens of each discussion tree, post-LN by default (pre-LN with ``pre_layernorm``),
-LayerNorm eps 1e-5, erf-GELU computed in fp32 — executed as one tape op
-(``engine.transformer_block``).
+LayerNorm eps 1e-5, the FFN activation computed in fp32 — executed as one tape op
+(``engine.transformer_block``).  ``activation_fn`` takes fairseq's names (utils.get_activation_fn): gelu (erf form, fused
+into fc1's epilogue), relu, gelu_accurate / gelu_fast, tanh and linear (a kernel of their own behind a plain fc1).
 """
 from __future__ import annotations
 
@@ -12,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from .. import engine as E
+from ..ops import ACT_KINDS
 from .multihead_attention import MultiheadAttention
 
 
@@ -23,8 +25,9 @@ class GraphormerGraphEncoderLayer(nn.Module):
         super().__init__()
         if init_fn is not None:
             init_fn()
-        if activation_fn != "gelu":
-            raise NotImplementedError("the HIP path implements the gelu activation the reference launches with")
+        if activation_fn not in ACT_KINDS:
+            raise RuntimeError("--activation-fn {} not supported".format(activation_fn))
+        self.activation_fn = activation_fn
         self.embedding_dim = embedding_dim
         self.num_attention_heads = num_attention_heads
         self.attention_dropout = attention_dropout
@@ -61,7 +64,7 @@ class GraphormerGraphEncoderLayer(nn.Module):
         t = self.training
         return E.transformer_block(tape, x, self.block_params(), spec, pre_ln=self.pre_layernorm, eps=1e-5,
                                    p_hidden=self.dropout_p if t else 0.0, p_attn=self.attention_dropout if t else 0.0,
-                                   p_act=self.activation_dropout_p if t else 0.0)
+                                   p_act=self.activation_dropout_p if t else 0.0, act=self.activation_fn)
 
     def forward(self, x: torch.Tensor, self_attn_bias: Optional[torch.Tensor] = None,
                 self_attn_mask: Optional[torch.Tensor] = None, self_attn_padding_mask: Optional[torch.Tensor] = None):
@@ -92,6 +95,7 @@ class GraphEncoderStack(nn.Module):
                  activation_fn: str = "relu", export: bool = False, q_noise: float = 0.0, qn_block_size: int = 8,
                  init_fn: Callable = None, pre_layernorm: bool = False):
         super().__init__()
+        self.activation_fn = activation_fn
         self.layers = nn.ModuleList([
             GraphormerGraphEncoderLayer(embedding_dim, ffn_embedding_dim, num_attention_heads, dropout, attention_dropout,
                                         activation_dropout, activation_fn, export, q_noise, qn_block_size, init_fn,

@@ -13,13 +13,14 @@ import torch
 from . import _lib as L
 from ._lib import (EPI_ACCUM, EPI_ASUM, EPI_ATOMIC, EPI_AUX_GRAD, EPI_BIAS, EPI_COLSUM, EPI_DGELU, EPI_DROPOUT, EPI_GELU, EPI_MULAUX, EPI_RESIDUAL, check, dt, lib,
                    ptr, stream)
-from ._lib import MdtError
+from ._lib import ACT_GELU, ACT_GELU_ACCURATE, ACT_LINEAR, ACT_RELU, ACT_TANH, MdtError
 
 __all__ = [
     "bert_embed_rows",
     "gemm", "colsum", "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "attention_mean_probs", "graph_attn_bias",
     "row_axpby", "row_scatter_add", "bert_embed_sum", "bert_embed_ln_rows", "vit_patchify", "vit_assemble", "vit_patch_embed", "graph_node_feature",
     "tanh_fwd", "tanh_bwd", "node_ce", "contrastive_loss", "fp8_quantize", "fp8_scale_update", "gemm_fp8", "cast", "transpose2d", "dropout", "dropout_mask",
+    "act_fwd", "ACT_KINDS", "ACT_GELU", "ACT_RELU", "ACT_GELU_ACCURATE", "ACT_TANH", "ACT_LINEAR",
     "EPI_BIAS", "EPI_GELU", "EPI_RESIDUAL", "EPI_DGELU", "EPI_ACCUM", "EPI_ATOMIC", "EPI_DROPOUT", "EPI_AUX_GRAD", "EPI_MULAUX", "EPI_ASUM",
 ]
 
@@ -452,6 +453,27 @@ def dropout(x, p, seed, out=None):
     check(lib.mdt_dropout(stream(), dt(x), x.shape[0], x.shape[1], ptr(x), _2d(x), ptr(out), _2d(out), float(p), int(seed)),
           "mdt_dropout")
     return out
+
+
+# fairseq utils.get_activation_fn names (gelu_fast is its deprecated alias of gelu_accurate) -> MDT_ACT_*
+ACT_KINDS = {"gelu": ACT_GELU, "relu": ACT_RELU, "gelu_accurate": ACT_GELU_ACCURATE, "gelu_fast": ACT_GELU_ACCURATE,
+             "tanh": ACT_TANH, "linear": ACT_LINEAR}
+
+
+def act_fwd(pre, kind, *, drop_p=0.0, drop_seed=0, want_u=True, out=None, u=None):
+    """(h, u) = (act(pre) * s, act'(pre) * s), s the dropout scale of counter row*N + col of site ``drop_seed`` (1 when
+    ``drop_p`` is 0); ``kind``: a name of ACT_KINDS or an ACT_* value.  ``out`` may be ``pre`` (in place); ``u``: the caller's buffer for u (any row
+    stride), else one is allocated when ``want_u`` and None is returned otherwise."""
+    k = ACT_KINDS[kind] if isinstance(kind, str) else int(kind)
+    if out is None:
+        out = torch.empty_like(pre)
+    assert out.dtype == pre.dtype and out.shape == pre.shape
+    if u is None and want_u:
+        u = torch.empty(pre.shape, dtype=pre.dtype, device=pre.device)
+    assert u is None or (u.dtype == pre.dtype and u.shape == pre.shape)
+    check(lib.mdt_act_fwd(stream(), dt(pre), k, pre.shape[0], pre.shape[1], ptr(pre), _2d(pre), ptr(out), _2d(out), ptr(u),
+                          _2d(u) if u is not None else 0, float(drop_p), int(drop_seed)), "mdt_act_fwd")
+    return out, u
 
 
 def dropout_mask(n, p, seed, device="cuda"):
