@@ -6,6 +6,9 @@ use; and against the head_dim 64 kernels themselves on zero-padded heads.
 A 16-wide head is half of the K = 32 contraction step of v_mfma_f32_16x16x32_bf16: the upper half is fed zeros, and the 16
 columns behind a head belong to the NEXT head (or the k block, or the next row).  Every case therefore has H >= 3 heads
 with independent random data per head: a fragment that strayed into its neighbour would show in out, lse and gradients.
+
+The strict gate for attention is tests/test_attention_routes_gpu.py: every kernel and route against the fp64 reference of
+tests/attention_reference.py with a derived bound per element; the assert_close gates here are wide enough for a skipped key.
 """
 import math
 
