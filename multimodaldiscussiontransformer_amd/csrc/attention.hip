@@ -120,6 +120,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mdt_attn_fwd_args& a = P.f;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the item's setup, written out (attn_item, attention_common.hpp, says why)
   const int h = blockIdx.x, seq = blockIdx.y;
   const int SL = a.S, D = a.H * HD;                      // SL: lse / dropout-counter geometry
   const int S = a.seq_offsets ? a.seq_offsets[seq + 1] - a.seq_offsets[seq] : a.S;   // this sequence's length
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams P) {
   const int sld = scratch_ld<T>(s_pad32);
   const Src<T> srcQ{qkv, tld, S};
   const Src<T> srcP{scratch, sld, 16};
-  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};   // written out: see bias_ctx
 
   float colb[NT];
 #pragma unroll
@@ -256,6 +257,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mdt_attn_fwd_args& a = P.f;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the item's setup, written out (attn_item, attention_common.hpp, says why)
   const int h = blockIdx.x, seq = blockIdx.y;
   const int SL = a.S, D = a.H * HD;                      // SL: lse / dropout-counter geometry
   const int S = a.seq_offsets ? a.seq_offsets[seq + 1] - a.seq_offsets[seq] : a.S;   // this sequence's length
@@ -272,7 +274,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
   float* s_delta = (float*)smem;
   float* s_lse = s_delta + s_pad32;
   float* s_hist = s_lse + s_pad32;
-  const int nhist = STRUCT ? ((a.num_spatial + 1 + 3) & ~3) : 0;
+  const int nhist = STRUCT ? attn_hist_size(a.num_spatial) : 0;
   char* after = (char*)(s_hist + nhist);
   bf16_t* img0 = (bf16_t*)after;
   bf16_t* img1 = img0 + (BF ? s_pad32 * IMG_LD<HD> : 0);
@@ -303,7 +305,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
   }
   __syncthreads();
 
-  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+  const BiasCtx bc = bias_ctx(a, seq, h, S);
   const int drop_bh = seq * a.H + h;   // counters: attention_common.hpp
   const Src<T> gQ{qkv, tld, S};
   const Src<T> gDO{dout, dld, S};
@@ -363,19 +365,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
           const float ds = sc[t][r] * (dp[t][r] - del[r]);
           const int q = q0 + (lane >> 4) * 4 + r;
           scratch[((lane >> 4) * 4 + r) * sld + key] = from_f32<T>(ds);
-          if (q < S && key < S) {
-            if (P.d_dense_bias) P.d_dense_bias[(((int64_t)seq * a.H + h) * S + q) * S + key] = ds;
-            if constexpr (STRUCT) {
-              if (P.d_sp_table && ds != 0.f) {
-                if (q >= 1 && key >= 1) {
-                  const int idx = a.spatial_pos[((int64_t)seq * (S - 1) + (q - 1)) * (S - 1) + (key - 1)];
-                  if (idx != 0) atomicAdd(s_hist + idx, ds);  // nn.Embedding(padding_idx=0): row 0 gets no gradient
-                } else {
-                  atomicAdd(s_hist + a.num_spatial, ds);
-                }
-              }
-            }
-          }
+          if (q < S && key < S) attn_bias_grad_add<STRUCT>(P, s_hist, seq, h, S, q, key, ds);
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -409,17 +399,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnParams P) {
     srcQ = gQ;
     srcDO = gDO;
   }
-  if constexpr (STRUCT) {
-    if (P.d_sp_table) {
-      for (int i = tid; i <= a.num_spatial; i += 256) {
-        const float v = s_hist[i];
-        if (v != 0.f) {
-          if (i < a.num_spatial) atomicAdd(P.d_sp_table + (int64_t)i * a.H + h, v);
-          else if (P.d_virt) atomicAdd(P.d_virt + h, v);
-        }
-      }
-    }
-  }
+  if constexpr (STRUCT) attn_bias_grad_flush(P, s_hist, h, tid, 256);
   // ------------------------------------------------------------------ pass B
   {
     const Src<T> gK{qkv + D, tld, S};
@@ -542,7 +522,7 @@ __global__ __launch_bounds__(256) void attn_mean_probs_kernel(mdt_attn_fwd_args 
     const T* krow = (const T*)a.qkv + ((int64_t)seq * a.seq_stride + (int64_t)key * a.pos_stride) * a.ld_qkv + (int64_t)H * hd;
     float acc = 0.f;
     for (int h = 0; h < H; ++h) {
-      BiasCtx bc{seq, h, S, H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+      const BiasCtx bc = bias_ctx(a, seq, h, S);
       float v = key_only_bias<T>(bc, key);
       if (v == 0.f) {
         float dot = 0.f;
@@ -571,7 +551,7 @@ static int launch_bwd(hipStream_t st, const AttnParams& p) {
   constexpr int s_pad32 = (NT * 16 + 31) & ~31;
   constexpr bool BF = !std::is_same<T, float>::value;
   const int sld = s_pad32 + (BF ? 8 : 1);
-  const int nhist = STRUCT ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
+  const int nhist = STRUCT ? attn_hist_size(p.f.num_spatial) : 0;
   const size_t lds = (size_t)(2 * s_pad32 + nhist) * 4 + (size_t)4 * 16 * sld * sizeof(T) +
                (BF ? (size_t)2 * s_pad32 * IMG_LD<HD> * 2 : 0);
   if (lds > 160 * 1024) { set_error("attention_bwd (v1): S=%d with head_dim %d needs %zu bytes of LDS", p.f.S, HD, lds); return MDT_ERR_UNSUPPORTED; }
@@ -719,7 +699,7 @@ __global__ __launch_bounds__(256) void attn_head_weights_kernel(mdt_attn_fwd_arg
     const int key = (int)(i % S), q = (int)((i / S) % S), h = (int)((i / ((int64_t)S * S)) % H), seq = (int)(i / ((int64_t)S * S * H));
     const T* qrow = (const T*)a.qkv + ((int64_t)seq * a.seq_stride + (int64_t)q * a.pos_stride) * a.ld_qkv + h * hd;
     const T* krow = (const T*)a.qkv + ((int64_t)seq * a.seq_stride + (int64_t)key * a.pos_stride) * a.ld_qkv + (int64_t)H * hd + h * hd;
-    BiasCtx bc{seq, h, S, H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+    const BiasCtx bc = bias_ctx(a, seq, h, S);
     float v = key_only_bias<T>(bc, key);
     if (v == 0.f) {
       float dot = 0.f;

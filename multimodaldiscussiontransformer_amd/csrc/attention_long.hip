@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void attn_long_fwd_kernel(AttnParams P) {
   const int qc = qok ? q : S - 1;
   const int64_t row0 = (int64_t)seq * a.seq_stride, tld = a.pos_stride * a.ld_qkv;
   const T* qkv = (const T*)a.qkv + row0 * a.ld_qkv + h * HD;
-  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+  const BiasCtx bc = bias_ctx(a, seq, h, S);
   float qv[DL], acc[DL];
 #pragma unroll
   for (int d = 0; d < DL; ++d) { qv[d] = to_f32(qkv[(int64_t)qc * tld + c0 + d]) * a.scale; acc[d] = 0.f; }
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(64) void attn_long_dq_kernel(AttnParams P) {
   const T* qkv = (const T*)a.qkv + row0 * a.ld_qkv + h * HD;
   const T* dorow = (const T*)P.dout + (row0 + (int64_t)qc * a.pos_stride) * P.ld_dout + h * HD + c0;
   const T* orow = (const T*)a.out + (row0 + (int64_t)qc * a.pos_stride) * a.ld_out + h * HD + c0;
-  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+  const BiasCtx bc = bias_ctx(a, seq, h, S);
   float qv[DL], dov[DL], dq[DL];
   float delta = 0.f;
 #pragma unroll
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(64) void attn_long_dkv_kernel(AttnParams P) {
   const T* dout = (const T*)P.dout + row0 * P.ld_dout + h * HD;
   const T* outp = (const T*)a.out + row0 * a.ld_out + h * HD;
   const int64_t dld = a.pos_stride * P.ld_dout, old_ = a.pos_stride * a.ld_out;
-  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+  const BiasCtx bc = bias_ctx(a, seq, h, S);
   float kv[DL], vv[DL], dk[DL], dv[DL];
 #pragma unroll
   for (int d = 0; d < DL; ++d) {

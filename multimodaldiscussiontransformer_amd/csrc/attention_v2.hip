@@ -20,6 +20,8 @@
 // and the two-pass backward kernels (v2, v3) take all four — a 16-wide head is half a K = 32 contraction step (v2_ks)
 // and one 16-row output tile of the transposed products, the wide ones are three / four steps and six / eight tiles; the
 // one-pass backward kernels (v4, v4x, v5) are written for 64.  32 would need a launch line only (v2_ld / v2_ks cover it); it is not instantiated.
+#include <type_traits>
+
 #include "attention_common.hpp"
 
 namespace mdt {
@@ -176,6 +178,39 @@ __device__ __forceinline__ Row32 rows4_exchange(const f32x4 (&x)[4], float scale
   r.b = __builtin_bit_cast(bf16x8, uint4{lo[2], hi[2], lo[3], hi[3]});
   return r;
 }
+// both stores of a row's 64 columns (`row`: the first of them)
+__device__ __forceinline__ void rows4_store(bf16_t* row, const Row32& v, int g) {
+  *(bf16x8*)(row + rows4_off(g)) = v.a;
+  *(bf16x8*)(row + rows4_off(g) + 32) = v.b;
+}
+// One 16-column accumulator tile on its own: lane (g, c) holds columns 4 g ... + 3 of row c (`p`: that place) — the four lanes of
+// a row write 32 contiguous bytes.  rows4_store / row_piece serve every backward kernel; the forward keeps its three-way store
+// written out (one general form costs the 16-wide instantiations SGPRs or the 8-wave wide ones 2 - 4 VGPRs, whichever way the
+// row's address is formed).
+__device__ __forceinline__ void row_piece(bf16_t* p, const f32x4& x, float scale) {
+  *(bf16x4*)p = bf16x4{(bf16_t)(x[0] * scale), (bf16_t)(x[1] * scale), (bf16_t)(x[2] * scale), (bf16_t)(x[3] * scale)};
+}
+
+// P and dS of one accumulator tile with keys on lanes (the lane's key `key`, queries qb .. qb + 3), in the exp2 domain: on entry
+// sc holds S and dp holds dP; on return sc holds the kept P (the operand of dV) and dp holds dS = P (dP - delta) — both without
+// the 1 / (1 - p_drop) factor, which is applied once to the outputs.  l2v: lse * log2(e), +inf for rows without gradient, so
+// every p of such a row is exp2(-inf) = 0; kb: the key's bias, 0 or -inf.  STRUCT: the per-pair bias, for (q, key) inside the sequence.
+template <bool STRUCT>
+__device__ __forceinline__ void v2_p_ds(f32x4& sc, f32x4& dp, float scale2, float kb, const f32x4& l2v, const f32x4& dlv, const bool (&keep)[4],
+                                        const BiasCtx* bc = nullptr, int qb = 0, int key = 0, bool kok = false) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float v = __builtin_fmaf(sc[r], scale2, kb);
+    if constexpr (STRUCT) {
+      const int q = qb + r;
+      if (kok && q < bc->S) v = __builtin_fmaf(pair_bias<bf16_t, true>(*bc, q, key), LOG2E, v);
+    }
+    const float p = __builtin_amdgcn_exp2f(v - l2v[r]);
+    const float dpv = keep[r] ? dp[r] : 0.f;
+    sc[r] = keep[r] ? p : 0.f;
+    dp[r] = p * (dpv - dlv[r]);
+  }
+}
 
 // ---------------------------------------------------------------------------- forward
 // Softmax in the exp2 domain (scores and key bias pre-multiplied by log2 e: v_exp_f32 is exp2), masked keys
@@ -189,6 +224,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mdt_attn_fwd_args& a = P.f;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the item's setup, written out (attn_item, attention_common.hpp, says why)
   const int h = blockIdx.x, seq = a.seq_ids ? a.seq_ids[blockIdx.y] : (int)blockIdx.y;
   const int SL = a.S, D = a.H * HD;                      // SL: lse / dropout-counter geometry
   const int S = a.seq_offsets ? a.seq_offsets[seq + 1] - a.seq_offsets[seq] : a.S;   // this sequence's length
@@ -199,7 +235,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v2_kernel(AttnParams P) {
   bf16_t* imgK = (bf16_t*)smem;
   bf16_t* imgV = imgK + S_PAD * LD;
   float* s_kb = (float*)(imgV + S_PAD * LD);   // key-only bias (0 / -inf), [S_PAD]
-  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};   // written out: see bias_ctx
   // Ragged sequences: key tiles past this sequence's length are staged as zeros, their scores come out of the
   // (unguarded: a guard there costs the compiler 80 registers) MFMA loop as exact zeros and every later
   // per-element stage skips them, so they cost LDS reads and idle MFMA slots but no VALU work.
@@ -367,6 +403,7 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mdt_attn_fwd_args& a = P.f;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the item's setup, written out (attn_item, attention_common.hpp, says why)
   const int h = blockIdx.x, seq = a.seq_ids ? a.seq_ids[blockIdx.y] : (int)blockIdx.y;
   const int SL = a.S, D = a.H * HD;                      // SL: lse / dropout-counter geometry
   const int S = a.seq_offsets ? a.seq_offsets[seq + 1] - a.seq_offsets[seq] : a.S;   // this sequence's length
@@ -381,8 +418,8 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
   float* s_lse = s_kb + S_PAD;
   float* s_delta = s_lse + S_PAD;
   float* s_hist = s_delta + S_PAD;
-  const int nhist = STRUCT ? ((a.num_spatial + 1 + 3) & ~3) : 0;
-  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+  const int nhist = STRUCT ? attn_hist_size(a.num_spatial) : 0;
+  const BiasCtx bc = bias_ctx(a, seq, h, S);
   v2_stage<HD>(img0, qkv + D, tld, S, S_PAD, tid);      // K
   v2_stage<HD>(img1, qkv + 2 * D, tld, S, S_PAD, tid);  // V
   for (int i = tid; i < S_PAD; i += 256) {
@@ -442,19 +479,7 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
         const float ds = sc[t][r] * (dp[t][r] - del);
         sc[t][r] = ds;
         const int key = t * 16 + 4 * g + r;
-        if (qok && key < S) {
-          if (P.d_dense_bias) P.d_dense_bias[(((int64_t)seq * a.H + h) * S + q) * S + key] = ds;
-          if constexpr (STRUCT) {
-            if (P.d_sp_table && ds != 0.f) {
-              if (q >= 1 && key >= 1) {
-                const int idx = a.spatial_pos[((int64_t)seq * (S - 1) + (q - 1)) * (S - 1) + (key - 1)];
-                if (idx != 0) atomicAdd(s_hist + idx, ds);
-              } else {
-                atomicAdd(s_hist + a.num_spatial, ds);
-              }
-            }
-          }
-        }
+        if (qok && key < S) attn_bias_grad_add<STRUCT>(P, s_hist, seq, h, S, q, key, ds);
       }
     f32x4 dq[ND];
 #pragma unroll
@@ -467,27 +492,14 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
       __builtin_amdgcn_sched_barrier(0);
     }
     if (qok) {
-      bf16_t* orow = dqkv + (int64_t)q * gld + 4 * g;
 #pragma unroll
-      for (int d = 0; d < ND; ++d)
-        *(bf16x4*)(orow + d * 16) = bf16x4{(bf16_t)(dq[d][0] * a.scale), (bf16_t)(dq[d][1] * a.scale),
-                                           (bf16_t)(dq[d][2] * a.scale), (bf16_t)(dq[d][3] * a.scale)};
+      for (int d = 0; d < ND; ++d) row_piece(dqkv + (int64_t)q * gld + 4 * g + d * 16, dq[d], a.scale);
     }
   }
   __syncthreads();   // delta complete; K / V images are free
   v2_stage<HD>(img0, qkv, tld, S, S_PAD, tid);    // Q
   v2_stage<HD>(img1, dout, dld, S, S_PAD, tid);   // dO
-  if constexpr (STRUCT) {
-    if (P.d_sp_table) {
-      for (int i = tid; i <= a.num_spatial; i += 256) {
-        const float v = s_hist[i];
-        if (v != 0.f) {
-          if (i < a.num_spatial) atomicAdd(P.d_sp_table + (int64_t)i * a.H + h, v);
-          else if (P.d_virt) atomicAdd(P.d_virt + h, v);
-        }
-      }
-    }
-  }
+  if constexpr (STRUCT) attn_bias_grad_flush(P, s_hist, h, tid, 256);
   __syncthreads();
   // ------------------------------------------------------------------ pass B: keys on lanes
   for (int kt = wave; kt < n_t; kt += 4) {
@@ -552,9 +564,8 @@ __global__ __launch_bounds__(256) void attn_bwd_v2_kernel(AttnParams P) {
       bf16_t* vrow = dqkv + (int64_t)key * gld + 2 * D + 4 * g;
 #pragma unroll
       for (int d = 0; d < ND; ++d) {
-        *(bf16x4*)(krow + d * 16) = bf16x4{(bf16_t)(dk[d][0] * a.scale), (bf16_t)(dk[d][1] * a.scale),
-                                           (bf16_t)(dk[d][2] * a.scale), (bf16_t)(dk[d][3] * a.scale)};
-        *(bf16x4*)(vrow + d * 16) = bf16x4{(bf16_t)dv[d][0], (bf16_t)dv[d][1], (bf16_t)dv[d][2], (bf16_t)dv[d][3]};
+        row_piece(krow + d * 16, dk[d], a.scale);
+        row_piece(vrow + d * 16, dv[d], 1.0f);
       }
     }
   }
@@ -579,24 +590,20 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
   const mdt_attn_fwd_args& a = P.f;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthr = blockDim.x, nw = nthr >> 6;      // 4 waves, or 8 for long sequences in the 128-register build
-  const int h = blockIdx.x, seq = a.seq_ids ? a.seq_ids[blockIdx.y] : (int)blockIdx.y;
-  const int SL = a.S, D = a.H * HD;                      // SL: lse / dropout-counter geometry
-  const int S = a.seq_offsets ? a.seq_offsets[seq + 1] - a.seq_offsets[seq] : a.S;   // this sequence's length
-  const int64_t row0 = a.seq_offsets ? (int64_t)a.seq_offsets[seq] : (int64_t)seq * a.seq_stride;
-  const bf16_t* qkv = (const bf16_t*)a.qkv + row0 * a.ld_qkv + h * HD;
-  const bf16_t* dout = (const bf16_t*)P.dout + row0 * P.ld_dout + h * HD;
-  const bf16_t* outp = (const bf16_t*)a.out + row0 * a.ld_out + h * HD;
-  bf16_t* dqkv = (bf16_t*)P.dqkv + row0 * P.ld_dqkv + h * HD;
-  const int64_t tld = a.pos_stride * a.ld_qkv, dld = a.pos_stride * P.ld_dout, old_ = a.pos_stride * a.ld_out,
-                gld = a.pos_stride * P.ld_dqkv;
+  const int h = blockIdx.x;
+  const AttnItem<bf16_t> it = attn_item<bf16_t, HD>(P, h, blockIdx.y);
+  const int seq = it.seq, S = it.S, SL = it.SL, D = it.D;
+  const bf16_t *qkv = it.qkv, *dout = it.dout, *outp = it.out;
+  bf16_t* dqkv = it.dqkv;
+  const int64_t tld = it.tld, dld = it.dld, old_ = it.old_, gld = it.gld;
   bf16_t* img0 = (bf16_t*)smem;
   bf16_t* img1 = img0 + s_pad * LD;
   float* s_kb = (float*)(img1 + s_pad * LD);
   float* s_lse = s_kb + s_pad;
   float* s_delta = s_lse + s_pad;
   float* s_hist = s_delta + s_pad;
-  const int nhist = STRUCT ? ((a.num_spatial + 1 + 3) & ~3) : 0;
-  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+  const int nhist = STRUCT ? attn_hist_size(a.num_spatial) : 0;
+  const BiasCtx bc = bias_ctx(a, seq, h, S);
   const int s_live = (S + CW - 1) & ~(CW - 1);                    // rows this (possibly ragged) sequence really uses, in 64-key chunks
   if (s_live > s_pad) return;                           // longer than this launch's bound (s_cap)
   // Latency hiding (the waves of this kernel sat in s_waitcnt / s_barrier for half to two thirds of their cycles):
@@ -688,11 +695,7 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
       for (int t = 0; t < CT; ++t) {
         const f32x4 kb = *(const f32x4*)(s_kb + (t0 + t) * 16 + 4 * g);
         bool keep[4] = {true, true, true, true};
-        if constexpr (DROP) {
-          const uint32_t w0 = drop_mix((rp + 8 * (t0 + t)) ^ P.drop.key), w1 = drop_mix((rp + 8 * (t0 + t) + 1) ^ P.drop.key);
-          keep[0] = drop_keep_lo(P.drop, w0); keep[1] = drop_keep_hi(P.drop, w0);
-          keep[2] = drop_keep_lo(P.drop, w1); keep[3] = drop_keep_hi(P.drop, w1);
-        }
+        if constexpr (DROP) attn_keep4_keys(P.drop, rp + 8 * (t0 + t), keep);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v = __builtin_fmaf(sc[t][r], scale2, kb[r]);
@@ -705,18 +708,7 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
           const float ds = p * (dpe - del);           // true dS = ds / (1 - p_drop)
           sc[t][r] = ds;
           if constexpr (STRUCT) {
-            if (qok && key < S) {
-              const float dst = ds * ik;
-              if (P.d_dense_bias) P.d_dense_bias[(((int64_t)seq * a.H + h) * S + q) * S + key] = dst;
-              if (P.d_sp_table && dst != 0.f) {
-                if (q >= 1 && key >= 1) {
-                  const int idx = a.spatial_pos[((int64_t)seq * (S - 1) + (q - 1)) * (S - 1) + (key - 1)];
-                  if (idx != 0) atomicAdd(s_hist + idx, dst);
-                } else {
-                  atomicAdd(s_hist + a.num_spatial, dst);
-                }
-              }
-            }
+            if (qok && key < S) attn_bias_grad_add<true>(P, s_hist, seq, h, S, q, key, ds * ik);
           }
         }
       }
@@ -730,10 +722,8 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
     }
     if (qok) {
       const float os = a.scale * ik;
-      bf16_t* orow = dqkv + (int64_t)q * gld + 4 * g;
 #pragma unroll
-      for (int d = 0; d < ND; ++d)
-        *(bf16x4*)(orow + d * 16) = bf16x4{(bf16_t)(dq[d][0] * os), (bf16_t)(dq[d][1] * os), (bf16_t)(dq[d][2] * os), (bf16_t)(dq[d][3] * os)};
+      for (int d = 0; d < ND; ++d) row_piece(dqkv + (int64_t)q * gld + 4 * g + d * 16, dq[d], os);
     }
   }
   bf16x8 fk_n[v2_ks<HD>], fv_n[v2_ks<HD>];
@@ -747,22 +737,10 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
   __syncthreads();   // K / V images are free
   v2_stage<HD, LD>(img0, qkv, tld, S, s_live, tid, nthr);    // Q
   v2_stage<HD, LD>(img1, dout, dld, S, s_live, tid, nthr);   // dO
-  if constexpr (STRUCT) {
-    if (P.d_sp_table) {
-      for (int i = tid; i <= a.num_spatial; i += nthr) {
-        const float v = s_hist[i];
-        if (v != 0.f) {
-          if (i < a.num_spatial) atomicAdd(P.d_sp_table + (int64_t)i * a.H + h, v);
-          else if (P.d_virt) atomicAdd(P.d_virt + h, v);
-        }
-      }
-    }
-  }
+  if constexpr (STRUCT) attn_bias_grad_flush(P, s_hist, h, tid, nthr);
   __syncthreads();
   // ------------------------------------------------------------------ pass B (keys on lanes)
-  // A lane holds four consecutive QUERIES of one key, so its four dropout decisions sit in four different mixer
-  // words; the neighbouring lane (key ^ 1) needs the same four words (other half), so each lane of the pair
-  // computes two of them and they trade through one DPP quad swap each.
+  // (dropout decisions of a lane's four queries: attn_keep4_queries)
   const int odd = c & 1;
   const uint32_t base_rp = (uint32_t)(drop_bh * SL) * s2h;
   for (int kt = wave; kt < n_t; kt += nw) {
@@ -806,27 +784,8 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
         const f32x4 l2v = *(const f32x4*)(s_lse + qb);
         const f32x4 dlv = *(const f32x4*)(s_delta + qb);
         bool keep[4] = {true, true, true, true};
-        if constexpr (DROP) {
-          const uint32_t ra = kh + (uint32_t)(qb + 2 * odd) * s2h;
-          const uint32_t wa = drop_mix(ra ^ P.drop.key), wb = drop_mix((ra + s2h) ^ P.drop.key);
-          const uint32_t pa = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)wa, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-          const uint32_t pb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)wb, 0xB1, 0xF, 0xF, false);
-          const uint32_t w[4] = {odd ? pa : wa, odd ? pb : wb, odd ? wa : pa, odd ? wb : pb};
-#pragma unroll
-          for (int r = 0; r < 4; ++r) keep[r] = ((w[r] >> (16 * odd)) & 0xFFFFu) >= P.drop.thresh;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float v = __builtin_fmaf(sc[t][r], scale2, kb);
-          if constexpr (STRUCT) {
-            const int q = qb + r;
-            if (kok && q < S) v = __builtin_fmaf(pair_bias<bf16_t, true>(bc, q, key), LOG2E, v);
-          }
-          const float p = __builtin_amdgcn_exp2f(v - l2v[r]);
-          const float dpv = keep[r] ? dp[t][r] : 0.f;
-          sc[t][r] = keep[r] ? p : 0.f;
-          dp[t][r] = p * (dpv - dlv[r]);
-        }
+        if constexpr (DROP) attn_keep4_queries(P.drop, kh, qb, s2h, odd, keep);
+        v2_p_ds<STRUCT>(sc[t], dp[t], scale2, kb, l2v, dlv, keep, &bc, qb, key, kok);
       }
 #pragma unroll
       for (int pi = 0; pi < CT / 2; ++pi) {
@@ -846,8 +805,8 @@ __device__ __forceinline__ void attn_bwd_v3_body(const AttnParams& P, int s_pad)
       bf16_t* vrow = dqkv + (int64_t)key * gld + 2 * D + 4 * g;
 #pragma unroll
       for (int d = 0; d < ND; ++d) {
-        *(bf16x4*)(krow + d * 16) = bf16x4{(bf16_t)(dk[d][0] * os), (bf16_t)(dk[d][1] * os), (bf16_t)(dk[d][2] * os), (bf16_t)(dk[d][3] * os)};
-        *(bf16x4*)(vrow + d * 16) = bf16x4{(bf16_t)(dv[d][0] * ik), (bf16_t)(dv[d][1] * ik), (bf16_t)(dv[d][2] * ik), (bf16_t)(dv[d][3] * ik)};
+        row_piece(krow + d * 16, dk[d], os);
+        row_piece(vrow + d * 16, dv[d], ik);
       }
     }
   }
@@ -893,6 +852,98 @@ __device__ __forceinline__ bf16x8 v2_frag_tr_ld(const bf16_t* img, int ld, int t
   return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
+// ---- pieces the one-pass kernels (v4, v4x, v5) share: one LDS layout, one arithmetic, bit-identical outputs
+// What a thread requests of an item: NCH 16-byte chunks each of Q, dO and O (NCH * nthr >= 8 * the image's rows: host check), its
+// lse value and mask bytes.  No lane masks around the requests: see v2_stage_req.  WITH_O false (v4x): no O, delta starts at
+// zero — phase 1 sums it.  q_rows: the rows the forward computed (q_limit).
+template <int HD, int NCH, bool WITH_O>
+__device__ __forceinline__ void onepass_request(bf16x8 (&cq)[NCH], bf16x8 (&cg)[NCH], bf16x8 (&co)[NCH], float& lv, KeyBytes& kbv, const mdt_attn_fwd_args& a,
+                                                const BiasCtx& bc, const bf16_t* qkv, const bf16_t* dout, const bf16_t* outp, int64_t tld, int64_t dld,
+                                                int64_t old_, int SL, int q_rows, int rows_live, int tid, int nthr) {
+  static_assert(HD == 64, "delta reduction and staging assume 8 chunks per row");
+  const int S = bc.S;
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) {
+    const int e = tid + j * nthr, r = e >> 3, c8 = e & 7;
+    const int rc = r < S ? r : S - 1, ro = r < q_rows ? r : q_rows - 1;
+    cq[j] = *(const bf16x8*)(qkv + rc * tld + c8 * 8);
+    cg[j] = *(const bf16x8*)(dout + rc * dld + c8 * 8);
+    if constexpr (WITH_O) co[j] = *(const bf16x8*)(outp + ro * old_ + c8 * 8);
+    else co[j] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+  }
+  const int ti = tid < rows_live ? tid : 0;
+  lv = a.lse[((int64_t)bc.seq * a.H + bc.h) * SL + (ti < q_rows ? ti : q_rows - 1)];
+  kbv = key_only_bias_req(bc, ti, qkv);
+}
+// ... and what it does with them once they have arrived: Q -> img0; dO -> img1 by the same (row, chunk) walk that forms
+// delta = rowsum(dO * O): the 8 lanes of a row hold its 8 chunks, three shuffles finish the row (rows_live * 8 is a multiple of
+// 64, with v5's 512 threads of 256: whole waves, no divergence); then the key bias and lse * log2(e) of row tid.
+template <int HD, int NCH>
+__device__ __forceinline__ void onepass_stage(bf16_t* img0, bf16_t* img1, float* s_kb, float* s_lse, float* s_delta, const bf16x8 (&cq)[NCH],
+                                              const bf16x8 (&cg)[NCH], const bf16x8 (&co)[NCH], float lv, KeyBytes kbv, const BiasCtx& bc, int q_rows,
+                                              int rows_live, float rik, int tid, int nthr) {
+  static_assert(HD == 64, "delta reduction and staging assume 8 chunks per row");
+  const int S = bc.S;
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) {
+    const int e = tid + j * nthr, r = e >> 3, c8 = e & 7;
+    if (e < rows_live * 8) {
+      const bf16x8 z = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      const bf16x8 gv = r < S ? cg[j] : z;
+      *(bf16x8*)(img0 + r * v2_ld<HD> + c8 * 8) = r < S ? cq[j] : z;
+      *(bf16x8*)(img1 + r * v2_ld<HD> + c8 * 8) = gv;
+      float de = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) de += (float)co[j][k] * (float)gv[k];
+      de += __shfl_xor(de, 1, 64);
+      de += __shfl_xor(de, 2, 64);
+      de += __shfl_xor(de, 4, 64);
+      if (c8 == 0) s_delta[r] = r < q_rows ? de * rik : 0.f;
+    }
+  }
+  if (tid < rows_live) {
+    s_kb[tid] = key_only_bias_of(bc, tid, kbv);
+    s_lse[tid] = (tid >= q_rows || lv == -INFINITY) ? INFINITY : lv * LOG2E;
+  }
+}
+// dS^T[key][q] of a pair of query tiles: the lane's four queries of either tile are contiguous — one 8-byte write per tile
+__device__ __forceinline__ void onepass_put_ds(bf16_t* ds, const bf16x8& fs, bool second) {
+  *(bf16x4*)ds = bf16x4{fs[0], fs[1], fs[2], fs[3]};
+  if (second) *(bf16x4*)(ds + 16) = bf16x4{fs[4], fs[5], fs[6], fs[7]};
+}
+// K goes where Q was — from the registers that already hold it: the K fragments of the waves ARE the rows of K (lane
+// (g, c) of the owner of key tile kt holds chunks g and 4 + g of row 16 kt + c), so K is read from memory once per
+// item, not twice, and no load stands between the two phases.  Rows past S inside a tile hold a copy of the last row
+// (v2_frag_glb clamps) and meet dS^T rows that are exact zeros; the odd pair partner past n_t keeps Q's zero rows.
+template <int HD>
+__device__ __forceinline__ void onepass_put_k(bf16_t* img0, const bf16x8 (&fk)[v2_ks<HD>], int kt, int lane) {
+#pragma unroll
+  for (int ks = 0; ks < v2_ks<HD>; ++ks) *(bf16x8*)(img0 + (kt * 16 + (lane & 15)) * v2_ld<HD> + ks * 32 + 8 * (lane >> 4)) = fk[ks];
+}
+// phase 2 (queries on lanes, wave `wave` of nw owns query tiles wave, wave + nw, ...): dQ^T = K^T dS^T with K staged where Q was.
+// Site: v5 only.  attn_bwd_v4_body keeps the same loop written out: through this function attn_bwd_v4x_kernel<64, DROP> takes 126
+// VGPRs instead of 120.
+template <int HD>
+__device__ __forceinline__ void onepass_phase2(const bf16_t* img0, const bf16_t* dsT, int ldq, bf16_t* dqkv, int64_t gld, int S, int n_t, int n_tq,
+                                               int wave, int nw, int lane, float scale) {
+  constexpr int ND = HD / 16;
+  static_assert(ND == 4, "rows4_exchange: 64-column rows");
+  const int n_pair_k = (n_t + 1) >> 1;
+  for (int qt = wave; qt < n_tq; qt += nw) {
+    const int q = qt * 16 + (lane & 15);
+    f32x4 dq[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) dq[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int pk = 0; pk < n_pair_k; ++pk) {
+      const bf16x8 fs = v2_frag_tr_ld(dsT, ldq, 2 * pk, qt * 16, lane, 2 * pk + 1 < n_t);
+#pragma unroll
+      for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr<HD>(img0, 2 * pk, d * 16, lane), fs, dq[d]);
+    }
+    const Row32 qv = rows4_exchange(dq, scale);
+    if (q < S) rows4_store(dqkv + (int64_t)q * gld, qv, lane >> 4);
+  }
+}
+
 // EXACT (rows of at most 6 tiles = 96 tokens, launch_v3): delta_i = sum_j P_ij dP_ij is formed HERE, in fp32, from the very P and dP
 // that make dS — not as rowsum(dO o O) from the forward's bf16-rounded output.  The two are equal in exact arithmetic; with O
 // rounded to 2^-9 the second one is off by dO . (O_bf16 - O), the same for every key of a row, which is harmless at the block's
@@ -910,23 +961,19 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
   const mdt_attn_fwd_args& a = P.f;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthr = blockDim.x, nw = nthr >> 6;
-  const int h = blockIdx.x, seq = a.seq_ids ? a.seq_ids[blockIdx.y] : (int)blockIdx.y;
-  const int SL = a.S, D = a.H * HD;
-  const int S = a.seq_offsets ? a.seq_offsets[seq + 1] - a.seq_offsets[seq] : a.S;
-  const int64_t row0 = a.seq_offsets ? (int64_t)a.seq_offsets[seq] : (int64_t)seq * a.seq_stride;
-  const bf16_t* qkv = (const bf16_t*)a.qkv + row0 * a.ld_qkv + h * HD;
-  const bf16_t* dout = (const bf16_t*)P.dout + row0 * P.ld_dout + h * HD;
-  const bf16_t* outp = (const bf16_t*)a.out + row0 * a.ld_out + h * HD;
-  bf16_t* dqkv = (bf16_t*)P.dqkv + row0 * P.ld_dqkv + h * HD;
-  const int64_t tld = a.pos_stride * a.ld_qkv, dld = a.pos_stride * P.ld_dout, old_ = a.pos_stride * a.ld_out,
-                gld = a.pos_stride * P.ld_dqkv;
+  const int h = blockIdx.x;
+  const AttnItem<bf16_t> it = attn_item<bf16_t, HD>(P, h, blockIdx.y);
+  const int seq = it.seq, S = it.S, SL = it.SL, D = it.D;
+  const bf16_t *qkv = it.qkv, *dout = it.dout, *outp = it.out;
+  bf16_t* dqkv = it.dqkv;
+  const int64_t tld = it.tld, dld = it.dld, old_ = it.old_, gld = it.gld;
   bf16_t* img0 = (bf16_t*)smem;                       // Q, then K
   bf16_t* img1 = img0 + rows_img * v2_ld<HD>;              // dO
   float* s_kb = (float*)(img1 + rows_img * v2_ld<HD>);
   float* s_lse = s_kb + rows_img;
   float* s_delta = s_lse + rows_img;                   // EXACT: [8 key tiles][rows_img] partial row sums, one slab per wave
   bf16_t* dsT = (bf16_t*)(s_delta + rows_img * (EXACT ? 8 : 1));   // [16 * tiles][ldq]: dS^T, key-major
-  BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
+  const BiasCtx bc = bias_ctx(a, seq, h, S);
   const int n_t = (S + 15) >> 4;
   const int rows_live = ((n_t + 1) >> 1) * 32;         // this sequence's rows, in pairs of tiles (zero rows past S)
   if (rows_live > rows_img || S <= 0) return;          // longer than this launch's bound (s_cap); empty: nothing to write
@@ -947,44 +994,12 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
     }
   }
   {
-    static_assert(HD == 64, "delta reduction and staging assume 8 chunks per row");
     const int q_rows = (a.q_limit > 0 && ((a.q_limit + 15) & ~15) < S) ? ((a.q_limit + 15) & ~15) : S;   // rows the forward computed
     bf16x8 cq[2], cg[2], co[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {      // no lane masks around the requests: see v2_stage_req
-      const int e = tid + j * nthr, r = e >> 3, c8 = e & 7;
-      const int rc = r < S ? r : S - 1, ro = r < q_rows ? r : q_rows - 1;
-      cq[j] = *(const bf16x8*)(qkv + rc * tld + c8 * 8);
-      cg[j] = *(const bf16x8*)(dout + rc * dld + c8 * 8);
-      if constexpr (!EXACT) co[j] = *(const bf16x8*)(outp + ro * old_ + c8 * 8);
-      else co[j] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};       // delta starts at zero: phase 1 sums it
-    }
-    const int ti = tid < rows_live ? tid : 0;
-    const float lv = a.lse[((int64_t)seq * a.H + h) * SL + (ti < q_rows ? ti : q_rows - 1)];
-    const KeyBytes kbv = key_only_bias_req(bc, ti, qkv);
-    // Q -> img0; dO -> img1 by the same (row, chunk) walk that forms delta = rowsum(dO * O): the 8 lanes of a row hold
-    // its 8 chunks, three shuffles finish the row (rows_live * 8 is a multiple of 64: whole waves, no divergence)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int e = tid + j * nthr, r = e >> 3, c8 = e & 7;
-      if (e < rows_live * 8) {
-        const bf16x8 z = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        const bf16x8 gv = r < S ? cg[j] : z;
-        *(bf16x8*)(img0 + r * v2_ld<HD> + c8 * 8) = r < S ? cq[j] : z;
-        *(bf16x8*)(img1 + r * v2_ld<HD> + c8 * 8) = gv;
-        float de = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) de += (float)co[j][k] * (float)gv[k];
-        de += __shfl_xor(de, 1, 64);
-        de += __shfl_xor(de, 2, 64);
-        de += __shfl_xor(de, 4, 64);
-        if (c8 == 0) s_delta[r] = r < q_rows ? de * rik : 0.f;
-      }
-    }
-    if (tid < rows_live) {
-      s_kb[tid] = key_only_bias_of(bc, tid, kbv);
-      s_lse[tid] = (tid >= q_rows || lv == -INFINITY) ? INFINITY : lv * LOG2E;
-    }
+    float lv;
+    KeyBytes kbv;
+    onepass_request<HD, 2, !EXACT>(cq, cg, co, lv, kbv, a, bc, qkv, dout, outp, tld, dld, old_, SL, q_rows, rows_live, tid, nthr);
+    onepass_stage<HD, 2>(img0, img1, s_kb, s_lse, s_delta, cq, cg, co, lv, kbv, bc, q_rows, rows_live, rik, tid, nthr);
   }
   __syncthreads();
   const int drop_bh = seq * a.H + h;
@@ -1029,16 +1044,10 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
             const f32x4 l2v = *(const f32x4*)(s_lse + qb);
             bool keep[4] = {true, true, true, true};
             if constexpr (DROP) {
-              const uint32_t ra = kh + (uint32_t)(qb + 2 * odd) * s2h;
-              const uint32_t wa = drop_mix(ra ^ P.drop.key), wb = drop_mix((ra + s2h) ^ P.drop.key);
-              const uint32_t pa = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)wa, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-              const uint32_t pb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)wb, 0xB1, 0xF, 0xF, false);
-              const uint32_t w[4] = {odd ? pa : wa, odd ? pb : wb, odd ? wa : pa, odd ? wb : pb};
+              attn_keep4_queries(P.drop, kh, qb, s2h, odd, keep);   // the four booleans, folded into this pair's mask
 #pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                keep[r] = ((w[r] >> (16 * odd)) & 0xFFFFu) >= P.drop.thresh;
+              for (int r = 0; r < 4; ++r)
                 if (!keep[r]) keepA[pr] &= ~(1u << (4 * t + r));
-              }
             }
             float x[4];
 #pragma unroll
@@ -1076,8 +1085,7 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
           }
           const bf16x8 fp = v2_pack(sc[0], sc[1]);
           const bf16x8 fs = v2_pack(dp[0], dp[1]);
-          *(bf16x4*)(ds_row + t0 * 16) = bf16x4{fs[0], fs[1], fs[2], fs[3]};
-          if (t0 + 1 < n_tq) *(bf16x4*)(ds_row + t0 * 16 + 16) = bf16x4{fs[4], fs[5], fs[6], fs[7]};
+          onepass_put_ds(ds_row + t0 * 16, fs, t0 + 1 < n_tq);
 #pragma unroll
           for (int d = 0; d < ND; ++d) {
             dv[d] = mfma_bf16(v2_frag_tr<HD>(img1, t0, d * 16, lane), fp, dv[d]);
@@ -1105,29 +1113,12 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
         const f32x4 l2v = *(const f32x4*)(s_lse + qb);
         const f32x4 dlv = *(const f32x4*)(s_delta + qb);
         bool keep[4] = {true, true, true, true};
-        if constexpr (DROP) {
-          const uint32_t ra = kh + (uint32_t)(qb + 2 * odd) * s2h;
-          const uint32_t wa = drop_mix(ra ^ P.drop.key), wb = drop_mix((ra + s2h) ^ P.drop.key);
-          const uint32_t pa = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)wa, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-          const uint32_t pb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)wb, 0xB1, 0xF, 0xF, false);
-          const uint32_t w[4] = {odd ? pa : wa, odd ? pb : wb, odd ? wa : pa, odd ? wb : pb};
-#pragma unroll
-          for (int r = 0; r < 4; ++r) keep[r] = ((w[r] >> (16 * odd)) & 0xFFFFu) >= P.drop.thresh;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = __builtin_fmaf(sc[t][r], scale2, kb);
-          const float p = __builtin_amdgcn_exp2f(v - l2v[r]);
-          const float dpv = keep[r] ? dp[t][r] : 0.f;
-          sc[t][r] = keep[r] ? p : 0.f;
-          dp[t][r] = p * (dpv - dlv[r]);
-        }
+        if constexpr (DROP) attn_keep4_queries(P.drop, kh, qb, s2h, odd, keep);
+        v2_p_ds<false>(sc[t], dp[t], scale2, kb, l2v, dlv, keep);
       }
       const bf16x8 fp = v2_pack(sc[0], sc[1]);
       const bf16x8 fs = v2_pack(dp[0], dp[1]);
-      // dS^T[key][q]: the lane's four queries of either tile are contiguous — one 8-byte write per tile
-      *(bf16x4*)(ds_row + t0 * 16) = bf16x4{fs[0], fs[1], fs[2], fs[3]};
-      if (t0 + 1 < n_tq) *(bf16x4*)(ds_row + t0 * 16 + 16) = bf16x4{fs[4], fs[5], fs[6], fs[7]};
+      onepass_put_ds(ds_row + t0 * 16, fs, t0 + 1 < n_tq);
 #pragma unroll
       for (int d = 0; d < ND; ++d) {
         dv[d] = mfma_bf16(v2_frag_tr<HD>(img1, t0, d * 16, lane), fp, dv[d]);
@@ -1138,27 +1129,17 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
     static_assert(ND == 4, "rows4_exchange: 64-column rows");
     const Row32 kv = rows4_exchange(dk, a.scale * ik), vv = rows4_exchange(dv, ik);
     if (kok) {
-      bf16_t* krow = dqkv + (int64_t)key * gld + D + rows4_off(g);
-      bf16_t* vrow = dqkv + (int64_t)key * gld + 2 * D + rows4_off(g);
-      *(bf16x8*)krow = kv.a;
-      *(bf16x8*)(krow + 32) = kv.b;
-      *(bf16x8*)vrow = vv.a;
-      *(bf16x8*)(vrow + 32) = vv.b;
+      rows4_store(dqkv + (int64_t)key * gld + D, kv, g);
+      rows4_store(dqkv + (int64_t)key * gld + 2 * D, vv, g);
     }
   } else if constexpr (EXACT) {
     __syncthreads();                               // the delta barrier between the two sweeps of the waves that own a key tile
   }
-  // K goes where Q was — from the registers that already hold it: the K fragments of the waves ARE the rows of K (lane
-  // (g, c) of the owner of key tile kt holds chunks g and 4 + g of row 16 kt + c), so K is read from memory once per
-  // item, not twice, and no load stands between the two phases.  Rows past S inside a tile hold a copy of the last row
-  // (v2_frag_glb clamps) and meet dS^T rows that are exact zeros; the odd pair partner past n_t keeps Q's zero rows.
   __syncthreads();   // every dS^T tile is in LDS; the Q / dO images are free
-  if (kt < n_t) {
-#pragma unroll
-    for (int ks = 0; ks < v2_ks<HD>; ++ks) *(bf16x8*)(img0 + (key0 + c) * v2_ld<HD> + ks * 32 + 8 * g) = fk[ks];
-  }
+  if (kt < n_t) onepass_put_k<HD>(img0, fk, kt, lane);
   __syncthreads();
   // ------------------------------------------------------------------ phase 2 (queries on lanes): dQ^T = K^T dS^T
+  // (written out: see onepass_phase2)
   for (int qt = wave; qt < n_tq; qt += nw) {
     const int q = qt * 16 + c;
     f32x4 dq[ND];
@@ -1170,11 +1151,7 @@ __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_i
       for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr<HD>(img0, 2 * pk, d * 16, lane), fs, dq[d]);
     }
     const Row32 qv = rows4_exchange(dq, a.scale * ik);
-    if (q < S) {
-      bf16_t* orow = dqkv + (int64_t)q * gld + rows4_off(g);
-      *(bf16x8*)orow = qv.a;
-      *(bf16x8*)(orow + 32) = qv.b;
-    }
+    if (q < S) rows4_store(dqkv + (int64_t)q * gld, qv, g);
   }
 }
 
@@ -1266,29 +1243,12 @@ __device__ __forceinline__ void v5_phase1(const AttnParams& P, const bf16_t* img
         for (int t = 0; t < 2; ++t) {
           const int qb = (t0 + t) * 16 + 4 * g;
           bool keep[4] = {true, true, true, true};
-          if constexpr (DROP) {
-            const uint32_t ra = kh[u] + (uint32_t)(qb + 2 * odd) * s2h;
-            const uint32_t wa = drop_mix(ra ^ P.drop.key), wb = drop_mix((ra + s2h) ^ P.drop.key);
-            const uint32_t pa = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)wa, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-            const uint32_t pb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)wb, 0xB1, 0xF, 0xF, false);
-            const uint32_t w[4] = {odd ? pa : wa, odd ? pb : wb, odd ? wa : pa, odd ? wb : pb};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) keep[r] = ((w[r] >> (16 * odd)) & 0xFFFFu) >= P.drop.thresh;
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float v = __builtin_fmaf(sc[u][t][r], scale2, kb[u]);
-            const float p = __builtin_amdgcn_exp2f(v - l2v[t][r]);
-            const float dpv = keep[r] ? dp[u][t][r] : 0.f;
-            sc[u][t][r] = keep[r] ? p : 0.f;
-            dp[u][t][r] = p * (dpv - dlv[t][r]);
-          }
+          if constexpr (DROP) attn_keep4_queries(P.drop, kh[u], qb, s2h, odd, keep);
+          v2_p_ds<false>(sc[u][t], dp[u][t], scale2, kb[u], l2v[t], dlv[t], keep);
         }
         fp[u] = v2_pack(sc[u][0], sc[u][1]);
         fs[u] = v2_pack(dp[u][0], dp[u][1]);
-        // dS^T[key][q]: the lane's four queries of either tile are contiguous — one 8-byte write per tile
-        *(bf16x4*)(ds_row[u] + t0 * 16) = bf16x4{fs[u][0], fs[u][1], fs[u][2], fs[u][3]};
-        if (t0 + 1 < n_tq) *(bf16x4*)(ds_row[u] + t0 * 16 + 16) = bf16x4{fs[u][4], fs[u][5], fs[u][6], fs[u][7]};
+        onepass_put_ds(ds_row[u] + t0 * 16, fs[u], t0 + 1 < n_tq);
       }
     }
 #pragma unroll
@@ -1306,12 +1266,8 @@ __device__ __forceinline__ void v5_phase1(const AttnParams& P, const bf16_t* img
   for (int u = 0; u < NU; ++u) {
     const Row32 kv = rows4_exchange(dk[u], a.scale * ik), vv = rows4_exchange(dv[u], ik);
     if (key[u] < S) {
-      bf16_t* krow = dqkv + (int64_t)key[u] * gld + D + rows4_off(g);
-      bf16_t* vrow = dqkv + (int64_t)key[u] * gld + 2 * D + rows4_off(g);
-      *(bf16x8*)krow = kv.a;
-      *(bf16x8*)(krow + 32) = kv.b;
-      *(bf16x8*)vrow = vv.a;
-      *(bf16x8*)(vrow + 32) = vv.b;
+      rows4_store(dqkv + (int64_t)key[u] * gld + D, kv, g);
+      rows4_store(dqkv + (int64_t)key[u] * gld + 2 * D, vv, g);
     }
   }
 }
@@ -1334,8 +1290,7 @@ __device__ __forceinline__ int v5_sload(const int* p) {
 
 template <int HD, bool DROP>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_v5_kernel(AttnParams P, int rows_img, int ldq, int n_items) {
-  constexpr int ND = HD / 16, NCH = 4;         // 16-byte chunks per thread and tensor: rows_img * 8 <= 4 * 512 (host check)
-  static_assert(HD == 64, "staging assumes 8 chunks per row");
+  constexpr int NCH = 4;         // 16-byte chunks per thread and tensor: rows_img * 8 <= 4 * 512 (host check)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mdt_attn_fwd_args& a = P.f;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1380,18 +1335,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const bf16_t* qkv = (const bf16_t*)a.qkv + row0 * a.ld_qkv + h * HD;
       const bf16_t* dout = (const bf16_t*)P.dout + row0 * P.ld_dout + h * HD;
       const bf16_t* outp = (const bf16_t*)a.out + row0 * a.ld_out + h * HD;
-#pragma unroll
-      for (int j = 0; j < NCH; ++j) {
-        const int e = tid + j * 512, r = e >> 3, c8 = e & 7;
-        const int rc = r < S ? r : S - 1;
-        cq[j] = *(const bf16x8*)(qkv + rc * tld + c8 * 8);
-        cg[j] = *(const bf16x8*)(dout + rc * dld + c8 * 8);
-        co[j] = *(const bf16x8*)(outp + (r < q_rows ? r : q_rows - 1) * old_ + c8 * 8);
-      }
-      const int ti = tid < rows_live ? tid : 0;
-      lv = a.lse[((int64_t)seq * a.H + h) * SL + (ti < q_rows ? ti : q_rows - 1)];
-      BiasCtx bc{seq, h, S, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
-      kbv = key_only_bias_req(bc, ti, qkv);
+      onepass_request<HD, NCH, true>(cq, cg, co, lv, kbv, a, bias_ctx(a, seq, h, S), qkv, dout, outp, tld, dld, old_, SL, q_rows, rows_live, tid, 512);
     }
   };
   auto request_frags = [&](int tid) {
@@ -1419,28 +1363,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int cS = S, c_nt = n_t, c_rows = rows_live, c_qrows = q_rows, c_seq = seq, c_h = h;
     const int64_t c_row0 = row0;
     const int tid1 = v5_opaque(tid);
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      const int e = tid1 + j * 512, r = e >> 3, c8 = e & 7;
-      if (e < c_rows * 8) {        // whole waves (c_rows * 8 is a multiple of 256)
-        const bf16x8 z = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        const bf16x8 gv = r < cS ? cg[j] : z;
-        *(bf16x8*)(img0 + r * v2_ld<HD> + c8 * 8) = r < cS ? cq[j] : z;
-        *(bf16x8*)(img1 + r * v2_ld<HD> + c8 * 8) = gv;
-        float de = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) de += (float)co[j][k] * (float)gv[k];
-        de += __shfl_xor(de, 1, 64);
-        de += __shfl_xor(de, 2, 64);
-        de += __shfl_xor(de, 4, 64);
-        if (c8 == 0) s_delta[r] = r < c_qrows ? de * rik : 0.f;
-      }
-    }
-    if (tid1 < c_rows) {
-      BiasCtx bc{c_seq, c_h, cS, a.H, a.key_mask, a.key_pad, a.dense_bias, a.attn_bias, a.spatial_pos, a.sp_table, a.virt};
-      s_kb[tid1] = key_only_bias_of(bc, tid1, kbv);
-      s_lse[tid1] = (tid1 >= c_qrows || lv == -INFINITY) ? INFINITY : lv * LOG2E;
-    }
+    onepass_stage<HD, NCH>(img0, img1, s_kb, s_lse, s_delta, cq, cg, co, lv, kbv, bias_ctx(a, c_seq, c_h, cS), c_qrows, c_rows, rik, tid1, 512);
     // the K / V fragments count as arrived HERE on every path: phase 1 runs under a wave-uniform branch, and where the paths
     // meet again the compiler's wait bookkeeping keeps the worst case — it then waited for this item's dK / dV stores before
     // writing K to LDS
@@ -1459,42 +1382,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (wave + 8 < c_nt) v5_phase1<HD, DROP, 2>(P, img0, img1, s_kb, s_lse, s_delta, dsT, ldq, wk, wv, wave, lane1, cS, SL, c_seq * a.H + c_h, n_tq, dqkv, gld, D, ik);
     else if (wave < c_nt) v5_phase1<HD, DROP, 1>(P, img0, img1, s_kb, s_lse, s_delta, dsT, ldq, wk, wv, wave, lane1, cS, SL, c_seq * a.H + c_h, n_tq, dqkv, gld, D, ik);
     __syncthreads();   // every dS^T tile is in LDS; the Q / dO images are free
-    // K goes where Q was, from the fragment registers (see v4)
+    // K goes where Q was, from the fragment registers (see onepass_put_k)
     const int tid2 = v5_opaque(tid), lane2 = tid2 & 63;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
-      if (wave + 8 * u < c_nt) {
-#pragma unroll
-        for (int ks = 0; ks < v2_ks<HD>; ++ks) *(bf16x8*)(img0 + ((wave + 8 * u) * 16 + (lane2 & 15)) * v2_ld<HD> + ks * 32 + 8 * (lane2 >> 4)) = wk[u][ks];
-      }
+      if (wave + 8 * u < c_nt) onepass_put_k<HD>(img0, wk[u], wave + 8 * u, lane2);
     // ---- the next item's K / V fragments, into the registers just written out: they arrive under phase 2
     if (more) request_frags(tid2);
     __syncthreads();
     // ---- phase 2 (queries on lanes): dQ^T = K^T dS^T
-    const int n_pair_k = (c_nt + 1) >> 1;
-    const int lane3 = v5_opaque(lane);
-    for (int qt = wave; qt < n_tq; qt += 8) {
-      const int q = qt * 16 + (lane3 & 15);
-      f32x4 dq[ND];
-#pragma unroll
-      for (int d = 0; d < ND; ++d) dq[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int pk = 0; pk < n_pair_k; ++pk) {
-        const bf16x8 fs = v2_frag_tr_ld(dsT, ldq, 2 * pk, qt * 16, lane3, 2 * pk + 1 < c_nt);
-#pragma unroll
-        for (int d = 0; d < ND; ++d) dq[d] = mfma_bf16(v2_frag_tr<HD>(img0, 2 * pk, d * 16, lane3), fs, dq[d]);
-      }
-      const Row32 qv = rows4_exchange(dq, a.scale * ik);
-      if (q < cS) {
-        bf16_t* orow = dqkv + (int64_t)q * gld + rows4_off(lane3 >> 4);
-        *(bf16x8*)orow = qv.a;
-        *(bf16x8*)(orow + 32) = qv.b;
-      }
-    }
+    onepass_phase2<HD>(img0, dsT, ldq, dqkv, gld, cS, c_nt, n_tq, wave, 8, v5_opaque(lane), a.scale * ik);
     if (!more) break;
     it = nxt;
     __syncthreads();   // the images and dS^T are free for the next item
   }
 }
+
+static int launch_cap(const mdt_attn_fwd_args& a) { return a.s_cap > 0 ? a.s_cap : a.S; }   // longest sequence of this launch
 
 // LDS of the one-pass kernel for rows of up to S keys; 0 = does not fit
 static size_t v4_lds_bytes(int S, int* rows_img, int* ldq) {
@@ -1527,7 +1431,7 @@ AttnRoute attn_bwd_route(const AttnParams& p) {
   const mdt_attn_fwd_args& a = p.f;
   const bool st_bias = a.attn_bias != nullptr, binned = a.seq_ids != nullptr || a.s_cap > 0;
   const bool dense_only = (a.dense_bias != nullptr || p.d_dense_bias != nullptr) && !st_bias;
-  const int cap = a.s_cap > 0 ? a.s_cap : a.S;                   // longest sequence of this launch
+  const int cap = launch_cap(a);
   const int n_t = (cap + 15) / 16;
   int rows_img = 0, ldq = 0;
   const bool one_pass = a.hd == 64 && !st_bias && !dense_only && v4_lds_bytes(cap, &rows_img, &ldq) != 0 && n_t <= 16;
@@ -1554,12 +1458,34 @@ AttnRoute attn_bwd_route(const AttnParams& p) {
   return forced != AttnRoute::none && ok(forced) ? forced : r;
 }
 
+// (structural bias, dropout) of a launch and its head width as template arguments (with_layout / with_epilogue in gemm.hip)
+template <typename F>
+static int with_flags(const AttnParams& p, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  const bool s = p.f.attn_bias != nullptr, d = p.f.drop_p > 0.f;
+  if (s && d) return f(T{}, T{});
+  if (s) return f(T{}, N{});
+  if (d) return f(N{}, T{});
+  return f(N{}, N{});
+}
+// head_dim: 16, 64, 96 or 128 (dispatch() in attention.hip refuses every other width before it gets here)
+template <typename F>
+static int with_head_dim(int hd, F&& f) {
+  switch (hd) {
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 96: return f(std::integral_constant<int, 96>{});
+    case 128: return f(std::integral_constant<int, 128>{});
+    default: return f(std::integral_constant<int, 64>{});
+  }
+}
+
 // the one-pass kernels (64-wide heads, no structural bias): r is v4 | v4x | v5
 template <bool DROP>
 static int launch_one_pass(hipStream_t st, const AttnParams& p, AttnRoute r) {
   // In-call A/B with dropout 0.1 (tools/attn_onepass_ab.py): ViT rows (512 x 201) 755 -> 525 us, padded BERT rows
   // (2048 x 104) 993 -> 792 us, ragged BERT rows (8-100 tokens) 592 -> 493 us; gradients equal to bf16 rounding of delta.
-  const int cap = p.f.s_cap > 0 ? p.f.s_cap : p.f.S;          // longest sequence of this launch
+  const int cap = launch_cap(p.f);
   const dim3 grid(p.f.H, p.f.nseq);
   int rows_img = 0, ldq = 0;
   const size_t lds4 = v4_lds_bytes(cap, &rows_img, &ldq);
@@ -1580,10 +1506,10 @@ static int launch_v3(hipStream_t st, const AttnParams& p, AttnRoute r) {
   if constexpr (HD == 64 && !STRUCT) {
     if (r != AttnRoute::v3) return launch_one_pass<DROP>(st, p, r);
   }
-  const int cap = p.f.s_cap > 0 ? p.f.s_cap : p.f.S;          // longest sequence of this launch
+  const int cap = launch_cap(p.f);
   const bool tight = HD == 128 && cap > 256;                  // 320 rows of 128-wide heads do not fit: 288 rows, 32-key chunks
   const int s_pad = tight ? (cap + 31) & ~31 : (cap + 63) & ~63;
-  const int nhist = STRUCT ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
+  const int nhist = STRUCT ? attn_hist_size(p.f.num_spatial) : 0;
   const size_t lds = (size_t)2 * s_pad * (tight ? v2_ld<HD, true> : v2_ld<HD>) * 2 + (size_t)3 * s_pad * 4 + (size_t)nhist * 4;
   if (lds > 160 * 1024) { set_error("attention_bwd_v3: S=%d needs %zu bytes of LDS", cap, lds); return MDT_ERR_UNSUPPORTED; }
   const dim3 grid(p.f.H, p.f.nseq);
@@ -1597,29 +1523,16 @@ static int launch_v3(hipStream_t st, const AttnParams& p, AttnRoute r) {
   else return launch_route<attn_bwd_v3_occ4_kernel<HD, DROP>>("v3", grid, s_pad <= 128 ? 256 : 512, lds, st, p, s_pad);
 }
 
-template <int HD>
-static int dispatch_v3(hipStream_t st, const AttnParams& p, AttnRoute r) {
-  const bool s = p.f.attn_bias != nullptr, d = p.f.drop_p > 0.f;
-  if (s && d) return launch_v3<HD, true, true>(st, p, r);
-  if (s) return launch_v3<HD, true, false>(st, p, r);
-  if (d) return launch_v3<HD, false, true>(st, p, r);
-  return launch_v3<HD, false, false>(st, p, r);
-}
-
-// head_dim: 16, 64, 96 or 128 (dispatch() in attention.hip refuses every other width before it gets here)
 int attention_v3_bwd_dispatch(hipStream_t st, const AttnParams& p, AttnRoute r) {
-  switch (p.f.hd) {
-    case 16: return dispatch_v3<16>(st, p, r);
-    case 96: return dispatch_v3<96>(st, p, r);
-    case 128: return dispatch_v3<128>(st, p, r);
-    default: return dispatch_v3<64>(st, p, r);
-  }
+  return with_head_dim(p.f.hd, [&](auto hd) {
+    return with_flags(p, [&](auto s, auto d) { return launch_v3<decltype(hd)::value, decltype(s)::value, decltype(d)::value>(st, p, r); });
+  });
 }
 
 template <int HD, int NT, bool STRUCT, bool DROP, bool BWD>
 static int launch_v2(hipStream_t st, const AttnParams& p) {
   constexpr int S_PAD = ((NT + 1) / 2) * 32;
-  const int nhist = (STRUCT && BWD) ? ((p.f.num_spatial + 1 + 3) & ~3) : 0;
+  const int nhist = (STRUCT && BWD) ? attn_hist_size(p.f.num_spatial) : 0;
   const size_t lds = (size_t)2 * S_PAD * (BWD ? v2_ld<HD> : v2_ld_nt<HD, NT>) * 2 + (size_t)(BWD ? 3 : 1) * S_PAD * 4 + (size_t)nhist * 4 + (BWD ? 0 : 16);   // forward: + the staging's spare chunk
   if constexpr (BWD && NT > 7) {
     // the whole-row backward runs out of registers past 112 keys; attn_bwd_route sends those to the v3 family
@@ -1632,34 +1545,31 @@ static int launch_v2(hipStream_t st, const AttnParams& p) {
   }
 }
 
-template <int HD, bool STRUCT, bool DROP, bool BWD>
-static int dispatch_v2_nt(hipStream_t st, const AttnParams& p) {
-  const int nt = ((p.f.s_cap > 0 ? p.f.s_cap : p.f.S) + 15) / 16;
-#define V2_CASE(N_) if (nt <= N_) return launch_v2<HD, N_, STRUCT, DROP, BWD>(st, p);
-  V2_CASE(2) V2_CASE(4) V2_CASE(5) V2_CASE(7) V2_CASE(9) V2_CASE(13) V2_CASE(17)
-#undef V2_CASE
+// the key-tile rung of a whole-row launch as a template argument: the first that holds the launch's longest sequence
+template <typename F>
+static int with_rung(const AttnParams& p, F&& f) {
+  const int nt = (launch_cap(p.f) + 15) / 16;
+  if (nt <= 2) return f(std::integral_constant<int, 2>{});
+  if (nt <= 4) return f(std::integral_constant<int, 4>{});
+  if (nt <= 5) return f(std::integral_constant<int, 5>{});
+  if (nt <= 7) return f(std::integral_constant<int, 7>{});
+  if (nt <= 9) return f(std::integral_constant<int, 9>{});
+  if (nt <= 13) return f(std::integral_constant<int, 13>{});
+  if (nt <= 17) return f(std::integral_constant<int, 17>{});
   set_error("attention_v2: S=%d exceeds 272", p.f.S);
   return MDT_ERR_UNSUPPORTED;
 }
 
-template <int HD>
-static int dispatch_v2(hipStream_t st, const AttnParams& p, bool bwd) {
-  const bool s = p.f.attn_bias != nullptr, d = p.f.drop_p > 0.f;
-#define V2_GO(S_, D_) return bwd ? dispatch_v2_nt<HD, S_, D_, true>(st, p) : dispatch_v2_nt<HD, S_, D_, false>(st, p);
-  if (s && d) V2_GO(true, true)
-  if (s) V2_GO(true, false)
-  if (d) V2_GO(false, true)
-  V2_GO(false, false)
-#undef V2_GO
-}
-
 int attention_v2_dispatch(hipStream_t st, const AttnParams& p, bool bwd) {
-  switch (p.f.hd) {
-    case 16: return dispatch_v2<16>(st, p, bwd);
-    case 96: return dispatch_v2<96>(st, p, bwd);
-    case 128: return dispatch_v2<128>(st, p, bwd);
-    default: return dispatch_v2<64>(st, p, bwd);
-  }
+  return with_head_dim(p.f.hd, [&](auto hd) {
+    return with_flags(p, [&](auto s, auto d) {
+      return with_rung(p, [&](auto nt) {
+        constexpr int HD = decltype(hd)::value, NT = decltype(nt)::value;
+        constexpr bool STRUCT = decltype(s)::value, DROP = decltype(d)::value;
+        return bwd ? launch_v2<HD, NT, STRUCT, DROP, true>(st, p) : launch_v2<HD, NT, STRUCT, DROP, false>(st, p);
+      });
+    });
+  });
 }
 
 }  // namespace mdt

@@ -1,6 +1,6 @@
 # In-call A/B of two builds of libmdt_hip.so (ab_libs/old.so / ab_libs/new.so — scratch copies, git-ignored, DELETE them after the run: they ship with every gpurun lease): boxes differ by
 # several per cent, so both arms must run inside ONE gpurun call.  Usage: gpurun -- 'bash tools/ab_libs.sh [cmd...]'
-set -e
+set -e -o pipefail   # an arm that faults or times out ends the run: no later arm starts on that card
 export MDT_SKIP_SOURCE_HASH=1   # two builds against one csrc/: the import-time source-hash check is for shipped trees
 L=multimodaldiscussiontransformer_amd/libmdt_hip.so
 out=gpurun_out/ab_libs.log; rm -f $out

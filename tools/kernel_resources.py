@@ -17,5 +17,5 @@ for b in blocks:
         return int(m.group(1)) if m else -1
 
     print("%-102s vgpr=%d agpr=%d spill=%d scratch=%d occ=%d lds=%d" % (
-        dn, g("VGPRs"), g("AGPRs"), g("VGPR Spill"), g(r"ScratchSize \[bytes/lane\]"),
+        dn, g("VGPRs"), g("AGPRs"), g(r"VGPRs? Spill"), g(r"ScratchSize \[bytes/lane\]"),
         g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")))
