@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void fp8_quantize_kernel(int64_t rows, int64_t
       // code, which the MFMA propagates into the product and on to the loss, as the bf16 path would) and it marks the
       // running maximum as +inf, which fp8_scale_update leaves the scale alone for
       const float x = v[e] * scale;
-      const bool bad = !(fabsf(v[e]) <= 3.0e38f);      // NaN or infinity
+      const bool bad = !(fabsf(v[e]) <= 3.4028234663852886e38f);      // NaN or infinity: every finite value, FLT_MAX included, is a maximum
       amax = bad ? __builtin_inff() : fmaxf(amax, fabsf(v[e]));
       v[e] = (x != x) ? x : fminf(fmaxf(x, -FMAX), FMAX);   // saturate: the formats have no room above FMAX (e4m3fn: NaN)
     }

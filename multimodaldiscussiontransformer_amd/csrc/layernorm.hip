@@ -88,7 +88,7 @@ __device__ __forceinline__ void ln_fwd_row(const V* xv, const V* gv, const V* bv
 #pragma unroll
         for (int j = 0; j < VN; ++j) {
           const float r = o.get(j);                 // the ROUNDED output
-          const bool bad = !(fabsf(r) <= 3.0e38f);
+          const bool bad = !(fabsf(r) <= 3.4028234663852886e38f);
           qmax = bad ? __builtin_inff() : fmaxf(qmax, fabsf(r));
           const float xq = r * qs;
           qv[j] = (xq != xq) ? xq : fminf(fmaxf(xq, -FMAX), FMAX);
