@@ -94,12 +94,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_tile128(GemmParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
 
-  // XCD-aware tile order: the blocks sharing an XCD (blockIdx % 8) walk one contiguous
-  // chunk of the row-major tile grid, so an A row panel is reused from that XCD's L2.
-  const int nwg = p.tiles_m * p.tiles_n;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int tile = xcd_run(p.tiles_m * p.tiles_n, blockIdx.x);   // XCD-aware order of the row-major tile grid
   const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
   const int64_t m0 = (int64_t)tm * T_BM, n0 = (int64_t)tn * T_BN;
   const int64_t kbeg = (int64_t)blockIdx.z * p.k_chunk;
@@ -107,19 +102,9 @@ __global__ __launch_bounds__(256) void gemm_bf16_tile128(GemmParams p) {
   const int nk = (int)((kend - kbeg + T_BK - 1) / T_BK);
 
   const int64_t lda_b = p.lda * 2, ldb_b = p.ldb * 2;
-  // descriptors based at the first row this block touches (32-bit offsets stay small)
-  const char* a_base;
-  const char* b_base;
-  int64_t a_bytes, b_bytes;
-  if constexpr (!A_KM) { a_base = (const char*)p.A + m0 * lda_b; a_bytes = (p.M - m0) * lda_b; }
-  else { a_base = (const char*)p.A + kbeg * lda_b; a_bytes = (kend - kbeg) * lda_b; }
-  if constexpr (!B_KM) { b_base = (const char*)p.B + n0 * ldb_b; b_bytes = (p.N - n0) * ldb_b; }
-  else { b_base = (const char*)p.B + kbeg * ldb_b; b_bytes = (kend - kbeg) * ldb_b; }
-  const unsigned a_rec = (unsigned)(a_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : a_bytes);
-  const unsigned b_rec = (unsigned)(b_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : b_bytes);
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, a_rec, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)b_base, 0, b_rec, 0x00020000);
-  // k offsets are relative to the descriptor base: k-contiguous operands start at
+  const Window wa = operand_window<A_KM>(p.A, lda_b, m0, p.M, kbeg, kend), wb = operand_window<B_KM>(p.B, ldb_b, n0, p.N, kbeg, kend);
+  const __amdgpu_buffer_rsrc_t rsA = clamped_rsrc(wa), rsB = clamped_rsrc(wb);
+  // k offsets are relative to the window's base (operand_window): k-contiguous operands start at
   // absolute k (base = row m0, column 0), k-major ones at kbeg.
   const int64_t a_k0 = A_KM ? 0 : kbeg, b_k0 = B_KM ? 0 : kbeg;
   const int a_col0 = A_KM ? (int)m0 : 0, b_col0 = B_KM ? (int)n0 : 0;
@@ -181,10 +166,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tile256(GemmParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave / WN, wc = wave % WN;
 
-  const int nwg = p.tiles_m * p.tiles_n;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int tile = xcd_run(p.tiles_m * p.tiles_n, blockIdx.x);
   const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
   const int64_t kbeg = (int64_t)blockIdx.z * p.k_chunk;
@@ -192,17 +174,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_tile256(GemmParams p) {
   const int nk = (int)((kend - kbeg + T_BK - 1) / T_BK);
 
   const int64_t lda_b = p.lda * 2, ldb_b = p.ldb * 2;
-  const char* a_base;
-  const char* b_base;
-  int64_t a_bytes, b_bytes;
-  if constexpr (!A_KM) { a_base = (const char*)p.A + m0 * lda_b; a_bytes = (p.M - m0) * lda_b; }
-  else { a_base = (const char*)p.A + kbeg * lda_b; a_bytes = (kend - kbeg) * lda_b; }
-  if constexpr (!B_KM) { b_base = (const char*)p.B + n0 * ldb_b; b_bytes = (p.N - n0) * ldb_b; }
-  else { b_base = (const char*)p.B + kbeg * ldb_b; b_bytes = (kend - kbeg) * ldb_b; }
-  const unsigned a_rec = (unsigned)(a_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : a_bytes);
-  const unsigned b_rec = (unsigned)(b_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : b_bytes);
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, a_rec, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)b_base, 0, b_rec, 0x00020000);
+  const Window wa = operand_window<A_KM>(p.A, lda_b, m0, p.M, kbeg, kend), wb = operand_window<B_KM>(p.B, ldb_b, n0, p.N, kbeg, kend);
+  const __amdgpu_buffer_rsrc_t rsA = clamped_rsrc(wa), rsB = clamped_rsrc(wb);
   const int64_t a_k0 = A_KM ? 0 : kbeg, b_k0 = B_KM ? 0 : kbeg;
   const int a_col0 = A_KM ? (int)m0 : 0, b_col0 = B_KM ? (int)n0 : 0;
 
@@ -286,35 +259,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp256(GemmParams p) {
   const int wr = wave >> 2, wc = wave & 3;
   const bool late = wave >= 4;
 
-  // Work items = (K slab, tile), slab-major.  Workgroups are dispatched x-fastest and dealt round-robin to the 8 XCDs
-  // by their linear id, so XCD x = id % 8 takes the x-th contiguous run of the work list: with split-K (the weight
-  // gradients: 9-36 tiles per slab, 7-28 slabs) the tiles that share a slab's dY / X panels sit in ONE XCD's L2
-  // instead of being re-fetched through the fabric by all eight (3 x fewer fabric bytes on these launches).
-  const int tiles = p.tiles_m * p.tiles_n;
-  const int nwg = tiles * (int)gridDim.z;
-  const int bid = (int)blockIdx.z * (int)gridDim.x + (int)blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int work = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int slab = work / tiles;
-  const int tile = work - slab * tiles;
-  // Within a slab each XCD owns a contiguous run of this order: `group_n` column tiles wide, all the way down the rows,
-  // then the next group (group_n = tiles_n is plain row-major).
-  int tm, tn;
-  {
-    const int G = p.group_n, per_group = p.tiles_m * G;
-    const int gi = tile / per_group;
-    const int full = p.tiles_n / G;
-    if (gi < full) {
-      const int r = tile - gi * per_group;
-      tm = r / G;
-      tn = gi * G + (r - tm * G);
-    } else {
-      const int gsz = p.tiles_n - full * G;
-      const int r = tile - full * per_group;
-      tm = r / gsz;
-      tn = full * G + (r - tm * gsz);
-    }
-  }
+  // work item (K slab, tile) in the XCD-aware slab-major order, the tile in the grouped order (gemm_tiles.hpp: xcd_run,
+  // slab_work, tile_coords)
+  int slab, tile, tm, tn;
+  slab_work(p, slab, tile);
+  tile_coords(p, tile, tm, tn);
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
   const int64_t kbeg = (int64_t)slab * p.k_chunk;
   const int64_t kend = (kbeg + p.k_chunk < p.K) ? kbeg + p.k_chunk : p.K;
@@ -322,17 +271,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp256(GemmParams p) {
   const int nhs = 2 * nk;                      // 32-deep steps
 
   const int64_t lda_b = p.lda * 2, ldb_b = p.ldb * 2;
-  const char* a_base;
-  const char* b_base;
-  int64_t a_bytes, b_bytes;
-  if constexpr (!A_KM) { a_base = (const char*)p.A + m0 * lda_b; a_bytes = (p.M - m0) * lda_b; }
-  else { a_base = (const char*)p.A + kbeg * lda_b; a_bytes = (kend - kbeg) * lda_b; }
-  if constexpr (!B_KM) { b_base = (const char*)p.B + n0 * ldb_b; b_bytes = (p.N - n0) * ldb_b; }
-  else { b_base = (const char*)p.B + kbeg * ldb_b; b_bytes = (kend - kbeg) * ldb_b; }
-  const unsigned a_rec = (unsigned)(a_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : a_bytes);
-  const unsigned b_rec = (unsigned)(b_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : b_bytes);
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, a_rec, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)b_base, 0, b_rec, 0x00020000);
+  const Window wa = operand_window<A_KM>(p.A, lda_b, m0, p.M, kbeg, kend), wb = operand_window<B_KM>(p.B, ldb_b, n0, p.N, kbeg, kend);
+  const __amdgpu_buffer_rsrc_t rsA = clamped_rsrc(wa), rsB = clamped_rsrc(wb);
   const int64_t a_k0 = A_KM ? 0 : kbeg, b_k0 = B_KM ? 0 : kbeg;
   const int a_col0 = A_KM ? (int)m0 : 0, b_col0 = B_KM ? (int)n0 : 0;
 
@@ -352,12 +292,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp256(GemmParams p) {
     char* st = smem + buf * PP_STAGE;
     stage_step<A_KM, BM, 8>(rsA, lda_b, a_k0 + (int64_t)hs * 32, a_col0, st, wave, lane);
     stage_step<B_KM, BN, 8>(rsB, ldb_b, b_k0 + (int64_t)hs * 32, b_col0, st + A_BYTES, wave, lane);
-  };
-  auto wait_pieces = [&](int halves) {           // all but the youngest `halves` steps of this wave have landed
-    if (halves >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (halves == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (halves == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
   static_assert(PP_DIST >= 2 && PP_DIST <= 4, "wait_pieces assumes at most 3 steps left in flight");
 #pragma unroll
@@ -439,8 +373,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp256(GemmParams p) {
 }
 
 // ------------------------------------------------------------------ persistent form of the ping-pong kernel
-// One workgroup per CU walks tiles v = blockIdx.x, + gridDim.x, ... (the XCD-aware order above holds because
-// gridDim.x is a multiple of 8).  The stage ring simply keeps turning across tile boundaries: the last PP_DIST
+// One workgroup per CU walks tiles v = blockIdx.x, + gridDim.x, ... (the XCD-aware order, gemm_tiles.hpp xcd_run, holds
+// because gridDim.x is a multiple of 8).  The stage ring simply keeps turning across tile boundaries: the last PP_DIST
 // steps of a tile issue the first PP_DIST steps of the NEXT tile, so its operands land while this tile's
 // register-resident epilogue (no LDS, no barrier) runs — the ~2 us first-fetch latency and the workgroup
 // launch / drain that a 12-step (K = 768) tile pays per tile otherwise are gone.  At a boundary the early
@@ -480,57 +414,19 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp256p(GemmParams p) {
   const int nhs = (int)((p.K * ESZ + 63) / 64);           // 64-byte steps
   const int64_t lda_b = p.lda * ESZ, ldb_b = p.ldb * ESZ;
 
-  struct Desc { __amdgpu_buffer_rsrc_t rsA, rsB; int a_col0, b_col0; int64_t m0, n0; };
-  auto make_desc = [&](int v) {
-    const int q8 = nvt >> 3, r8 = nvt & 7, xcd = v & 7;
-    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (v >> 3);
+  auto make_desc = [&](int v) {              // virtual id v -> its tile, in the XCD-aware grouped order
     int tm, tn;
-    {
-      const int G = p.group_n, per_group = p.tiles_m * G;
-      const int gi = tile / per_group;
-      const int full = p.tiles_n / G;
-      if (gi < full) {
-        const int r = tile - gi * per_group;
-        tm = r / G;
-        tn = gi * G + (r - tm * G);
-      } else {
-        const int gsz = p.tiles_n - full * G;
-        const int r = tile - full * per_group;
-        tm = r / gsz;
-        tn = full * G + (r - tm * gsz);
-      }
-    }
-    Desc d;
-    d.m0 = (int64_t)tm * BM;
-    d.n0 = (int64_t)tn * BN;
+    tile_coords(p, xcd_run(nvt, v), tm, tn);
+    const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
     // diagnostic (MDT_GEMM_DIAG=8): every tile LOADS the operand panels of tile (0, 0) — all fills hit L2 — while
     // stores still go to the tile's own place: separates the fill's miss path from the loop's own cost
-    const int64_t lm0 = (p.epilogue & (1 << 23)) ? 0 : d.m0, ln0 = (p.epilogue & (1 << 23)) ? 0 : d.n0;
-    const char* a_base;
-    const char* b_base;
-    int64_t a_bytes, b_bytes;
-    if constexpr (!A_KM) { a_base = (const char*)p.A + lm0 * lda_b; a_bytes = (p.M - lm0) * lda_b; }
-    else { a_base = (const char*)p.A; a_bytes = p.K * lda_b; }
-    if constexpr (!B_KM) { b_base = (const char*)p.B + ln0 * ldb_b; b_bytes = (p.N - ln0) * ldb_b; }
-    else { b_base = (const char*)p.B; b_bytes = p.K * ldb_b; }
-    const unsigned a_rec = (unsigned)(a_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : a_bytes);
-    const unsigned b_rec = (unsigned)(b_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : b_bytes);
-    d.rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, a_rec, 0x00020000);
-    d.rsB = __builtin_amdgcn_make_buffer_rsrc((void*)b_base, 0, b_rec, 0x00020000);
-    d.a_col0 = A_KM ? (int)lm0 : 0;
-    d.b_col0 = B_KM ? (int)ln0 : 0;
-    return d;
+    const bool diag_l2 = (p.epilogue & (1 << 23)) != 0;
+    return tile_desc<A_KM, B_KM>(p, lda_b, ldb_b, m0, n0, diag_l2 ? 0 : m0, diag_l2 ? 0 : n0);
   };
-  auto issue_step = [&](const Desc& d, int hs, int buf) {
+  auto issue_step = [&](const TileDesc& d, int hs, int buf) {
     char* st = smem + buf * PP_STAGE;
     stage_step<A_KM, BM, 8>(d.rsA, lda_b, (int64_t)hs * 32, d.a_col0, st, wave, lane);
     stage_step<B_KM, BN, 8>(d.rsB, ldb_b, (int64_t)hs * 32, d.b_col0, st + A_BYTES, wave, lane);
-  };
-  auto wait_pieces = [&](int halves) {
-    if (halves >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (halves == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (halves == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
   static_assert(PP_DIST >= 2 && PP_DIST <= 4, "wait_pieces assumes at most 3 steps left in flight");
   unsigned jit_state = JIT ? ((unsigned)blockIdx.x * 2654435761u) ^ ((unsigned)wave * 0x9E3779B9u) ^ (unsigned)__builtin_amdgcn_s_memtime() : 0u;
@@ -578,9 +474,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp256p(GemmParams p) {
     v_next = *slot;
     __syncthreads();
   }
-  Desc cur = make_desc(v);
+  TileDesc cur = make_desc(v);
   bool has_next = v_next >= 0;
-  Desc nxt = make_desc(has_next ? v_next : v);
+  TileDesc nxt = make_desc(has_next ? v_next : v);
 #pragma unroll
   for (int h = 0; h < PP_DIST; ++h) issue_step(cur, h, h);       // host guarantees nhs >= PP_DIST
   wait_pieces(PP_DIST - 1);
@@ -718,75 +614,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int nhs = (int)((p.K + 31) / 32);
   const int64_t lda_b = p.lda * 2, ldb_b = p.ldb * 2;
 
-  struct Desc { __amdgpu_buffer_rsrc_t rsA, rsB; int a_col0, b_col0; int64_t m0, n0; };
-  auto make_desc = [&](int v) {
-    const int q8 = nvt >> 3, r8 = nvt & 7, xcd = v & 7;
-    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (v >> 3);
+  auto make_desc = [&](int v) {              // virtual id v -> its tile, in the XCD-aware grouped order
     int tm, tn;
-    {
-      const int G = p.group_n, per_group = p.tiles_m * G;
-      const int gi = tile / per_group;
-      const int full = p.tiles_n / G;
-      if (gi < full) {
-        const int r = tile - gi * per_group;
-        tm = r / G;
-        tn = gi * G + (r - tm * G);
-      } else {
-        const int gsz = p.tiles_n - full * G;
-        const int r = tile - full * per_group;
-        tm = r / gsz;
-        tn = full * G + (r - tm * gsz);
-      }
-    }
-    Desc d;
-    d.m0 = (int64_t)tm * BM;
-    d.n0 = (int64_t)tn * BN;
-    const char* a_base;
-    const char* b_base;
-    int64_t a_bytes, b_bytes;
-    if constexpr (!A_KM) { a_base = (const char*)p.A + d.m0 * lda_b; a_bytes = (p.M - d.m0) * lda_b; }
-    else { a_base = (const char*)p.A; a_bytes = p.K * lda_b; }
-    if constexpr (!B_KM) { b_base = (const char*)p.B + d.n0 * ldb_b; b_bytes = (p.N - d.n0) * ldb_b; }
-    else { b_base = (const char*)p.B; b_bytes = p.K * ldb_b; }
-    const unsigned a_rec = (unsigned)(a_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : a_bytes);
-    const unsigned b_rec = (unsigned)(b_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : b_bytes);
-    d.rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, a_rec, 0x00020000);
-    d.rsB = __builtin_amdgcn_make_buffer_rsrc((void*)b_base, 0, b_rec, 0x00020000);
-    d.a_col0 = A_KM ? (int)d.m0 : 0;
-    d.b_col0 = B_KM ? (int)d.n0 : 0;
-    return d;
+    tile_coords(p, xcd_run(nvt, v), tm, tn);
+    const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
+    return tile_desc<A_KM, B_KM>(p, lda_b, ldb_b, m0, n0, m0, n0);
   };
-  // The wave's 8 LDS-DMA pieces of a step: pieces 0-3 of A, 4-7 of B (piece index inside the operand = wave + 4 i).
-  // Their per-lane offsets do not depend on the step or the tile: the step (and, for a k-major operand, the tile's
-  // column origin) rides in the instruction's SCALAR offset, so a piece costs no vector arithmetic.
+  // The wave's 8 LDS-DMA pieces of a step: pieces 0-3 of A, 4-7 of B; per-lane offsets fixed for the launch (w4_piece_voff)
   unsigned voffA[4], voffB[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int piece = wave + 4 * i;
-    if constexpr (!A_KM) {
-      const int row = piece * 16 + (lane >> 2);
-      voffA[i] = (unsigned)(row * lda_b + (((lane & 3) ^ swz_h(row)) * 16));
-    } else {
-      const int k = piece * 2 + (lane >> 5), c16 = lane & 31;
-      voffA[i] = (unsigned)(k * lda_b + ((((c16 >> 1) ^ swz_km(k)) * 16 + (c16 & 1) * 8) * 2));
-    }
-    if constexpr (!B_KM) {
-      const int row = piece * 16 + (lane >> 2);
-      voffB[i] = (unsigned)(row * ldb_b + (((lane & 3) ^ swz_h(row)) * 16));
-    } else {
-      const int k = piece * 2 + (lane >> 5), c16 = lane & 31;
-      voffB[i] = (unsigned)(k * ldb_b + ((((c16 >> 1) ^ swz_km(k)) * 16 + (c16 & 1) * 8) * 2));
-    }
+    voffA[i] = w4_piece_voff<A_KM>(wave + 4 * i, lane, lda_b);
+    voffB[i] = w4_piece_voff<B_KM>(wave + 4 * i, lane, ldb_b);
   }
-  auto soff_a = [&](const Desc& d, int hs) -> int { return A_KM ? (int)((int64_t)hs * 32 * lda_b) + d.a_col0 * 2 : hs * 64; };
-  auto soff_b = [&](const Desc& d, int hs) -> int { return B_KM ? (int)((int64_t)hs * 32 * ldb_b) + d.b_col0 * 2 : hs * 64; };
-  auto issue_piece = [&](const Desc& d, int sa, int sb, int buf, int q) __attribute__((always_inline)) {
+  auto soff_a = [&](const TileDesc& d, int hs) -> int { return A_KM ? (int)((int64_t)hs * 32 * lda_b) + d.a_col0 * 2 : hs * 64; };
+  auto soff_b = [&](const TileDesc& d, int hs) -> int { return B_KM ? (int)((int64_t)hs * 32 * ldb_b) + d.b_col0 * 2 : hs * 64; };
+  auto issue_piece = [&](const TileDesc& d, int sa, int sb, int buf, int q) __attribute__((always_inline)) {
     char* st = smem + buf * PP_STAGE;
     const int piece = wave + 4 * (q & 3);
     if (q < 4) w4_dma(d.rsA, st + piece * 1024, voffA[q & 3], sa);
     else w4_dma(d.rsB, st + A_BYTES + piece * 1024, voffB[q & 3], sb);
   };
-  auto issue_step = [&](const Desc& d, int hs, int buf) {
+  auto issue_step = [&](const TileDesc& d, int hs, int buf) {
     const int sa = soff_a(d, hs), sb = soff_b(d, hs);
 #pragma unroll
     for (int q = 0; q < 8; ++q) issue_piece(d, sa, sb, buf, q);
@@ -803,16 +652,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
   int v = blockIdx.x;
   int v_next = v + (int)gridDim.x < nvt ? v + (int)gridDim.x : -1;
-  Desc cur = make_desc(v);
+  TileDesc cur = make_desc(v);
   bool has_next = v_next >= 0;
   // after the last tile the ring keeps turning on a descriptor of zero records (every load reads as 0, nobody reads the
   // stage): the loop needs no "nothing left to request" case and the vmcnt arithmetic is the same in every step
-  auto null_desc = [&](Desc d) {
-    d.rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0, 0x00020000);
-    d.rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, 0, 0x00020000);
-    return d;
-  };
-  Desc nxt = has_next ? make_desc(v_next) : null_desc(cur);
+  TileDesc nxt = has_next ? make_desc(v_next) : null_tile(p, cur);
 #pragma unroll
   for (int h = 0; h < PP_DIST; ++h) issue_step(cur, h, h);        // host guarantees nhs >= PP_DIST
   wait_vm<(PP_DIST - 1) * 8>();
@@ -835,7 +679,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   bf16x8 pend[W4_NPEND];
 #pragma unroll
   for (int i = 0; i < W4_NPEND; ++i) pend[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc((void*)p.C, 0, 0, 0x00020000);
+  __amdgpu_buffer_rsrc_t rsP = clamped_rsrc(p.C, 0);
   const int c_lane = lane & 15, g_lane = lane >> 4;
   const unsigned voffP = (unsigned)((wr * 128 + c_lane) * (p.ldc * 2) + (wc * 128 + 16 * (g_lane & 1) + 8 * (g_lane >> 1)) * 2);
   const int ldc16 = (int)(p.ldc * 2 * 16);         // bytes between row tiles
@@ -856,11 +700,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int i = 0; i < W4_DS; ++i) asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen" ::"v"(zero4), "v"(voffP), "s"(rsP) : "memory");
 #endif
   }
-  auto desc_c = [&](const Desc& d) {
-    const int64_t bytes = (p.M - d.m0) * p.ldc * 2 - d.n0 * 2;
-    return __builtin_amdgcn_make_buffer_rsrc((void*)((bf16_t*)p.C + d.m0 * p.ldc + d.n0), 0,
-                                             (unsigned)(bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : bytes), 0x00020000);
-  };
 
   // one 32-k step on fragment set `cur`: FIRST starts the accumulators from zero; NW = vector-memory operations that may
   // still be in flight when the step begins; ST >= 0: pending vectors ST and ST + 1 leave in this step
@@ -872,7 +711,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #else
 #define W4_MF(i_, j_) (void)first
 #endif
-  auto step = [&](auto cs_c, auto first_c, auto nw_c, auto st_c, auto ld_c, const Desc& d_issue, int hs_issue) __attribute__((always_inline)) {
+  auto step = [&](auto cs_c, auto first_c, auto nw_c, auto st_c, auto ld_c, const TileDesc& d_issue, int hs_issue) __attribute__((always_inline)) {
     constexpr int cs = decltype(cs_c)::value, ns = cs ^ 1;
     constexpr bool first = decltype(first_c)::value;
     constexpr int NW = decltype(nw_c)::value, ST = decltype(st_c)::value;
@@ -909,7 +748,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   auto run_step = [&](auto cs_c, auto first_c, auto nw_c, auto st_c, auto ld_c, int hs) __attribute__((always_inline)) {
     const int tgt = hs + PP_DIST;
     const bool same = tgt < nhs;
-    Desc d = nxt;
+    TileDesc d = nxt;
     if (same) d = cur;
     step(cs_c, first_c, nw_c, st_c, ld_c, d, same ? tgt : tgt - nhs);
   };
@@ -946,11 +785,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     EpiPre<4> epf;
     EpiBuf eb;
     if constexpr (PEND) {
-      auto desc_of = [&](const void* base, int64_t ld) {
-        const int64_t bytes = (p.M - cur.m0) * ld * 2 - cur.n0 * 2;
-        return __builtin_amdgcn_make_buffer_rsrc((void*)((bf16_t*)base + cur.m0 * ld + cur.n0), 0,
-                                                 (unsigned)(bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : bytes), 0x00020000);
-      };
+      auto desc_of = [&](const void* base, int64_t ld) { return output_window<bf16_t>(base, ld, p.M, cur.m0, cur.n0); };
       auto voff_of = [&](int64_t ld) { return (unsigned)((wr * 128 + c_lane) * (ld * 2) + (wc * 128 + 16 * (g_lane & 1) + 8 * (g_lane >> 1)) * 2); };
       eb.rsC = desc_of(p.C, p.ldc); eb.voffC = voffP; eb.ldc16 = ldc16;
       eb.rsX = eb.rsC; eb.voffX = voffP; eb.ldx16 = ldc16;
@@ -997,7 +832,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     v += gridDim.x;
     v_next = v + (int)gridDim.x < nvt ? v + (int)gridDim.x : -1;
     has_next = v_next >= 0;
-    nxt = has_next ? make_desc(v_next) : null_desc(cur);
+    nxt = has_next ? make_desc(v_next) : null_tile(p, cur);
   }
 #undef W4_N
 #undef W4_MF
@@ -1148,6 +983,8 @@ static int g_tile_queue_sets = 0;
 // same rows at the same time — each XCD keeps its half of B resident and the second reader of an A panel finds it in the
 // Infinity Cache.  In-call A/B at N = 3072, K = 768: +3-4 % (fabric reads 2.7 -> ~1.3 GB).  Finer groups lose (A then
 // streams from HBM once per group); odd splits (N = 2304) lose.  b_panel: bytes of one 256-column panel of B.
+// Invariant (gemm_tiles.hpp tile_coords: the ragged last group is never reached): group_n DIVIDES tiles_n — what is returned
+// here, and the 1 plan_gemm picks for wide split-K launches.
 static int xcd_group_n(int tiles_m, int tiles_n, double b_panel, int n_cus) {
   if (tiles_n % 2 == 0 && b_panel * tiles_n > 3.5e6 && b_panel * (tiles_n / 2) <= 2.5e6 && (double)tiles_m * tiles_n >= 4.0 * n_cus)
     return tiles_n / 2;

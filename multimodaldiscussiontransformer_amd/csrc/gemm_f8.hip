@@ -62,43 +62,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int nsp = nst >> 1;                           // 128-k steps
   const int64_t lda_b = p.lda, ldb_b = p.ldb;         // bytes: one per element
 
+  // this kernel's own tile descriptor: both operands are k-contiguous, so no column origins (Desc's a_col0 / b_col0), and
+  // the statement order below is the one its instruction stream was tuned with
   struct Desc { __amdgpu_buffer_rsrc_t rsA, rsB; int64_t m0, n0; };
-  auto make_desc = [&](int v) {
-    const int q8 = nvt >> 3, r8 = nvt & 7, xcd = v & 7;
-    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (v >> 3);
+  auto make_desc = [&](int v) {              // virtual id v -> its tile, in the XCD-aware grouped order
     int tm, tn;
-    {
-      const int G = p.group_n, per_group = p.tiles_m * G;
-      const int gi = tile / per_group;
-      const int full = p.tiles_n / G;
-      if (gi < full) {
-        const int r = tile - gi * per_group;
-        tm = r / G;
-        tn = gi * G + (r - tm * G);
-      } else {
-        const int gsz = p.tiles_n - full * G;
-        const int r = tile - full * per_group;
-        tm = r / gsz;
-        tn = full * G + (r - tm * gsz);
-      }
-    }
+    tile_coords(p, xcd_run(nvt, v), tm, tn);
     Desc d;
     d.m0 = (int64_t)tm * BM;
     d.n0 = (int64_t)tn * BN;
     const int64_t a_bytes = (p.M - d.m0) * lda_b, b_bytes = (p.N - d.n0) * ldb_b;
-    const unsigned a_rec = (unsigned)(a_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : a_bytes);
-    const unsigned b_rec = (unsigned)(b_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : b_bytes);
-    d.rsA = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.A + d.m0 * lda_b), 0, a_rec, 0x00020000);
-    d.rsB = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.B + d.n0 * ldb_b), 0, b_rec, 0x00020000);
+    const unsigned a_rec = clamped_records(a_bytes), b_rec = clamped_records(b_bytes);
+    d.rsA = raw_rsrc((const char*)p.A + d.m0 * lda_b, a_rec);
+    d.rsB = raw_rsrc((const char*)p.B + d.n0 * ldb_b, b_rec);
     return d;
   };
   // the wave's 8 LDS-DMA pieces of a stage: 4 of A, 4 of B, 16 rows of 64 bytes each; the stage rides in the scalar offset
   unsigned voffA[4], voffB[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int row = (wave + 4 * i) * 16 + (lane >> 2);
-    voffA[i] = (unsigned)(row * lda_b + (((lane & 3) ^ swz_h(row)) * 16));
-    voffB[i] = (unsigned)(row * ldb_b + (((lane & 3) ^ swz_h(row)) * 16));
+    voffA[i] = w4_piece_voff<false>(wave + 4 * i, lane, lda_b);
+    voffB[i] = w4_piece_voff<false>(wave + 4 * i, lane, ldb_b);
   }
   auto issue_piece = [&](const Desc& d, int soff, int buf, int q) __attribute__((always_inline)) {
     char* st = smem + buf * PP_STAGE;
@@ -112,8 +96,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   Desc cur = make_desc(v);
   bool has_next = v_next >= 0;
   auto null_desc = [&](Desc d) {        // after the last tile the ring keeps turning on descriptors of zero records
-    d.rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0, 0x00020000);
-    d.rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, 0, 0x00020000);
+    d.rsA = clamped_rsrc(p.A, 0);
+    d.rsB = clamped_rsrc(p.B, 0);
     return d;
   };
   Desc nxt = has_next ? make_desc(v_next) : null_desc(cur);
@@ -150,7 +134,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   bf16x8 pend[F8W_NPEND];
 #pragma unroll
   for (int i = 0; i < F8W_NPEND; ++i) pend[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc((void*)p.C, 0, 0, 0x00020000);
+  __amdgpu_buffer_rsrc_t rsP = clamped_rsrc(p.C, 0);
   const int c_lane = lane & 15, g_lane = lane >> 4;
   const unsigned voffP = (unsigned)((wr * 128 + c_lane) * (p.ldc * 2) + (wc * 128 + 16 * (g_lane & 1) + 8 * (g_lane >> 1)) * 2);
   const int ldc16 = (int)(p.ldc * 2 * 16);
@@ -240,11 +224,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     EpiPre<4> epf;
     EpiBuf eb;
     if constexpr (PEND) {
-      auto desc_of = [&](const void* base, int64_t ld) {
-        const int64_t bytes = (p.M - cur.m0) * ld * 2 - cur.n0 * 2;
-        return __builtin_amdgcn_make_buffer_rsrc((void*)((bf16_t*)base + cur.m0 * ld + cur.n0), 0,
-                                                 (unsigned)(bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : bytes), 0x00020000);
-      };
+      auto desc_of = [&](const void* base, int64_t ld) { return output_window<bf16_t>(base, ld, p.M, cur.m0, cur.n0); };
       auto voff_of = [&](int64_t ld) { return (unsigned)((wr * 128 + c_lane) * (ld * 2) + (wc * 128 + 16 * (g_lane & 1) + 8 * (g_lane >> 1)) * 2); };
       eb.rsC = desc_of(p.C, p.ldc); eb.voffC = voffP; eb.ldc16 = ldc16;
       eb.rsX = eb.rsC; eb.voffX = voffP; eb.ldx16 = ldc16;
@@ -254,9 +234,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       if constexpr (PK == 1) { eb.rsR = desc_of(p.aux, p.ldaux); eb.voffR = voff_of(p.ldaux); eb.ldr16 = (int)(p.ldaux * 32); }
       if constexpr (PK == 2) { eb.rsR = desc_of(p.residual, p.ldr); eb.voffR = voff_of(p.ldr); eb.ldr16 = (int)(p.ldr * 32); }
       if constexpr (Q8 != 0) {                      // one byte per element: a lane's 8 columns are 8 bytes, a column pair 32
-        const int64_t bytes = (p.M - cur.m0) * p.ld_q8 - cur.n0;
-        eb.rsQ = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.q8_out + cur.m0 * p.ld_q8 + cur.n0), 0,
-                                                   (unsigned)(bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : bytes), 0x00020000);
+        eb.rsQ = output_window<char>(p.q8_out, p.ld_q8, p.M, cur.m0, cur.n0);
         eb.voffQ = (unsigned)((wr * 128 + c_lane) * p.ld_q8 + (wc * 128 + 16 * (g_lane & 1) + 8 * (g_lane >> 1)));
         eb.ldq16 = (int)(p.ld_q8 * 16);
         eb.q_scale = q_scale;

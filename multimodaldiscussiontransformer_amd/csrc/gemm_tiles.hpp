@@ -59,6 +59,105 @@ __device__ __forceinline__ void epilogue_store(const GemmParams& p, int64_t row,
   *c = from_f32<TOut>(v);
 }
 
+// ------------------------------------------------------------------ work order
+// Workgroups are dispatched x-fastest and dealt round-robin to the 8 XCDs by their linear id, so XCD x = id % 8 takes the
+// x-th CONTIGUOUS run of a list of n work items: neighbours in the list share an XCD's L2.  Position in the list of workgroup
+// (or, in the persistent kernels, virtual id) `id`; a bijection of [0, n) for any n when the ids are 0 .. n - 1.
+//   Row-major tile lists (tile128, tile256, patch embedding): an A row panel is reused from that XCD's L2.
+//   Split-K lists of (K slab, tile), slab-major (slab_work below; the weight gradients: 9-36 tiles per slab, 7-28 slabs): the
+//   tiles that share a slab's dY / X panels sit in ONE XCD's L2 instead of being re-fetched through the fabric by all eight
+//   (3 x fewer fabric bytes on these launches).
+__device__ __forceinline__ int xcd_run(int n, int id) {
+  const int q8 = n >> 3, r8 = n & 7, xcd = id & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+}
+
+// Work items = (K slab, tile), slab-major, for a grid of tiles x slabs workgroups (x, z): this workgroup's item.
+__device__ __forceinline__ void slab_work(const GemmParams& p, int& slab, int& tile) {
+  const int tiles = p.tiles_m * p.tiles_n;
+  const int work = xcd_run(tiles * (int)gridDim.z, (int)blockIdx.z * (int)gridDim.x + (int)blockIdx.x);
+  slab = work / tiles;
+  tile = work - slab * tiles;
+}
+
+// Tile order of the 256 x 256 kernels: `group_n` column tiles wide, all the way down the rows, then the next group, so each
+// XCD owns a contiguous run of this order (group_n = tiles_n is plain row-major, 1 column-major).  The host only ever sets a
+// group_n that DIVIDES tiles_n — tiles_n, tiles_n / 2 with tiles_n even, or 1 (plan_gemm, xcd_group_n) — so the ragged last
+// group (gi >= full) is never reached.  The branch stays all the same: without it the 4-wave kernels, which have no scalar
+// register to spare, come out with another register assignment all through their K loops.
+__device__ __forceinline__ void tile_coords(const GemmParams& p, int tile, int& tm, int& tn) {
+  const int G = p.group_n, per_group = p.tiles_m * G;
+  const int gi = tile / per_group;
+  const int full = p.tiles_n / G;
+  if (gi < full) {
+    const int r = tile - gi * per_group;
+    tm = r / G;
+    tn = gi * G + (r - tm * G);
+  } else {
+    const int gsz = p.tiles_n - full * G;
+    const int r = tile - full * per_group;
+    tm = r / gsz;
+    tn = full * G + (r - tm * gsz);
+  }
+}
+
+// ------------------------------------------------------------------ buffer descriptors
+// `bytes` from `base` on, clamped to what a descriptor's 32-bit record count holds; raw (untyped) 32-bit format.  Anything
+// past it reads as zero and is dropped on a store: bytes = 0 is the descriptor that loads zeros and stores nothing.
+__device__ __forceinline__ unsigned clamped_records(int64_t bytes) { return (unsigned)(bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : bytes); }
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void* base, unsigned records) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, records, 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t clamped_rsrc(const void* base, int64_t bytes) { return raw_rsrc(base, clamped_records(bytes)); }
+
+// What a workgroup loads of one GEMM operand, based at the first row it touches so that 32-bit offsets stay small.
+//   k-contiguous ([rows | columns][k], KM = false): rows rc0 .. rc_end of the operand, based at (rc0, k = 0) — k offsets
+//                                                   into it are absolute;
+//   k-major      ([k][rows | columns], KM = true):  k-rows k0 .. k_end, based at (k0, column 0) — k offsets are relative to
+//                                                   k0 and the tile's column origin is added by the loads.
+// rc0 is the origin the caller wants LOADED (MDT_GEMM_DIAG=8 passes 0 there for every tile).
+struct Window { const char* base; int64_t bytes; };
+template <bool KM>
+__device__ __forceinline__ Window operand_window(const void* base, int64_t ld_bytes, int64_t rc0, int64_t rc_end, int64_t k0, int64_t k_end) {
+  if constexpr (!KM) return Window{(const char*)base + rc0 * ld_bytes, (rc_end - rc0) * ld_bytes};
+  else return Window{(const char*)base + k0 * ld_bytes, (k_end - k0) * ld_bytes};
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t clamped_rsrc(Window w) { return clamped_rsrc(w.base, w.bytes); }
+
+// Rows m0 .. M of a row-major output (or epilogue operand) with elements of type T, based at element (m0, n0): the window the
+// epilogues of the 4-wave kernels store through — rows past M fall outside it and are dropped.
+template <typename T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t output_window(const void* base, int64_t ld, int64_t M, int64_t m0, int64_t n0) {
+  constexpr int64_t ESZ = sizeof(T);
+  const int64_t bytes = (M - m0) * ld * ESZ - n0 * ESZ;
+  return clamped_rsrc((const T*)base + m0 * ld + n0, bytes);
+}
+
+// One tile of a persistent kernel (pp256p, w4p, f8_w4): its origin and the windows its operand panels are loaded through.
+// a_col0 / b_col0: column origin of a k-major operand inside its window (0 for a k-contiguous one).
+struct TileDesc { __amdgpu_buffer_rsrc_t rsA, rsB; int a_col0, b_col0; int64_t m0, n0; };
+// tile (m0, n0) of p, LOADING the panels at (lm0, ln0) — the same origin except under MDT_GEMM_DIAG=8; k = 0 .. K
+template <bool A_KM, bool B_KM>
+__device__ __forceinline__ TileDesc tile_desc(const GemmParams& p, int64_t lda_b, int64_t ldb_b, int64_t m0, int64_t n0,
+                                              int64_t lm0, int64_t ln0) {
+  TileDesc d;
+  d.m0 = m0;
+  d.n0 = n0;
+  const Window wa = operand_window<A_KM>(p.A, lda_b, lm0, p.M, 0, p.K), wb = operand_window<B_KM>(p.B, ldb_b, ln0, p.N, 0, p.K);
+  const unsigned a_rec = clamped_records(wa.bytes), b_rec = clamped_records(wb.bytes);
+  d.rsA = raw_rsrc(wa.base, a_rec);
+  d.rsB = raw_rsrc(wb.base, b_rec);
+  d.a_col0 = A_KM ? (int)lm0 : 0;
+  d.b_col0 = B_KM ? (int)ln0 : 0;
+  return d;
+}
+// d with operand windows of zero records: every load reads as 0
+__device__ __forceinline__ TileDesc null_tile(const GemmParams& p, TileDesc d) {
+  d.rsA = clamped_rsrc(p.A, 0);
+  d.rsB = clamped_rsrc(p.B, 0);
+  return d;
+}
+
 
 // ------------------------------------------------------------------ bf16 128x128x64 kernel
 constexpr int T_BM = 128, T_BN = 128, T_BK = 64;
@@ -309,6 +408,14 @@ constexpr int PP_STAGE = 2 * 256 * 64;   // 32 KiB: one 32-k ring stage of the 2
 
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// 8-wave ping-pong kernels (4 LDS-DMA pieces per wave and 32-k step, at most 3 steps left in flight: PP_DIST <= 4): all but
+// the youngest `halves` steps of this wave have landed
+__device__ __forceinline__ void wait_pieces(int halves) {
+  if (halves >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+  else if (halves == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+  else if (halves == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
 
 // ------------------------------------------------------------------ 4-wave form of the persistent kernel
 // One wave per SIMD with the whole register file (256 accumulators in AGPRs + 256 VGPRs), 128 x 128 of the 256 x 256 tile
@@ -337,6 +444,21 @@ __device__ __forceinline__ bf16x8 w4_frag(const char* lds_tile, int rc_base, int
     i32x2 lo, hi;
     asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3" : "=&v"(lo), "=&v"(hi) : "v"(addr), "n"(4 * RB) : "memory");
     return __builtin_bit_cast(bf16x8, i32x4{lo[0], lo[1], hi[0], hi[1]});
+  }
+}
+
+// Per-lane offset of LDS-DMA piece i (0-3; piece index inside the operand = wave + 4 i) of a 4-wave kernel's 32-k stage of a
+// 256-row operand, from (first row | k-row of the stage, column origin) — the 1-KiB pieces and source swizzles of stage_step.
+// It does not depend on the step or the tile: the step (and, for a k-major operand, the tile's column origin) rides in the
+// instruction's SCALAR offset, so a piece costs no vector arithmetic.
+template <bool KM>
+__device__ __forceinline__ unsigned w4_piece_voff(int piece, int lane, int64_t ld_bytes) {
+  if constexpr (!KM) {
+    const int row = piece * 16 + (lane >> 2);
+    return (unsigned)(row * ld_bytes + (((lane & 3) ^ swz_h(row)) * 16));
+  } else {
+    const int k = piece * 2 + (lane >> 5), c16 = lane & 31;
+    return (unsigned)(k * ld_bytes + ((((c16 >> 1) ^ swz_km(k)) * 16 + (c16 & 1) * 8) * 2));
   }
 }
 

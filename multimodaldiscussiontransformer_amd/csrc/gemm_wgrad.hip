@@ -6,8 +6,8 @@
 // on one fragment set while the reads fill the other.  Against the 8-wave ping-pong kernel (gemm_bf16_pp256<float>), whose
 // READ segment (24 transposing fragment reads + 4 LDS-DMA issues + two waits) outlasts the partner group's 32-MFMA segment
 // on these launches (MFMA pipe busy 0.515, profiles/round2_r2v8_sq_counters.json): a third less LDS read traffic and no
-// segment hand-over.  One work item (K slab, tile) per workgroup, slab-major and XCD-aware exactly as in gemm_bf16_pp256
-// (the tiles that share a slab's dY / X panels sit in one XCD's L2); no persistence — a slab's 200+ K-tiles amortise the
+// segment hand-over.  One work item (K slab, tile) per workgroup, slab-major and XCD-aware (gemm_tiles.hpp slab_work:
+// the tiles that share a slab's dY / X panels sit in one XCD's L2); no persistence — a slab's 200+ K-tiles amortise the
 // prologue.  Epilogue: the four 64 x 64 blocks of a wave go through its 16-KiB LDS slot (the ring is idle by then) and leave
 // as 256-byte contiguous fp32 atomics (tile_epilogue<float>); MDT_EPI_ASUM (the bias gradient riding on the weight
 // gradient) as in the 8-wave kernel: in the workgroups of tile column 0 the two waves that hold the same A fragments take
@@ -30,30 +30,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
 
-  // work items = (K slab, tile), slab-major; XCD x = id % 8 takes the x-th contiguous run of the list (gemm_bf16_pp256)
-  const int tiles = p.tiles_m * p.tiles_n;
-  const int nwg = tiles * (int)gridDim.z;
-  const int bid = (int)blockIdx.z * (int)gridDim.x + (int)blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int work = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int slab = work / tiles;
-  const int tile = work - slab * tiles;
-  int tm, tn;
-  {
-    const int G = p.group_n, per_group = p.tiles_m * G;
-    const int gi = tile / per_group;
-    const int full = p.tiles_n / G;
-    if (gi < full) {
-      const int r = tile - gi * per_group;
-      tm = r / G;
-      tn = gi * G + (r - tm * G);
-    } else {
-      const int gsz = p.tiles_n - full * G;
-      const int r = tile - full * per_group;
-      tm = r / gsz;
-      tn = full * G + (r - tm * gsz);
-    }
-  }
+  // work item (K slab, tile) in the XCD-aware slab-major order, the tile in the grouped order (gemm_tiles.hpp: xcd_run,
+  // slab_work, tile_coords)
+  int slab, tile, tm, tn;
+  slab_work(p, slab, tile);
+  tile_coords(p, tile, tm, tn);
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
   const int64_t kbeg = (int64_t)slab * p.k_chunk;
   const int64_t kend = (kbeg + p.k_chunk < p.K) ? kbeg + p.k_chunk : p.K;
@@ -64,6 +45,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // the atomics still go to the item's own place: separates the fill's miss path from the loop's own cost
   const bool diag_l2 = (p.epilogue & (1 << 23)) != 0;
   const int64_t lm0 = diag_l2 ? 0 : m0, ln0 = diag_l2 ? 0 : n0, lk0 = diag_l2 ? 0 : kbeg;
+  // Windows based at the item's FIRST ELEMENT — (row lm0, k lk0) of a k-contiguous operand, (k-row lk0, column lm0) of a
+  // k-major one — not at the start of that row as operand_window bases them: steps then ride in the scalar offset alone.
   const char* a_base;
   const char* b_base;
   int64_t a_bytes, b_bytes;
@@ -71,34 +54,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   else { a_base = (const char*)p.A + lk0 * lda_b + lm0 * 2; a_bytes = (kend - kbeg) * lda_b - lm0 * 2; }
   if constexpr (!B_KM) { b_base = (const char*)p.B + ln0 * ldb_b + lk0 * 2; b_bytes = (p.N - ln0) * ldb_b - lk0 * 2; }
   else { b_base = (const char*)p.B + lk0 * ldb_b + ln0 * 2; b_bytes = (kend - kbeg) * ldb_b - ln0 * 2; }
-  const unsigned a_rec = (unsigned)(a_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : a_bytes);
-  const unsigned b_rec = (unsigned)(b_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : b_bytes);
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, a_rec, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)b_base, 0, b_rec, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsA = clamped_rsrc(a_base, a_bytes), rsB = clamped_rsrc(b_base, b_bytes);
 
-  // The wave's 8 LDS-DMA pieces of a step: pieces 0-3 of A, 4-7 of B (piece index inside the operand = wave + 4 i); the
-  // per-lane offsets do not depend on the step, which rides in the instruction's scalar offset (gemm_bf16_w4p).
+  // The wave's 8 LDS-DMA pieces of a step: pieces 0-3 of A, 4-7 of B; per-lane offsets fixed for the launch (w4_piece_voff).
   // A k-major operand past its last k-row (a slab's tail) and a k-contiguous one past row M read as zeros through the
   // descriptor; a k-major row's columns past the tile (m0 + 256 > M) belong to the next k-row and are masked by the atomics'
   // row test in the epilogue.
   unsigned voffA[4], voffB[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int piece = wave + 4 * i;
-    if constexpr (!A_KM) {
-      const int row = piece * 16 + (lane >> 2);
-      voffA[i] = (unsigned)(row * lda_b + (((lane & 3) ^ swz_h(row)) * 16));
-    } else {
-      const int k = piece * 2 + (lane >> 5), c16 = lane & 31;
-      voffA[i] = (unsigned)(k * lda_b + ((((c16 >> 1) ^ swz_km(k)) * 16 + (c16 & 1) * 8) * 2));
-    }
-    if constexpr (!B_KM) {
-      const int row = piece * 16 + (lane >> 2);
-      voffB[i] = (unsigned)(row * ldb_b + (((lane & 3) ^ swz_h(row)) * 16));
-    } else {
-      const int k = piece * 2 + (lane >> 5), c16 = lane & 31;
-      voffB[i] = (unsigned)(k * ldb_b + ((((c16 >> 1) ^ swz_km(k)) * 16 + (c16 & 1) * 8) * 2));
-    }
+    voffA[i] = w4_piece_voff<A_KM>(wave + 4 * i, lane, lda_b);
+    voffB[i] = w4_piece_voff<B_KM>(wave + 4 * i, lane, ldb_b);
   }
   auto soff_a = [&](int hs) -> int { return A_KM ? (int)((int64_t)hs * 32 * lda_b) : hs * 64; };
   auto soff_b = [&](int hs) -> int { return B_KM ? (int)((int64_t)hs * 32 * ldb_b) : hs * 64; };

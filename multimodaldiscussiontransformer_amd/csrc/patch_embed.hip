@@ -28,9 +28,7 @@ __global__ __launch_bounds__(256) void vit_patch_embed_kernel(PatchParams p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
-  const int nwg = p.tiles_m * p.tiles_n, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int tile = xcd_run(p.tiles_m * p.tiles_n, blockIdx.x);   // XCD-aware order of the row-major tile grid
   const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
   const int64_t m0 = (int64_t)tm * T_BM, n0 = (int64_t)tn * T_BN;
   const int nk = p.K / T_BK;
@@ -47,9 +45,7 @@ __global__ __launch_bounds__(256) void vit_patch_embed_kernel(PatchParams p) {
   const int a_swz = swz_kc(arow);
 
   const int64_t ldw_b = p.ldw * 2;
-  const char* b_base = (const char*)p.w + n0 * ldw_b;
-  const int64_t b_bytes = ((int64_t)p.D - n0) * ldw_b;
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)b_base, 0, (unsigned)(b_bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : b_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsB = clamped_rsrc((const char*)p.w + n0 * ldw_b, ((int64_t)p.D - n0) * ldw_b);
 
   f32x4 acc[4][4];
 #pragma unroll

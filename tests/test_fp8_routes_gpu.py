@@ -88,6 +88,9 @@ def _cases():
         add(PP, False, epi, 300, 256, 768, families=["integer"])
         add(PP, False, epi, 300, 256, 256, families=["random"])
     add(PP, False, "g_mulaux_colsum", PERSIST, 768, 768, families=["integer"])
+    # the halved tile order (group_n = tiles_n / 2 on 256 CUs; one byte per element): B panels 18 x 256 x 768 = 3.54 MB > 3.5 MB,
+    # one half 1.77 MB <= 2.5 MB, 57 x 18 = 1026 tiles >= 4 x 256.  Last in the table: a case's seed is its index
+    add(W4, False, "plain", 57 * 256, 4608, 768)
     return c
 
 

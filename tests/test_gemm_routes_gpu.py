@@ -40,6 +40,13 @@ ROUTES = {
     "splitk_pp256": ({"MDT_GEMM_ROUTE": "pp256"}, "pp256", bf16, 512, 512, 2013, True, 8),
     "splitk_w4s": ({"MDT_GEMM_ROUTE": "w4s"}, "w4s", bf16, 512, 512, 2013, True, 8),
     "asum_fallback": ({"MDT_GEMM_ROUTE": "tile128"}, "tile128", bf16, 512, 512, 2013, True, 8),
+    # 1 x 3 tiles, more column than row tiles: split-K walks them column-major (group_n = 1); slabs of 512 / 512 / 512 / 477 k
+    "splitk_pp256_colmajor": ({"MDT_GEMM_ROUTE": "pp256"}, "pp256", bf16, 256, 768, 2013, True, 8),
+    "splitk_w4s_colmajor": ({"MDT_GEMM_ROUTE": "w4s"}, "w4s", bf16, 256, 768, 2013, True, 8),
+    # the halved order (group_n = tiles_n / 2), the smallest shape that gets it on 256 CUs: B panels 12 x 256 x 768 x 2 = 4.7 MB
+    # > 3.5 MB, one half 2.36 MB <= 2.5 MB, 86 x 12 = 1032 tiles >= 4 x 256
+    "pp_halves": ({}, "w4p", bf16, 86 * 256, 3072, 768, False, 8),
+    "pp_halves_8wave": ({"MDT_GEMM_ROUTE": "pp256p"}, "pp256p", bf16, 86 * 256, 3072, 768, False, 8),
 }
 
 E = R                         # the flag constants
@@ -83,8 +90,14 @@ MATRIX = (
     + [("splitk_pp256", e, f32, None, 4) for e in ("atomic", "atomic_asum")]
     + [("splitk_w4s", e, f32, None, 4) for e in ("atomic", "atomic_asum")]
     + [("asum_fallback", "atomic_asum", f32, None, 4)]
+    + [("splitk_pp256_colmajor", e, f32, None, 4) for e in ("atomic", "atomic_asum")]
+    + [("splitk_w4s_colmajor", e, f32, None, 4) for e in ("atomic", "atomic_asum")]
+    # alpha follows the row's index: the fc1 row sits where it gets 0.75.  At K = 768 and alpha = -1.25 the REFERENCE's own bound
+    # for the GELU output is looser than assert_within accepts (median bound / |ref| 8.5e-3 > 2^-7, whatever kernel ran).
+    + [("pp_halves", "plain", bf16, None, 1), ("pp_halves_8wave", "fc1_nodrop", bf16, None, 1), ("pp_halves", "dense", bf16, None, 1)]
 )
 ALPHAS = (1.0, 0.75, -1.25)
+assert ALPHAS[MATRIX.index(("pp_halves_8wave", "fc1_nodrop", bf16, None, 1)) % len(ALPHAS)] == 0.75
 SUM_ALPHAS = (1.0, -0.5, 2.0)  # column-sum cases: powers of two keep the integer results on a granule whose sums stay exact
 
 
