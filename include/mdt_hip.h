@@ -34,6 +34,7 @@ typedef enum { MDT_F32 = 0, MDT_BF16 = 1 } mdt_dtype;
 typedef enum {
   MDT_OK = 0,
   MDT_ERR_ARG = -1,          /* shape / alignment / null-pointer contract violated */
+  MDT_ERR_INVALID = MDT_ERR_ARG, /* the same status: what the ordered entry points return for a workspace that is too small */
   MDT_ERR_UNSUPPORTED = -2,  /* valid request this build has no kernel for */
   MDT_ERR_LAUNCH = -3        /* hipLaunch / hipMemsetAsync reported an error */
 } mdt_status;
@@ -424,6 +425,73 @@ int mdt_adam_step_guarded(void* stream, int dtype, int64_t n, void* param, float
 int mdt_adam_step_multi_guarded(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
                                 const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2,
                                 float eps, float weight_decay, int step, const mdt_adam_guard* guard);
+
+/* ------------------------------------------------------------------ ordered (bit-reproducible) gradient reductions
+ * The backward pass accumulates gradients with fp32 atomics (MDT_EPI_ATOMIC / _ASUM / _COLSUM, mdt_colsum, mdt_layernorm_bwd,
+ * mdt_row_scatter_add_f32, the structural-bias gradient of mdt_attention_bwd): two runs of one step agree to ~1e-7, not bit for
+ * bit.  The entry points below compute the same gradients with plain stores of per-workgroup partials into a CALLER-OWNED
+ * workspace and one fixed-order reducer, so their results are functions of the operands alone (and of the library build) — not
+ * of timing, of which workgroup ran first, or of other work on the device.  They are NOT bit-equal to the atomic forms (another
+ * summation order).  Each ..._workspace_bytes() is what the call with the same arguments needs; a smaller (or NULL) workspace is
+ * MDT_ERR_INVALID before anything is launched.  Workspaces must be 16-byte aligned and need no initialisation.
+ *
+ * mdt_sum_slices_f32 — THE reducer: out[r][c] = (accumulate ? out[r][c] : 0) + (((ws[0][r][c] + ws[1][r][c]) + ws[2][r][c]) + ...)
+ *   with ws[z][r][c] = ws[z * slice_stride + r * ld_ws + c]: the slices are added left to right in fp32, one rounding per add (there
+ *   is no multiply, hence no FMA), the old value of out joins last.  Any row strides >= cols. */
+int mdt_sum_slices_f32(void* stream, int64_t rows, int64_t cols, int slices, const float* ws, int64_t ld_ws, int64_t slice_stride,
+                       float* out, int64_t ldo, int accumulate);
+/* The weight-gradient GEMM: C[M,N] (fp32, row stride ldc) += alpha * op(A) @ op(B), operands as mdt_gemm.  One launch computes
+ * the K slabs (grid z = slab); slab z stores alpha * its fp32 partial tile to slice z of the workspace ([slabs][M][N]) and
+ * mdt_sum_slices_f32 adds the slices into C in ascending z.  The 4-wave weight-gradient kernel ("w4s") runs under the preconditions
+ * it has in mdt_gemm, the 128 x 128 tile kernel ("tile128") takes the other tile-aligned bf16 launches and the any-shape kernel
+ * ("generic") the rest, fp32 operands included (mdt_last_route()).  The slab count the planner chooses (<= split_k) stays inside;
+ * the result depends on it, so it is reproducible for one (shape, strides, alignment, split_k).  No bias sum rides here. */
+size_t mdt_gemm_splitk_ordered_workspace_bytes(int64_t M, int64_t N, int split_k);
+int mdt_gemm_splitk_ordered(void* stream, int dtype, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K,
+                            const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float alpha,
+                            int split_k, void* workspace, size_t workspace_bytes);
+/* mdt_colsum in a fixed order: out[n] += sum_m w[m] * X[m, n].  Rows are cut into blocks of 256; inside a block, row lane j of 4
+ * adds the terms of rows j, j + 4, ... in ascending order (each product w * x rounded first) and the block's partial is
+ * ((lane 0 + lane 1) + lane 2) + lane 3; mdt_sum_slices_f32 then adds the blocks in ascending order, the old out last. */
+size_t mdt_colsum_ordered_workspace_bytes(int64_t M, int64_t N);
+int mdt_colsum_ordered(void* stream, int dtype, int64_t M, int64_t N, const void* X, int64_t ldx, float* out,
+                       const int32_t* row_weight, void* workspace, size_t workspace_bytes);
+/* mdt_layernorm_bwd with the per-workgroup partials of dgamma, dbeta and the column sums stored to the workspace and added by
+ * mdt_sum_slices_f32 in ascending workgroup order (the old dgamma / dbeta / colsum joins last).  dx and dxd are bit-identical to
+ * mdt_layernorm_bwd's; the number of workgroups is a function of `rows` alone (MDT_LN_BWD_WGS is not read).  Runs the generic
+ * kernel ("ln_generic") for every D. */
+size_t mdt_layernorm_bwd_ordered_workspace_bytes(int64_t rows, int D);
+int mdt_layernorm_bwd_ordered(void* stream, int dtype, int64_t rows, int D, const void* dy, int64_t lddy,
+                              const void* x, int64_t ldx, const void* gamma, const float* mean, const float* rstd,
+                              const void* add, int64_t ldadd, void* dx, int64_t lddx, float* dgamma, float* dbeta,
+                              void* dxd, int64_t lddxd, float drop_p, uint64_t drop_seed, float* colsum,
+                              void* workspace, size_t workspace_bytes);
+/* The scatter-add of mdt_row_scatter_add_f32 in a fixed order, from segments in CSR form: segment s adds the source rows
+ * order[seg_off[s]] .. order[seg_off[s + 1] - 1] (source row r is src row r * s_stride + s_off, T = bf16 or fp32, converted to fp32)
+ * to table row seg_row[s] (seg_row < 0: skipped; every other seg_row at most once).  TWO-LEVEL ORDER: the segment's sources are
+ * taken in chunks of 64 in the order listed; a chunk is summed left to right, the chunk sums are added left to right, and the
+ * table's old value joins last:  table[seg_row[s]] = table[seg_row[s]] + ((chunk 0 + chunk 1) + chunk 2 ...).  An empty segment
+ * leaves its row untouched.  The CSR is the caller's (a stable sort of the index vector): the result is the same for any
+ * construction that lists a segment's sources in ascending source-row order.  No workspace: one thread owns one table element. */
+int mdt_row_segment_sum_f32(void* stream, int dtype, int nseg, int D, float* table, int64_t ldt, const int32_t* seg_row,
+                            const int32_t* seg_off, const int32_t* order, const void* src, int64_t lds, int64_t s_stride,
+                            int64_t s_off);
+/* Structural-bias gradient from a dense dS f32[nseq,H,S,S] (what mdt_attention_bwd stores through d_dense_bias, launched with
+ * d_sp_table = d_virt = NULL): d_sp_table[i][h] += sum of dS[s,h,q,key] over q >= 1, key >= 1 with spatial_pos[s,q-1,key-1] == i
+ * (row 0, the padding index, receives nothing); d_virt[h] += sum over q == 0 or key == 0.  One workgroup of T threads per
+ * (sequence, head): thread t adds elements t, t + T, ... of the row-major S x S matrix in that order into a private histogram;
+ * the T histograms are folded by halving (t += t + T / 2, then + T / 4, ... + 1); mdt_sum_slices_f32 then adds the sequences in
+ * ascending order, the old value last.  T is a function of num_spatial alone — 256 up to 95 table rows, 128 up to 191, 64 up to
+ * 383, 32 up to 767 — so that the (num_spatial + 1) x T floats of histogram stay within 96 KiB of the 160 KiB of LDS a workgroup
+ * has; MDT_ERR_UNSUPPORTED for more rows.  Either output may be NULL. */
+size_t mdt_attn_bias_grad_ordered_workspace_bytes(int nseq, int H, int num_spatial);
+int mdt_attn_bias_grad_ordered(void* stream, int nseq, int S, int H, int num_spatial, const float* dS,
+                               const int32_t* spatial_pos, float* d_sp_table, float* d_virt, void* workspace,
+                               size_t workspace_bytes);
+/* Host-side count of the launches that accumulate with float atomics into caller memory (every site named above adds one per
+ * call); reset != 0 also puts it back to zero.  Nothing inside a kernel is inspected: a step that ran in ordered mode leaves it
+ * unchanged. */
+int64_t mdt_float_atomic_launches(int reset);
 
 /* ------------------------------------------------------------------ packer (host, C++)
  * Native replacement of preprocess_item + collator (data/pyg_datasets/pre_processing.py:18-69,

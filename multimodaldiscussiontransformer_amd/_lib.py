@@ -68,6 +68,18 @@ _SIGS = {
     "mdt_row_axpby": ([_vp, _i, _i64, _i, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _f,
                        _vp, _i64, _vp, _i64, _i64, _i64, _f, _i], _i),
     "mdt_row_scatter_add_f32": ([_vp, _i, _i64, _i, _vp, _i64, _vp, _vp, _i64, _i64, _i64], _i),
+    "mdt_sum_slices_f32": ([_vp, _i64, _i64, _i, _vp, _i64, _i64, _vp, _i64, _i], _i),
+    "mdt_gemm_splitk_ordered_workspace_bytes": ([_i64, _i64, _i], C.c_size_t),
+    "mdt_gemm_splitk_ordered": ([_vp, _i, _i, _i, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _i, _vp, C.c_size_t], _i),
+    "mdt_colsum_ordered_workspace_bytes": ([_i64, _i64], C.c_size_t),
+    "mdt_colsum_ordered": ([_vp, _i, _i64, _i64, _vp, _i64, _vp, _vp, _vp, C.c_size_t], _i),
+    "mdt_layernorm_bwd_ordered_workspace_bytes": ([_i64, _i], C.c_size_t),
+    "mdt_layernorm_bwd_ordered": ([_vp, _i, _i64, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
+                                   _vp, _i64, _f, C.c_uint64, _vp, _vp, C.c_size_t], _i),
+    "mdt_row_segment_sum_f32": ([_vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64], _i),
+    "mdt_attn_bias_grad_ordered_workspace_bytes": ([_i, _i, _i], C.c_size_t),
+    "mdt_attn_bias_grad_ordered": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t], _i),
+    "mdt_float_atomic_launches": ([_i], _i64),
     "mdt_bert_embed_sum": ([_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i64, _i64], _i),
     "mdt_bert_embed_rows": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64], _i),
     "mdt_bert_embed_ln_rows": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _i64, _vp, _i64, _vp, _vp], _i),

@@ -672,6 +672,7 @@ extern "C" int mdt_attention_bwd(void* stream, const mdt_attn_bwd_args* a) {
   p.drop = make_drop(a->f.drop_p, a->f.drop_seed);
   p.dout = a->dout; p.ld_dout = a->ld_dout; p.dqkv = a->dqkv; p.ld_dqkv = a->ld_dqkv;
   p.d_dense_bias = a->d_dense_bias; p.d_sp_table = a->d_sp_table; p.d_virt = a->d_virt;
+  if (p.d_sp_table || p.d_virt) note_float_atomic_launch();     // the structural-bias gradient (attn_bias_grad_add / _flush)
   return dispatch<true>((hipStream_t)stream, p);
 }
 

@@ -37,6 +37,12 @@ void set_error(const char* fmt, ...);
     return MDT_ERR_UNSUPPORTED;           \
   } while (0)
 int check_launch(const char* what);
+// Called by every host function that launches a kernel accumulating with float atomics into caller memory
+// (mdt_float_atomic_launches reports the count; host code only, nothing inside a kernel is counted).
+void note_float_atomic_launch();
+// The fixed-order reducer every ordered entry point ends in (ordered.hip, mdt_sum_slices_f32).
+int sum_slices_f32(hipStream_t st, int64_t rows, int64_t cols, int slices, const float* ws, int64_t ld_ws, int64_t slice_stride,
+                   float* out, int64_t ldo, int accumulate);
 
 // Routes: the kernel a GEMM / attention-backward launch takes (gemm.hip plan_gemm, attention_v2.hip attn_bwd_route).
 // MDT_GEMM_ROUTE / MDT_ATTN_BWD name one to force it; mdt_last_route() reports the route of the last launch.

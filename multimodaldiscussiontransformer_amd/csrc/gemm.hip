@@ -26,7 +26,7 @@ namespace mdt {
 
 // ------------------------------------------------------------------ generic kernel
 // 64x64x16 tiles, 4 waves (2x2 of 32x32), operands converted to fp32 in LDS.
-template <typename TIn, typename TOut, bool TA, bool TB>
+template <typename TIn, typename TOut, bool TA, bool TB, bool ORD = false>   // ORD: ordered split-K (GemmParams::slice_stride)
 __global__ __launch_bounds__(256) void gemm_generic_kernel(GemmParams p) {
   constexpr int BM = 64, BN = 64, BK = 16, LD = 68;
   __shared__ float As[BK][LD];
@@ -38,6 +38,7 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(GemmParams p) {
   const int64_t kend = (kbeg + p.k_chunk < p.K) ? kbeg + p.k_chunk : p.K;
   const TIn* A = (const TIn*)p.A;
   const TIn* B = (const TIn*)p.B;
+  if constexpr (ORD) p.C = (float*)p.C + (int64_t)blockIdx.z * p.slice_stride;
   f32x4 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -82,11 +83,11 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(GemmParams p) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        epilogue_store<TIn, TOut>(p, m0 + wr * 32 + i * 16 + (lane >> 4) * 4 + r,
+        epilogue_store<TIn, TOut, ORD>(p, m0 + wr * 32 + i * 16 + (lane >> 4) * 4 + r,
                                   n0 + wc * 32 + j * 16 + (lane & 15), acc[i][j][r]);
 }
 
-template <typename TOut, bool A_KM, bool B_KM>
+template <typename TOut, bool A_KM, bool B_KM, bool ORD = false>
 __global__ __launch_bounds__(256) void gemm_bf16_tile128(GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 stages x (A 16K + B 16K)
   const int tid = threadIdx.x;
@@ -100,6 +101,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_tile128(GemmParams p) {
   const int64_t kbeg = (int64_t)blockIdx.z * p.k_chunk;
   const int64_t kend = (kbeg + p.k_chunk < p.K) ? kbeg + p.k_chunk : p.K;
   const int nk = (int)((kend - kbeg + T_BK - 1) / T_BK);
+  if constexpr (ORD) p.C = (float*)p.C + (int64_t)blockIdx.z * p.slice_stride;
 
   const int64_t lda_b = p.lda * 2, ldb_b = p.ldb * 2;
   const Window wa = operand_window<A_KM>(p.A, lda_b, m0, p.M, kbeg, kend), wb = operand_window<B_KM>(p.B, ldb_b, n0, p.N, kbeg, kend);
@@ -142,7 +144,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_tile128(GemmParams p) {
         for (int j = 0; j < 4; ++j) acc[i][j] = mfma_bf16(a[i], b[j], acc[i][j]);
     }
   }
-  tile_epilogue<TOut>(p, acc, smem, wave, lane, m0 + wr * 64, n0 + wc * 64);
+  tile_epilogue<TOut, ORD>(p, acc, smem, wave, lane, m0 + wr * 64, n0 + wc * 64);
 }
 
 // ------------------------------------------------------------------ bf16 256-row tiles, 8 waves
@@ -1009,7 +1011,11 @@ struct GemmPlan {
 // pp256p; without the walk the 4-wave split-K w4s for fp32 atomic weight gradients with slabs of at least 256, else pp256.
 // MDT_GEMM_ROUTE=<route> takes that route wherever its preconditions (ok() below) hold; forcing pp256p also walks tiles of
 // only PP_DIST steps (K >= 128: stress runs, tools/gemm_stress.py).
-static GemmPlan plan_gemm(const GemmParams& p, int dtype, int out_dtype, int ta, int tb, int n_cus) {
+// `ordered` (mdt_gemm_splitk_ordered; p.epilogue = MDT_EPI_ATOMIC, fp32 C): the kernels with an ordered form only — w4s wherever
+// its preconditions hold, tile128 for the other tile-aligned launches, generic for the rest — whatever the tile count.  There
+// the ragged last slab of w4s is counted in whole 64-deep K-tiles (at least four: 193 rows; a k-major operand reads zeros past
+// its last k-row, a k-contiguous one has K % 64 == 0), where mdt_gemm asks for 256 rows.
+static GemmPlan plan_gemm(const GemmParams& p, int dtype, int out_dtype, int ta, int tb, int n_cus, bool ordered = false) {
   const Switches& sw = switches();
   const int64_t M = p.M, N = p.N, K = p.K;
   const int epi = p.epilogue;
@@ -1052,7 +1058,8 @@ static GemmPlan plan_gemm(const GemmParams& p, int dtype, int out_dtype, int ta,
         return persist(16) && nhs >= W4_NEXPL + 2 && !queue && !(epi & (1 << 24));
       case GemmRoute::w4s:           // fp32-accumulating split-K launches with at least four 64-deep K-tiles per slab
         return pp && out_dtype == MDT_F32 && !sw.gemm_stamp && (epi & MDT_EPI_ATOMIC) &&
-               !(epi & ((1 << 20) - 1) & ~(MDT_EPI_ATOMIC | MDT_EPI_ASUM)) && chunk >= 256 && K - (int64_t)(split - 1) * chunk >= 256;
+               !(epi & ((1 << 20) - 1) & ~(MDT_EPI_ATOMIC | MDT_EPI_ASUM)) && chunk >= 256 &&
+               (ordered ? (K - (int64_t)(split - 1) * chunk + T_BK - 1) / T_BK >= 4 : K - (int64_t)(split - 1) * chunk >= 256);
       default: return false;
     }
   };
@@ -1070,6 +1077,10 @@ static GemmPlan plan_gemm(const GemmParams& p, int dtype, int out_dtype, int ta,
   } else if (m256 && t256 >= 256) r = GemmRoute::tile256x128;
   else r = GemmRoute::tile128;
   if (sw.gemm_route != GemmRoute::none && ok(sw.gemm_route)) r = sw.gemm_route;
+  if (ordered) {
+    const GemmRoute f = sw.gemm_route;      // a forced route is honoured among the three
+    r = f == GemmRoute::generic || !fast ? GemmRoute::generic : ok(GemmRoute::w4s) && f != GemmRoute::tile128 ? GemmRoute::w4s : GemmRoute::tile128;
+  }
 
   GemmPlan pl{};
   pl.route = r;
@@ -1229,6 +1240,7 @@ extern "C" int mdt_gemm(void* stream, int dtype, int out_dtype, int trans_a, int
   // (MDT_EPI_ATOMIC already implies an fp32 C; said again because the kernels compute the sums in their fp32-output form only)
   MDT_CHECK_ARG(!(epilogue & MDT_EPI_ASUM) || (colsum && trans_a && (epilogue & MDT_EPI_ATOMIC) && !(epilogue & MDT_EPI_COLSUM) && dtype == MDT_BF16 && out_dtype == MDT_F32),
                 "mdt_gemm: MDT_EPI_ASUM needs bf16 operands, an fp32 C, trans_a = 1, MDT_EPI_ATOMIC, a colsum buffer and no MDT_EPI_COLSUM");
+  if (epilogue & (MDT_EPI_ATOMIC | MDT_EPI_ASUM | MDT_EPI_COLSUM)) note_float_atomic_launch();
   const GemmPlan pl = plan_gemm(p, dtype, out_dtype, trans_a, trans_b, num_cus());
   p.k_chunk = pl.k_chunk; p.split_k = pl.split_k; p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.group_n = pl.group_n;
   if (pl.strip_asum && (p.epilogue & MDT_EPI_ASUM)) {      // the row sums of the stored A ([K, M]) by the column-sum kernel
@@ -1272,6 +1284,52 @@ extern "C" int mdt_gemm(void* stream, int dtype, int out_dtype, int trans_a, int
   return e;
 }
 
+// Ordered split-K: the slab count never exceeds the split asked for (plan_gemm rounds the slab length UP), so that many
+// M x N fp32 slices always suffice.
+extern "C" size_t mdt_gemm_splitk_ordered_workspace_bytes(int64_t M, int64_t N, int split_k) {
+  if (M <= 0 || N <= 0) return 0;
+  return (size_t)(split_k < 1 ? 1 : split_k) * (size_t)M * (size_t)N * sizeof(float);
+}
+
+extern "C" int mdt_gemm_splitk_ordered(void* stream, int dtype, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K,
+                                       const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc,
+                                       float alpha, int split_k, void* workspace, size_t workspace_bytes) {
+  MDT_CHECK_ARG(dtype == MDT_F32 || dtype == MDT_BF16, "mdt_gemm_splitk_ordered: bad dtype %d", dtype);
+  MDT_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "mdt_gemm_splitk_ordered: negative shape");
+  if (M == 0 || N == 0) return MDT_OK;
+  MDT_CHECK_ARG(A && B && C && workspace, "mdt_gemm_splitk_ordered: null operand / workspace");
+  MDT_CHECK_ARG(ldc >= N && ((uintptr_t)workspace & 15) == 0, "mdt_gemm_splitk_ordered: ldc < N or workspace not 16-byte aligned");
+  if (split_k < 1) split_k = 1;
+  hipStream_t st = (hipStream_t)stream;
+  GemmParams p;
+  p.M = M; p.N = N; p.K = K; p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = workspace; p.ldc = N;
+  p.epilogue = MDT_EPI_ATOMIC;        // for the planner only: the w4s preconditions are those of the atomic split-K launch
+  p.alpha = alpha; p.bias = nullptr; p.residual = nullptr; p.ldr = 0; p.aux = nullptr; p.ldaux = 0; p.split_k = split_k;
+  p.drop = make_drop(0.f, 0);
+  p.colsum = nullptr; p.stamps = nullptr; p.tile_queue = nullptr; p.alpha_dev = p.alpha_dev2 = nullptr;
+  const GemmPlan pl = plan_gemm(p, dtype, MDT_F32, trans_a, trans_b, num_cus(), true);
+  p.epilogue = 0;
+  p.k_chunk = pl.k_chunk; p.split_k = pl.split_k; p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.group_n = pl.group_n;
+  p.slice_stride = M * N;
+  const size_t need = (size_t)pl.split_k * (size_t)M * (size_t)N * sizeof(float);
+  MDT_CHECK_ARG(workspace_bytes >= need, "mdt_gemm_splitk_ordered: workspace of %zu bytes, %zu needed (%d slabs of %lld x %lld fp32)",
+                workspace_bytes, need, pl.split_k, (long long)M, (long long)N);
+  int e;
+  if (pl.route == GemmRoute::w4s) e = launch_w4s(st, p, pl.grid, trans_a, trans_b);
+  else if (pl.route == GemmRoute::tile128)
+    e = with_layout(trans_a, trans_b, [&](auto a_km, auto b_km) -> int {
+      return launch_route<gemm_bf16_tile128<float, decltype(a_km)::value, decltype(b_km)::value, true>>("tile128", pl.grid, 256, 4 * T_TILE_BYTES, st, p);
+    });
+  else
+    e = with_layout(trans_a, trans_b, [&](auto ta, auto tb) -> int {
+      constexpr bool TA = decltype(ta)::value, TB = decltype(tb)::value;
+      if (dtype == MDT_F32) return launch_route<gemm_generic_kernel<float, float, TA, TB, true>>("generic", pl.grid, 256, 0, st, p);
+      return launch_route<gemm_generic_kernel<bf16_t, float, TA, TB, true>>("generic", pl.grid, 256, 0, st, p);
+    });
+  if (e) return e;
+  return sum_slices_f32(st, M, N, pl.split_k, (const float*)workspace, N, M * N, C, ldc, 1);
+}
+
 extern "C" size_t mdt_gemm_tile_queue_bytes(void) { return (size_t)512 * 16 * sizeof(int); }
 
 extern "C" int mdt_gemm_set_tile_queue(void* zeroed_device_buffer, size_t bytes) {
@@ -1313,6 +1371,7 @@ extern "C" int mdt_gemm_fp8_q8(void* stream, int a_format, int64_t M, int64_t N,
                   (!aux || (ldaux % 8 == 0 && ((uintptr_t)aux & 15) == 0)) && lda * 256 < (1ll << 31) && ldb * 256 < (1ll << 31);
   if (!ok) MDT_UNSUPPORTED("mdt_gemm_fp8: shape M=%lld N=%lld K=%lld (needs N %% 256 == 0, K %% 64 == 0, K >= 256, 16-byte rows)",
                            (long long)M, (long long)N, (long long)K);
+  if (epilogue & MDT_EPI_COLSUM) note_float_atomic_launch();
   GemmParams p;
   p.M = M; p.N = N; p.K = K; p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc;
   p.epilogue = epilogue; p.alpha = 1.0f; p.alpha_dev = inv_scale_a; p.alpha_dev2 = inv_scale_b;
@@ -1343,6 +1402,7 @@ extern "C" int mdt_colsum(void* stream, int dtype, int64_t M, int64_t N, const v
   MDT_CHECK_ARG(dtype == MDT_F32 || dtype == MDT_BF16, "mdt_colsum: dtype %d", dtype);
   if (M == 0 || N == 0) return MDT_OK;           // nothing to add (an empty X has no address)
   MDT_CHECK_ARG(X && out, "mdt_colsum: null pointer");
+  note_float_atomic_launch();
   hipStream_t st = (hipStream_t)stream;
   const int vn = dtype == MDT_BF16 ? 8 : 4;
   if (N % vn == 0 && ldx % vn == 0 && ((uintptr_t)X & 15) == 0) {

@@ -27,9 +27,12 @@ struct GemmParams {
   // 8-bit kernel only (gemm_f8.hip): the output ALSO leaves as fp8 for the next 8-bit GEMM — q8_out u8[M, N] = saturate(fmt,
   // bf16(out) * *q8_scale), *q8_amax = max(*q8_amax, max |bf16(out)|): exactly what mdt_fp8_quantize would make of the bf16 output
   void* q8_out = nullptr; int64_t ld_q8 = 0; const float* q8_scale = nullptr; float* q8_amax = nullptr; int q8_fmt = 0;
+  // ordered split-K (mdt_gemm_splitk_ordered, the ORD instantiations of the kernels): C is the workspace and K slab z stores its
+  // alpha-scaled fp32 partial tile with plain stores into slice z, slice_stride floats after slice z - 1
+  int64_t slice_stride = 0;
 };
 
-template <typename TIn, typename TOut>
+template <typename TIn, typename TOut, bool ORD = false>
 __device__ __forceinline__ void epilogue_store(const GemmParams& p, int64_t row, int64_t col, float v) {
   if (row >= p.M || col >= p.N) return;
   v *= p.alpha;
@@ -53,6 +56,7 @@ __device__ __forceinline__ void epilogue_store(const GemmParams& p, int64_t row,
   if (p.epilogue & MDT_EPI_COLSUM) atomicAdd(p.colsum + col, v);
   TOut* c = (TOut*)p.C + row * p.ldc + col;
   if constexpr (sizeof(TOut) == 4) {
+    if constexpr (ORD) { *c = v; return; }      // the slab's own slice (the kernel moved p.C there)
     if (p.epilogue & MDT_EPI_ATOMIC) { atomicAdd((float*)c, v); return; }
   }
   if (p.epilogue & MDT_EPI_ACCUM) v += to_f32(*c);
@@ -265,7 +269,7 @@ __device__ __forceinline__ bf16x8 load_frag_h(const char* lds_tile, int rc_base,
 // every global access is a full 16-byte vector and a wave instruction covers whole 128-B
 // (bf16) row segments — bias / GELU / residual / pre-activation traffic is coalesced too.
 // Split-K weight gradients leave with one 256-byte contiguous atomic instruction per row.
-template <typename TOut>
+template <typename TOut, bool ORD = false>
 __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[4][4], char* smem, int wave, int lane,
                                               int64_t m0w, int64_t n0w) {
   __syncthreads();  // every wave is done reading the last staged tile
@@ -278,6 +282,14 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[
       for (int r = 0; r < 4; ++r) ws[(i * 16 + (lane >> 4) * 4 + r) * 64 + j * 16 + (lane & 15)] = acc[i][j][r];
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   const int ep = p.epilogue;
+  if constexpr (ORD) {         // ordered split-K: the same walk with a store where the atomic is, into the slab's own slice
+    float* c = (float*)p.C + n0w + lane;
+    for (int row = 0; row < 64; ++row) {
+      const int64_t gr = m0w + row;
+      if (gr < p.M) c[gr * p.ldc] = p.alpha * ws[row * 64 + lane];
+    }
+    return;
+  }
   if constexpr (sizeof(TOut) == 4) {
     if (ep & MDT_EPI_ATOMIC) {
       if (ep & (1 << 20)) return;                 // diagnostic (MDT_GEMM_DIAG=1): no output — what the atomics' tail costs a launch

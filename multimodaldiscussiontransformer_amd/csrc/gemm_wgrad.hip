@@ -20,7 +20,7 @@
 
 namespace mdt {
 
-template <bool A_KM, bool B_KM>
+template <bool A_KM, bool B_KM, bool ORD = false>   // ORD: ordered split-K — the slab's tile is STORED to its slice of the workspace
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_bf16_w4s(GemmParams p) {
   constexpr int PP_DIST = 4, PP_NB = 5;
   constexpr int BM = 256, BN = 256, A_BYTES = BM * 64;
@@ -39,6 +39,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int64_t kbeg = (int64_t)slab * p.k_chunk;
   const int64_t kend = (kbeg + p.k_chunk < p.K) ? kbeg + p.k_chunk : p.K;
   const int nhs = 2 * (int)((kend - kbeg + 63) / 64);          // 32-deep steps (even; the host guarantees >= 8)
+  if constexpr (ORD) p.C = (float*)p.C + (int64_t)slab * p.slice_stride;
 
   const int64_t lda_b = p.lda * 2, ldb_b = p.ldb * 2;
   // diagnostic (MDT_GEMM_DIAG=8): every work item LOADS the panels of item (slab 0, tile (0, 0)) — all fills hit L2 — while
@@ -193,12 +194,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) blk[i][j] = acc[(h >> 1) * 4 + i][(h & 1) * 4 + j];
-    tile_epilogue<float>(p, blk, smem, wave, lane, m0 + wr * 128 + (h >> 1) * 64, n0 + wc * 128 + (h & 1) * 64);
+    tile_epilogue<float, ORD>(p, blk, smem, wave, lane, m0 + wr * 128 + (h >> 1) * 64, n0 + wc * 128 + (h & 1) * 64);
   }
 }
 
 int launch_w4s(hipStream_t st, const GemmParams& p, dim3 grid, int ta, int tb) {
   const size_t lds = (size_t)5 * PP_STAGE;
+  if (p.slice_stride) {
+    if (ta && tb) return launch_route<gemm_bf16_w4s<true, true, true>>("w4s", grid, 256, lds, st, p);
+    if (!ta && tb) return launch_route<gemm_bf16_w4s<false, true, true>>("w4s", grid, 256, lds, st, p);
+    if (ta && !tb) return launch_route<gemm_bf16_w4s<true, false, true>>("w4s", grid, 256, lds, st, p);
+    return launch_route<gemm_bf16_w4s<false, false, true>>("w4s", grid, 256, lds, st, p);
+  }
   if (ta && tb) return launch_route<gemm_bf16_w4s<true, true>>("w4s", grid, 256, lds, st, p);
   if (!ta && tb) return launch_route<gemm_bf16_w4s<false, true>>("w4s", grid, 256, lds, st, p);
   if (ta && !tb) return launch_route<gemm_bf16_w4s<true, false>>("w4s", grid, 256, lds, st, p);

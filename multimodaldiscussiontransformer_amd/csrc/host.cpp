@@ -31,6 +31,9 @@ int check_launch(const char* what) {
   return MDT_OK;
 }
 
+static std::atomic<long long> g_float_atomic_launches{0};
+void note_float_atomic_launch() { g_float_atomic_launches.fetch_add(1, std::memory_order_relaxed); }
+
 static thread_local const char* g_route = "";
 void set_last_route(const char* route) { g_route = route; }
 
@@ -84,6 +87,10 @@ extern "C" void mdt_reload_env(void) { mdt::read_switches(); }
 extern "C" int mdt_abi_version(void) { return MDT_ABI_VERSION; }
 extern "C" const char* mdt_last_error_string(void) { return mdt::g_err; }
 extern "C" const char* mdt_last_route(void) { return mdt::g_route; }
+extern "C" int64_t mdt_float_atomic_launches(int reset) {
+  return reset ? mdt::g_float_atomic_launches.exchange(0, std::memory_order_relaxed)
+               : mdt::g_float_atomic_launches.load(std::memory_order_relaxed);
+}
 
 // --------------------------------------------------------------------------- packer
 // (up, down) hops through the lowest common ancestor → 21-bucket spatial index

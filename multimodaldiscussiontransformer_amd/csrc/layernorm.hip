@@ -295,8 +295,9 @@ __device__ __forceinline__ void ln_bwd_row(int64_t row, int D, int lane, const V
 
 // The workgroup's four waves combine their partials through ONE [4 waves][W = NV * 64 * VN] LDS buffer used three times
 // (dgamma, dbeta, column sums; 16 KiB at D = 768: the 48 KiB of three buffers held a CU to three workgroups) and issue one
-// float atomic per column.
-template <int NV, int VN, bool CS>
+// float atomic per column.  ORD (mdt_layernorm_bwd_ordered): the three pointers are [gridDim.x][D] workspace arrays and the
+// workgroup STORES its partial row there instead; mdt_sum_slices_f32 then adds the workgroups in ascending order.
+template <int NV, int VN, bool CS, bool ORD = false>
 __device__ __forceinline__ void ln_bwd_reduce_columns(const LnBwdPartials<NV, VN, CS>& part, float* red, int lane, int wave, int D,
                                                       float* dgamma, float* dbeta, float* colsum) {
   if (!dgamma && !dbeta && !colsum) return;
@@ -314,13 +315,17 @@ __device__ __forceinline__ void ln_bwd_reduce_columns(const LnBwdPartials<NV, VN
       }
     __syncthreads();
     if (dst)
-      for (int c = threadIdx.x; c < D; c += 256) atomicAdd(dst + c, red[c] + red[W + c] + red[2 * W + c] + red[3 * W + c]);
+      for (int c = threadIdx.x; c < D; c += 256) {
+        const float v = red[c] + red[W + c] + red[2 * W + c] + red[3 * W + c];
+        if constexpr (ORD) dst[(int64_t)blockIdx.x * D + c] = v;
+        else atomicAdd(dst + c, v);
+      }
   }
 }
 
 // The generic backward shell: each wave walks rows_per_wave consecutive rows (the next row's x / dy / residual-gradient
 // vectors are requested before the current row is reduced) through 64-bit pointers, vectors past D masked.
-template <typename T, int NV, bool TAIL, bool CS = TAIL, typename V = Vec<T>>   // TAIL: second (dropped) output and / or column sums; CS: the column sums
+template <typename T, int NV, bool TAIL, bool CS = TAIL, typename V = Vec<T>, bool ORD = false>   // TAIL: second (dropped) output and / or column sums; CS: the column sums
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(int64_t rows, int D, const T* __restrict__ dy, int64_t lddy,
                                                             const T* __restrict__ x, int64_t ldx,
                                                             const T* __restrict__ gamma, const float* __restrict__ mean,
@@ -381,7 +386,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(int64_t rows, int D,
 #pragma unroll
     for (int i = 0; i < NV; ++i) { xv[i] = xn[i]; gy[i] = gn[i]; av[i] = an[i]; }
   }
-  ln_bwd_reduce_columns(part, red, lane, wave, D, dgamma, dbeta, colsum);
+  ln_bwd_reduce_columns<NV, VN, CS, ORD>(part, red, lane, wave, D, dgamma, dbeta, colsum);
 }
 
 // The backward shell for bf16 rows of 256 * NV elements (768: every LayerNorm of mDT-base; 1024: mDT-large) with its addresses in SCALAR registers: a wave owns whole
@@ -610,6 +615,32 @@ static int ln_bwd_dispatch(hipStream_t st, int64_t rows, int D, const void* dy, 
   return MDT_OK;
 }
 
+// Ordered form: the generic kernel (its row arithmetic, so dx / dxd keep their bits) with the per-workgroup partials stored to
+// the workspace [3][workgroups][D] (dgamma, dbeta, column sums).  The grid is a function of `rows` alone.
+static void ln_bwd_ordered_grid(int64_t rows, int& rpw, unsigned& grid) {
+  rpw = (int)((rows + 2048 * 4 - 1) / (2048 * 4));
+  if (rpw < 4) rpw = 4;
+  grid = (unsigned)((rows + 4 * rpw - 1) / (4 * rpw));
+}
+
+template <typename T>
+static int ln_bwd_ordered_dispatch(hipStream_t st, int64_t rows, int D, const void* dy, int64_t lddy, const void* x, int64_t ldx,
+                                   const void* gamma, const float* mean, const float* rstd, const void* add, int64_t ldadd,
+                                   void* dx, int64_t lddx, float* pg, float* pb, void* dxd, int64_t lddxd, DropCfg drop, float* pc) {
+  int rpw;
+  unsigned grid;
+  ln_bwd_ordered_grid(rows, rpw, grid);
+  const bool ok = ln_row_layout<T>(D, [&](auto nv, auto vec) {
+    constexpr int NV = decltype(nv)::value;
+    ln_launch(layernorm_bwd_kernel<T, NV, true, true, decltype(vec), true>, grid, (size_t)(4 * NV * 64 * decltype(vec)::N * 4), st,
+              rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, pg, pb, rpw, dxd, lddxd, drop, pc);
+  });
+  if (!ok) MDT_UNSUPPORTED("layernorm: D=%d not supported (vectors per lane %d)", D, ln_vectors_per_lane<T>(D));
+  if (int e = check_launch("layernorm_bwd_ordered")) return e;
+  set_last_route("ln_generic");
+  return MDT_OK;
+}
+
 }  // namespace mdt
 
 using namespace mdt;
@@ -675,8 +706,51 @@ extern "C" int mdt_layernorm_bwd(void* stream, int dtype, int64_t rows, int D, c
   MDT_CHECK_ARG(dy && x && gamma && mean && rstd && dx, "layernorm_bwd: null pointer");
   if (int e = ln_check(dtype, D, lddy, ldx, dy, x)) return e;
   if (int e = ln_check(dtype, D, lddx, add ? ldadd : lddx, dx, add ? add : dx)) return e;
+  if (dgamma || dbeta || colsum) note_float_atomic_launch();
   hipStream_t st = (hipStream_t)stream;
   return dtype == MDT_F32
              ? ln_bwd_dispatch<float>(st, rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, dgamma, dbeta, dxd, lddxd, drop, colsum)
              : ln_bwd_dispatch<bf16_t>(st, rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, dgamma, dbeta, dxd, lddxd, drop, colsum);
+}
+
+extern "C" size_t mdt_layernorm_bwd_ordered_workspace_bytes(int64_t rows, int D) {
+  if (rows <= 0 || D <= 0) return 0;
+  int rpw;
+  unsigned grid;
+  ln_bwd_ordered_grid(rows, rpw, grid);
+  return (size_t)3 * grid * (size_t)D * sizeof(float);
+}
+
+extern "C" int mdt_layernorm_bwd_ordered(void* stream, int dtype, int64_t rows, int D, const void* dy, int64_t lddy,
+                                         const void* x, int64_t ldx, const void* gamma, const float* mean, const float* rstd,
+                                         const void* add, int64_t ldadd, void* dx, int64_t lddx, float* dgamma, float* dbeta,
+                                         void* dxd, int64_t lddxd, float drop_p, uint64_t drop_seed, float* colsum,
+                                         void* workspace, size_t workspace_bytes) {
+  if (rows == 0) return MDT_OK;
+  MDT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "layernorm_bwd_ordered: dropout p=%f out of [0,1)", drop_p);
+  MDT_CHECK_ARG(!dxd || rows * D < DROP_MAX_ELEMS, "layernorm_bwd_ordered: dropout site of %lld elements (limit 2^33)", (long long)(rows * D));
+  const DropCfg drop = make_drop(dxd ? drop_p : 0.f, drop_seed);
+  MDT_CHECK_ARG(dy && x && gamma && mean && rstd && dx, "layernorm_bwd_ordered: null pointer");
+  if (int e = ln_check(dtype, D, lddy, ldx, dy, x)) return e;
+  if (int e = ln_check(dtype, D, lddx, add ? ldadd : lddx, dx, add ? add : dx)) return e;
+  const size_t need = mdt_layernorm_bwd_ordered_workspace_bytes(rows, D);
+  MDT_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0,
+                "layernorm_bwd_ordered: workspace of %zu bytes, %zu needed (16-byte aligned)", workspace_bytes, need);
+  int rpw;
+  unsigned grid;
+  ln_bwd_ordered_grid(rows, rpw, grid);
+  const int64_t slice = (int64_t)grid * D;
+  float* pg = dgamma ? (float*)workspace : nullptr;
+  float* pb = dbeta ? (float*)workspace + slice : nullptr;
+  float* pc = colsum ? (float*)workspace + 2 * slice : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  const int e = dtype == MDT_F32
+                    ? ln_bwd_ordered_dispatch<float>(st, rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, pg, pb, dxd, lddxd, drop, pc)
+                    : ln_bwd_ordered_dispatch<bf16_t>(st, rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, pg, pb, dxd, lddxd, drop, pc);
+  if (e) return e;
+  // workgroup w's partial row is slice w: rows = 1, cols = D, slice stride D
+  if (pg) if (int e2 = sum_slices_f32(st, 1, D, (int)grid, pg, D, D, dgamma, D, 1)) return e2;
+  if (pb) if (int e2 = sum_slices_f32(st, 1, D, (int)grid, pb, D, D, dbeta, D, 1)) return e2;
+  if (pc) if (int e2 = sum_slices_f32(st, 1, D, (int)grid, pc, D, D, colsum, D, 1)) return e2;
+  return MDT_OK;
 }

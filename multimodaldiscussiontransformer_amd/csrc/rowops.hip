@@ -363,6 +363,7 @@ extern "C" int mdt_row_scatter_add_f32(void* stream, int dtype, int64_t nrows, i
                                        const int32_t* idx, const void* src, int64_t lds_, int64_t s_stride, int64_t s_off) {
   if (nrows == 0) return MDT_OK;
   MDT_CHECK_ARG(table && idx && src, "row_scatter_add: null pointer");
+  note_float_atomic_launch();
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)((nrows + 3) / 4);
 #define K_(T, ...) hipLaunchKernelGGL((row_scatter_add_kernel<T>), grid, 256, 0, st, nrows, D, table, ldt, idx, (const T*)src, lds_, s_stride, s_off)

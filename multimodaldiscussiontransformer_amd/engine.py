@@ -30,6 +30,76 @@ from . import fp8 as F8
 from . import ops
 
 
+# ------------------------------------------------------------------------------------------
+# deterministic (ordered) mode: a process-wide switch.  On, every gradient reduction of the backward pass takes its
+# fixed-order form (ops.gemm_splitk_ordered, colsum_ordered, layernorm_bwd_ordered, row_segment_sum, attn_bias_grad_ordered:
+# plain stores of partials + one sequential reducer instead of fp32 atomics), so loss, gradients and the parameters after
+# the optimiser step are bit-for-bit functions of weights, batch, seeds and library build — in ONE process on ONE GPU, bf16
+# or fp32 (DESIGN.md §4 "ordered mode").  Off (the default), nothing changes.
+_DETERMINISTIC = os.environ.get("MDT_DETERMINISTIC", "0") == "1"
+
+
+def set_deterministic(on: bool) -> None:
+    global _DETERMINISTIC
+    if on and F8.ACTIVE is not None:
+        raise NotImplementedError("deterministic mode with fp8 GEMMs: the fp8 path has no ordered reductions (disable fp8 first)")
+    _DETERMINISTIC = bool(on)
+
+
+def deterministic() -> bool:
+    return _DETERMINISTIC
+
+
+_ORDERED_WS: dict = {}
+
+
+def ordered_workspace(nbytes: int, device) -> torch.Tensor:
+    """The ordered kernels' workspace of the CURRENT stream: one byte buffer per (device, stream) that only grows.  A call's
+    partials are consumed by the reducer enqueued right behind it on the same stream, so consecutive calls share it; a
+    buffer that is outgrown goes back to the stream-ordered caching allocator."""
+    key = (torch.device(device).index, torch.cuda.current_stream().cuda_stream)
+    ws = _ORDERED_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(int(nbytes) * 5 // 4, 1 << 20), dtype=torch.uint8, device=device)
+        _ORDERED_WS[key] = ws
+    return ws
+
+
+def colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None, row_weight=None) -> torch.Tensor:
+    """ops.colsum, or its ordered form in deterministic mode."""
+    if not _DETERMINISTIC:
+        return ops.colsum(x, out=out, row_weight=row_weight)
+    ws = ordered_workspace(ops.lib.mdt_colsum_ordered_workspace_bytes(x.shape[0], x.shape[1]), x.device)
+    return ops.colsum_ordered(x, out=out, row_weight=row_weight, ws=ws)
+
+
+def scatter_add(table_f32: torch.Tensor, idx: torch.Tensor, src: torch.Tensor, nrows: int) -> torch.Tensor:
+    """ops.row_scatter_add (embedding gradients); deterministic mode: the segment sum over a stable sort of ``idx``."""
+    if not _DETERMINISTIC:
+        return ops.row_scatter_add(table_f32, idx, src, nrows)
+    seg_row, seg_off, order = ops.segments_of(idx.reshape(-1)[:nrows], table_f32.shape[0])
+    return ops.row_segment_sum(table_f32, seg_row, seg_off, order, src)
+
+
+def layernorm_bwd(dy, x, gamma, mean, rstd, **kw):
+    """ops.layernorm_bwd, or its ordered form in deterministic mode."""
+    if not _DETERMINISTIC:
+        return ops.layernorm_bwd(dy, x, gamma, mean, rstd, **kw)
+    ws = ordered_workspace(ops.lib.mdt_layernorm_bwd_ordered_workspace_bytes(x.shape[0], x.shape[1]), x.device)
+    return ops.layernorm_bwd_ordered(dy, x, gamma, mean, rstd, ws=ws, **kw)
+
+
+def wgrad_gemm(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor, asum=None) -> None:
+    """out[N, K] (fp32) += dY^T X over the rows, split-K: fp32 atomics, or in deterministic mode the slabs in ascending order."""
+    split = _split_k(dy.shape[1], x.shape[1], dy.shape[0])
+    if not _DETERMINISTIC:
+        ops.gemm(dy, x, trans_a=True, trans_b=True, out=out, epilogue=ops.EPI_ATOMIC, split_k=split, asum=asum)
+        return
+    assert asum is None, "deterministic mode: no bias sum rides on the weight-gradient GEMM"
+    ws = ordered_workspace(ops.lib.mdt_gemm_splitk_ordered_workspace_bytes(out.shape[0], out.shape[1], split), dy.device)
+    ops.gemm_splitk_ordered(dy, x, out, trans_a=True, trans_b=True, split_k=split, ws=ws)
+
+
 class _StreamState(threading.local):
     """Which branch the calling thread is enqueuing for (autograd runs a tape's backward on its own thread)."""
     side_active = False
@@ -89,6 +159,13 @@ class Tape:
     #     recycles it in side-stream order; a dense gradient handed over by an op (``add_grad``) falls back to
     #     ``record_stream``.
     def enable_side(self, device):
+        # Deterministic mode runs the tape on ONE stream.  Both branch streams accumulate (read-modify-write) into shared
+        # destinations — the bottleneck exchanges' gradient buffers (rows_mix, take_rows, scatter_rows, graph_node_features
+        # with accumulate=True) and the workspace of the ordered reducers — and the order of those updates is fixed by
+        # fork / join events only where an exchange sits strictly between a join and the next fork; that has not been shown
+        # for every accumulate, so the mode does not rely on it.
+        if _DETERMINISTIC:
+            return
         if self.side is None:
             self.side = side_stream(device)
 
@@ -272,14 +349,14 @@ def wgrad(tape: Tape, dy: torch.Tensor, x: torch.Tensor, w: torch.nn.Parameter, 
     gw = tape.pgrad(w)
     gb = tape.pgrad(b) if b is not None else None
     if gw is not None:
-        # the bias gradient rides on the weight-gradient GEMM, which streams dY anyway (MDT_EPI_ASUM; bf16 operands)
-        ride = gb is not None and dy.dtype == torch.bfloat16 and _WGRAD_ASUM
-        ops.gemm(dy, x, trans_a=True, trans_b=True, out=gw.view(dy.shape[1], x.shape[1]), epilogue=ops.EPI_ATOMIC,
-                 split_k=_split_k(dy.shape[1], x.shape[1], dy.shape[0]), asum=gb.view(-1) if ride else None)
+        # the bias gradient rides on the weight-gradient GEMM, which streams dY anyway (MDT_EPI_ASUM; bf16 operands) — not in
+        # deterministic mode, where it is a column sum of its own
+        ride = gb is not None and dy.dtype == torch.bfloat16 and _WGRAD_ASUM and not _DETERMINISTIC
+        wgrad_gemm(dy, x, gw.view(dy.shape[1], x.shape[1]), asum=gb.view(-1) if ride else None)
         if ride:
             return
     if gb is not None:
-        ops.colsum(dy, out=gb.view(-1))
+        colsum(dy, out=gb.view(-1))
 
 
 _LN_BIAS_RIDE = os.environ.get("MDT_LN_BIAS_RIDE", "1") != "0"    # 0: those sums stay in the LayerNorm backward (A/B runs)
@@ -338,20 +415,20 @@ def linear(f8, x: torch.Tensor, w: torch.nn.Parameter, tag: str, *, grad=False, 
 def dyd_rides(g: torch.Tensor) -> bool:
     """bias gradients of the dense layers behind a LayerNorm ride on their weight-gradient GEMM (MDT_EPI_ASUM) when that
     GEMM takes the 256 x 256 kernel (bf16, enough rows); small problems keep the sums inside the LayerNorm backward"""
-    return _LN_BIAS_RIDE and g.dtype == torch.bfloat16 and g.shape[0] >= 8192
+    return _LN_BIAS_RIDE and g.dtype == torch.bfloat16 and g.shape[0] >= 8192 and not _DETERMINISTIC
 
 
 def _ln_bwd(tape, dy, x, w, b, mean, rstd, add=None):
-    return ops.layernorm_bwd(dy, x, w.data, mean, rstd, add=add, dgamma=tape.pgrad(w), dbeta=tape.pgrad(b))
+    return layernorm_bwd(dy, x, w.data, mean, rstd, add=add, dgamma=tape.pgrad(w), dbeta=tape.pgrad(b))
 
 
 def _ln_bwd_dense(tape, dy, x, w, b, mean, rstd, bias_param, p_drop, seed, add=None):
     """LayerNorm backward + the fused tail for the dense layer that feeds it: returns (dx, dxd) where dxd is dx
     through that layer's hidden-dropout mask, and accumulates the layer's bias gradient (column sums of dxd)."""
     gb = tape.pgrad(bias_param) if bias_param is not None else None
-    return ops.layernorm_bwd(dy, x, w.data, mean, rstd, add=add, dgamma=tape.pgrad(w), dbeta=tape.pgrad(b),
-                             drop_p=p_drop, drop_seed=seed, colsum=None if gb is None else gb.view(-1),
-                             want_dropped=True)
+    return layernorm_bwd(dy, x, w.data, mean, rstd, add=add, dgamma=tape.pgrad(w), dbeta=tape.pgrad(b),
+                         drop_p=p_drop, drop_seed=seed, colsum=None if gb is None else gb.view(-1),
+                         want_dropped=True)
 
 
 # ------------------------------------------------------------------------------------------
@@ -447,8 +524,11 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
         weight-gradient GEMM (None: summed elsewhere).  → gradient of the half's input (+ ``dres``)"""
         wgrad(tape, gd, h, P.fc2_w, fc2_b)
         gb1 = tape.pgrad(P.fc1_b)           # fc1 bias gradient = colsum(du): fused into the GEMM epilogue
+        det = _DETERMINISTIC                # ... or, in deterministic mode, summed from the stored du in a fixed order
         du, du8 = linear(f8, gd, P.fc2_w, "d_fc2", grad=True, q8_site=("d_fc1", id(P.fc1_w)), q8_grad=True, aux=u,
-                         epilogue=ops.EPI_MULAUX, colsum=None if gb1 is None else gb1.view(-1))
+                         epilogue=ops.EPI_MULAUX, colsum=None if (gb1 is None or det) else gb1.view(-1))
+        if det and gb1 is not None:
+            colsum(du, out=gb1.view(-1))
         wgrad(tape, du, f_in, P.fc1_w, None)
         return linear(f8, du, P.fc1_w, "d_fc1", grad=True, x8=du8, residual=dres)[0]     # 8-bit when the GEMM above handed over the quantised du
 
@@ -495,6 +575,8 @@ def _attention_bwd(tape: Tape, spec: AttnSpec, kw: dict, dctx, qkv, ctx, lse, sp
     tables' go to their parameters, a dense bias' to ``spec.dense_bias_var``.  ``spread``: takes ``dctx`` to all rows of
     ``qkv`` (a block with keep_rows).  → dqkv"""
     extra = {}
+    if spec.sp_table is not None and _DETERMINISTIC:
+        return _attention_bwd_ordered(tape, spec, kw, dctx, qkv, ctx, lse, spread)
     if spec.sp_table is not None:
         extra = dict(d_sp_table=tape.pgrad(spec.sp_table),
                      d_virt=None if tape.pgrad(spec.virt) is None else tape.pgrad(spec.virt).view(-1))
@@ -503,6 +585,23 @@ def _attention_bwd(tape: Tape, spec: AttnSpec, kw: dict, dctx, qkv, ctx, lse, sp
                                     **extra)
     if want_dense:
         tape.add_grad(spec.dense_bias_var, dbias)
+    return dqkv
+
+
+def _attention_bwd_ordered(tape: Tape, spec: AttnSpec, kw: dict, dctx, qkv, ctx, lse, spread):
+    """Deterministic mode, structural bias: the backward stores dS densely (the whole-row kernels do, for every route a
+    structural launch takes) with the table gradients switched off, and ops.attn_bias_grad_ordered reduces it in a fixed
+    order.  The key-chunked long path (more than 272 tokens) is refused: its dS image is S^2 * H * 4 bytes per tree."""
+    if spec.S > 272:
+        raise NotImplementedError(f"deterministic mode: a structural attention bias over {spec.S} tokens takes the long path "
+                                  "(S > 272), whose bias gradient exists with float atomics only")
+    dqkv, dS = ops.attention_bwd(spread(dctx), qkv, ctx, lse, spec.nseq, spec.S, spec.H, **kw, want_dense_dbias=True)
+    gt, gv = tape.pgrad(spec.sp_table), tape.pgrad(spec.virt)
+    if gt is not None:
+        ws = ordered_workspace(ops.lib.mdt_attn_bias_grad_ordered_workspace_bytes(spec.nseq, spec.H, gt.shape[0]), dS.device)
+        ops.attn_bias_grad_ordered(dS, spec.spatial_pos, gt, None if gv is None else gv.view(-1), ws=ws)
+    if spec.dense_bias_var is not None and spec.dense_bias_var.needs_grad:
+        tape.add_grad(spec.dense_bias_var, dS)
     return dqkv
 
 
@@ -582,13 +681,13 @@ def bert_embeddings(tape: Tape, ids, types, word, pos, typ) -> Var:
             return
         gw, gp, gt = tape.pgrad(word), tape.pgrad(pos), tape.pgrad(typ)
         if gw is not None:
-            ops.row_scatter_add(gw, ids.view(-1), g, M * Lq)
+            scatter_add(gw, ids.view(-1), g, M * Lq)
         if gp is not None:
-            ops.colsum(g.view(M, Lq * D), out=gp[:Lq].view(-1))
+            colsum(g.view(M, Lq * D), out=gp[:Lq].view(-1))
         if gt is not None:
             assert typ.shape[0] == 2, "token-type gradient is implemented for type_vocab_size == 2"
-            tot = ops.colsum(g)
-            one = ops.colsum(g, row_weight=types.view(-1))
+            tot = colsum(g)
+            one = colsum(g, row_weight=types.view(-1))
             ops.row_axpby(gt, 1, d_off=1, a=one.view(1, D), accumulate=True)
             ops.row_axpby(gt, 1, d_off=0, a=tot.view(1, D), b=one.view(1, D), beta=-1.0, accumulate=True)
 
@@ -600,13 +699,13 @@ def _embed_rows_grads(tape: Tape, g, rows, ids, types, pos_ids, word, pos, typ):
     gw, gp, gt = tape.pgrad(word), tape.pgrad(pos), tape.pgrad(typ)
     D = word.shape[1]
     if gw is not None:
-        ops.row_scatter_add(gw, ids, g, rows)
+        scatter_add(gw, ids, g, rows)
     if gp is not None:
-        ops.row_scatter_add(gp, pos_ids, g, rows)
+        scatter_add(gp, pos_ids, g, rows)
     if gt is not None:
         assert typ.shape[0] == 2, "token-type gradient is implemented for type_vocab_size == 2"
-        tot = ops.colsum(g)
-        one = ops.colsum(g, row_weight=types)
+        tot = colsum(g)
+        one = colsum(g, row_weight=types)
         ops.row_axpby(gt, 1, d_off=1, a=one.view(1, D), accumulate=True)
         ops.row_axpby(gt, 1, d_off=0, a=tot.view(1, D), b=one.view(1, D), beta=-1.0, accumulate=True)
 
@@ -690,16 +789,15 @@ def vit_embeddings(tape: Tape, images, proj_w, proj_b, cls, pos, patch: int) -> 
             if gw is not None:
                 kin_, kp_ = gw.view(D, -1).shape[1], cols.shape[1]
                 acc = gw.view(D, -1) if kp_ == kin_ else torch.zeros(D, kp_, dtype=torch.float32, device=g.device)
-                ops.gemm(dpatch, cols, trans_a=True, trans_b=True, out=acc, epilogue=ops.EPI_ATOMIC,
-                         split_k=_split_k(D, cols.shape[1], dpatch.shape[0]))
+                wgrad_gemm(dpatch, cols, acc)
                 if kp_ != kin_:
                     gw.view(D, -1).add_(acc[:, :kin_])
             if gb is not None:
-                ops.colsum(dpatch, out=gb)
+                colsum(dpatch, out=gb)
         if gp is not None:
-            ops.colsum(g.view(I, (npatch + 1) * D), out=gp.view(-1))
+            colsum(g.view(I, (npatch + 1) * D), out=gp.view(-1))
         if gc is not None:
-            ops.colsum(g.view(I, (npatch + 1) * D)[:, :D], out=gc.view(-1))
+            colsum(g.view(I, (npatch + 1) * D)[:, :D], out=gc.view(-1))
 
     tape.record(bwd)
     return o
@@ -726,7 +824,7 @@ def expand_sequences(tape: Tape, x: Var, nseq: int, s_in: int, n_front: int, fro
         if g is None:
             return
         if front is not None and tape.pgrad(front) is not None:
-            ops.colsum(g.view(nseq, S * D)[:, : n_front * D], out=tape.pgrad(front).view(-1))
+            colsum(g.view(nseq, S * D)[:, : n_front * D], out=tape.pgrad(front).view(-1))
         if x.needs_grad:
             dx = torch.empty_like(x.data)
             ops.row_axpby(dx, nseq * s_in, a=g, a_inner=s_in, a_stride=S, a_off=n_front)
@@ -758,7 +856,7 @@ def expand_rows(tape: Tape, x: Var, rows_out: int, body_idx, front_idx, n_front:
         if gf is not None:
             fr = torch.empty(nfront, D, dtype=g.dtype, device=g.device)
             ops.row_axpby(fr, nfront, a=g, ai=front_idx)
-            ops.colsum(fr.view(nfront // n_front, n_front * D), out=gf.view(-1))
+            colsum(fr.view(nfront // n_front, n_front * D), out=gf.view(-1))
         if x.needs_grad:
             dx = torch.empty_like(x.data)
             ops.row_axpby(dx, rows_in, a=g, ai=body_idx)
@@ -818,11 +916,11 @@ def graph_node_features(tape: Tape, text: Var, text_row_of_node, in_degree, out_
             ops.row_axpby(gt, M, di=src_rows_of_comment, a=g, ai=graph_rows_of_comment, accumulate=True)
         gi, go, gk = tape.pgrad(in_emb), tape.pgrad(out_emb), tape.pgrad(graph_token)
         if gi is not None:
-            ops.row_scatter_add(gi, in_scatter_idx, g, B * T)
+            scatter_add(gi, in_scatter_idx, g, B * T)
         if go is not None:
-            ops.row_scatter_add(go, out_scatter_idx, g, B * T)
+            scatter_add(go, out_scatter_idx, g, B * T)
         if gk is not None:
-            ops.colsum(g.view(B, T * D)[:, :D], out=gk.view(-1))
+            colsum(g.view(B, T * D)[:, :D], out=gk.view(-1))
 
     tape.record(bwd)
     return o

@@ -137,6 +137,10 @@ class GraphormerModel(FairseqEncoderModel):
         if on and act != "gelu":
             raise NotImplementedError(f"enable_fp8 with --activation-fn {act}: the fp8 path quantises h inside fc1's fused gelu "
                                       "epilogue, which the other activations do not go through")
+        from .. import engine
+        if on and engine.deterministic():
+            raise NotImplementedError("enable_fp8 in deterministic mode: the fp8 path has no ordered reductions "
+                                      "(engine.set_deterministic(False) first)")
         fp8.ACTIVE = fp8.Fp8State(next(self.parameters()).device, sites=sites) if on else None
         return fp8.ACTIVE
 

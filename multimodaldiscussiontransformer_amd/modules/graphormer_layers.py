@@ -83,6 +83,10 @@ class _GraphAttnBiasFn(torch.autograd.Function):
         g = g.contiguous()
         dt = torch.zeros(tshape, dtype=torch.float32, device=g.device)
         dv = torch.zeros(vshape[-1], dtype=torch.float32, device=g.device)
+        if E.deterministic():       # the fixed-order histogram of the dense gradient instead of the two atomic reductions
+            ws = E.ordered_workspace(ops.lib.mdt_attn_bias_grad_ordered_workspace_bytes(B, H, tshape[0]), g.device)
+            ops.attn_bias_grad_ordered(g.float(), sp.to(torch.int32).contiguous(), dt, dv, ws=ws)
+            return dt.to(dtype), dv.view(vshape).to(dtype), None, None
         # rows of the [B*H*S*S] gradient viewed per (b, h, i): scatter the node x node block into the table
         # via the row scatter-add kernel on a [B*N*N, H] rearrangement
         N = S - 1

@@ -20,6 +20,8 @@ __all__ = [
     "gemm", "colsum", "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "attention_mean_probs", "graph_attn_bias",
     "row_axpby", "row_scatter_add", "bert_embed_sum", "bert_embed_ln_rows", "vit_patchify", "vit_assemble", "vit_patch_embed", "graph_node_feature",
     "tanh_fwd", "tanh_bwd", "node_ce", "contrastive_loss", "fp8_quantize", "fp8_scale_update", "gemm_fp8", "cast", "transpose2d", "dropout", "dropout_mask",
+    "sum_slices", "gemm_splitk_ordered", "colsum_ordered", "layernorm_bwd_ordered", "segments_of", "row_segment_sum",
+    "attn_bias_grad_ordered", "float_atomic_launches",
     "act_fwd", "ACT_KINDS", "ACT_GELU", "ACT_RELU", "ACT_GELU_ACCURATE", "ACT_TANH", "ACT_LINEAR",
     "EPI_BIAS", "EPI_GELU", "EPI_RESIDUAL", "EPI_DGELU", "EPI_ACCUM", "EPI_ATOMIC", "EPI_DROPOUT", "EPI_AUX_GRAD", "EPI_MULAUX", "EPI_ASUM",
 ]
@@ -263,6 +265,112 @@ def row_scatter_add(table_f32, idx, src, nrows, *, s_stride=1, s_off=0):
     check(lib.mdt_row_scatter_add_f32(stream(), dt(src), nrows, table_f32.shape[1], ptr(table_f32), _2d(table_f32),
                                       ptr(idx), ptr(src), _2d(src), s_stride, s_off), "mdt_row_scatter_add_f32")
     return table_f32
+
+
+# ------------------------------------------------------------------------------------------
+# ordered (bit-reproducible) reductions: include/mdt_hip.h "ordered gradient reductions".  ``ws``: a caller-owned byte
+# buffer (the engine's growing per-stream workspace); None allocates one of the queried size for this call.
+def _workspace(ws, need: int, device):
+    if ws is None:
+        ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous()
+    return ws, ws.numel()
+
+
+def float_atomic_launches(reset: bool = False) -> int:
+    """Launches so far that accumulate with float atomics into caller memory (host-side count); ``reset`` zeroes it."""
+    return int(lib.mdt_float_atomic_launches(int(reset)))
+
+
+def sum_slices(ws: torch.Tensor, out: torch.Tensor, accumulate: bool = False) -> torch.Tensor:
+    """out[r, c] = (out[r, c] if accumulate else 0) + (((ws[0] + ws[1]) + ws[2]) + ...)[r, c]; ws f32[slices, rows, cols] with
+    any slice / row strides (unit inner stride), out f32[rows, cols] with any row stride."""
+    assert ws.dim() == 3 and out.dim() == 2 and ws.shape[1:] == out.shape and ws.dtype == out.dtype == torch.float32
+    assert ws.shape[2] == 0 or (ws.stride(2) == 1 and out.stride(1) == 1)
+    check(lib.mdt_sum_slices_f32(stream(), out.shape[0], out.shape[1], ws.shape[0], ptr(ws), ws.stride(1), ws.stride(0), ptr(out),
+                                 out.stride(0), int(accumulate)), "mdt_sum_slices_f32")
+    return out
+
+
+def gemm_splitk_ordered(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, *, trans_a=False, trans_b=False, alpha=1.0,
+                        split_k=1, ws=None) -> torch.Tensor:
+    """out[M, N] (fp32) += alpha * op(a) @ op(b) with the K slabs added in ascending order (no float atomics)."""
+    lda, ldb = _2d(a), _2d(b)
+    M, K = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
+    N = b.shape[1] if trans_b else b.shape[0]
+    assert (b.shape[0] if trans_b else b.shape[1]) == K and a.dtype == b.dtype
+    assert out.dtype == torch.float32 and out.shape == (M, N)
+    ws, nbytes = _workspace(ws, lib.mdt_gemm_splitk_ordered_workspace_bytes(M, N, int(split_k)), a.device)
+    check(lib.mdt_gemm_splitk_ordered(stream(), dt(a), int(trans_a), int(trans_b), M, N, K, ptr(a), lda, ptr(b), ldb, ptr(out),
+                                      _2d(out), float(alpha), int(split_k), ptr(ws), nbytes), "mdt_gemm_splitk_ordered")
+    return out
+
+
+def colsum_ordered(x: torch.Tensor, out: Optional[torch.Tensor] = None, row_weight=None, ws=None) -> torch.Tensor:
+    """``colsum`` in a fixed order (blocks of 256 rows, then the blocks in ascending order)."""
+    if out is None:
+        out = torch.zeros(x.shape[1], dtype=torch.float32, device=x.device)
+    assert row_weight is None or (row_weight.dtype == torch.int32 and row_weight.numel() == x.shape[0])
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == x.shape[1]
+    ws, nbytes = _workspace(ws, lib.mdt_colsum_ordered_workspace_bytes(x.shape[0], x.shape[1]), x.device)
+    check(lib.mdt_colsum_ordered(stream(), dt(x), x.shape[0], x.shape[1], ptr(x), _2d(x), ptr(out), ptr(row_weight), ptr(ws), nbytes),
+          "mdt_colsum_ordered")
+    return out
+
+
+def layernorm_bwd_ordered(dy, x, gamma, mean, rstd, add=None, dgamma=None, dbeta=None, dx=None, drop_p=0.0, drop_seed=0,
+                          colsum=None, want_dropped=False, ws=None):
+    """``layernorm_bwd`` whose dgamma / dbeta / column sums are added in a fixed order; dx and dxd keep their bits."""
+    rows, D = x.shape
+    if dx is None:
+        dx = torch.empty_like(x)
+    dxd = torch.empty_like(x) if (want_dropped and drop_p > 0.0) else None
+    ws, nbytes = _workspace(ws, lib.mdt_layernorm_bwd_ordered_workspace_bytes(rows, D), x.device)
+    check(lib.mdt_layernorm_bwd_ordered(stream(), dt(x), rows, D, ptr(dy), _2d(dy), ptr(x), _2d(x), ptr(gamma), ptr(mean),
+                                        ptr(rstd), ptr(add), _2d(add) if add is not None else 0, ptr(dx), _2d(dx),
+                                        ptr(dgamma), ptr(dbeta), ptr(dxd), _2d(dxd) if dxd is not None else 0, float(drop_p),
+                                        int(drop_seed), ptr(colsum), ptr(ws), nbytes), "mdt_layernorm_bwd_ordered")
+    if want_dropped:
+        return dx, (dxd if dxd is not None else dx)
+    return dx
+
+
+def segments_of(idx: torch.Tensor, n_table_rows: int):
+    """CSR segments of an index vector for ``row_segment_sum``: one segment per table row (most of them empty), the sources of a
+    segment in ascending source-row order (stable sort); negative indices belong to no segment.  No host synchronisation.
+    → (seg_row i32[T], seg_off i32[T + 1], order i32[n])"""
+    assert idx.dtype == torch.int32 and idx.dim() == 1
+    sorted_idx, order = torch.sort(idx, stable=True)
+    bounds = torch.arange(n_table_rows + 1, dtype=torch.int32, device=idx.device)
+    seg_off = torch.searchsorted(sorted_idx, bounds, out_int32=True)
+    return bounds[:-1], seg_off.contiguous(), order.to(torch.int32)
+
+
+def row_segment_sum(table_f32, seg_row, seg_off, order, src, *, s_stride=1, s_off=0):
+    """table[seg_row[s]] += the source rows order[seg_off[s] : seg_off[s + 1]] of ``src`` in that order, chunks of 64 (mdt_hip.h)."""
+    assert table_f32.dtype == torch.float32
+    for t in (seg_row, seg_off, order):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    nseg = seg_row.numel()
+    assert seg_off.numel() == nseg + 1
+    check(lib.mdt_row_segment_sum_f32(stream(), dt(src), nseg, table_f32.shape[1], ptr(table_f32), _2d(table_f32), ptr(seg_row),
+                                      ptr(seg_off), ptr(order), ptr(src), _2d(src), s_stride, s_off), "mdt_row_segment_sum_f32")
+    return table_f32
+
+
+def attn_bias_grad_ordered(dS, spatial_pos, d_sp_table=None, d_virt=None, ws=None):
+    """d_sp_table f32[num_spatial, H] / d_virt f32[H] += the structural-bias gradient of a dense dS f32[nseq, H, S, S]."""
+    nseq, H, S, _ = dS.shape
+    assert dS.dtype == torch.float32 and dS.is_contiguous() and dS.shape[3] == S
+    assert spatial_pos.dtype == torch.int32 and spatial_pos.is_contiguous() and spatial_pos.shape == (nseq, S - 1, S - 1)
+    assert d_sp_table is not None, "attn_bias_grad_ordered: the table gradient gives the number of bins"
+    assert d_sp_table.dtype == torch.float32 and d_sp_table.is_contiguous() and d_sp_table.shape[1] == H
+    assert d_virt is None or (d_virt.dtype == torch.float32 and d_virt.is_contiguous() and d_virt.numel() == H)
+    ns = d_sp_table.shape[0]
+    ws, nbytes = _workspace(ws, lib.mdt_attn_bias_grad_ordered_workspace_bytes(nseq, H, ns), dS.device)
+    check(lib.mdt_attn_bias_grad_ordered(stream(), nseq, S, H, ns, ptr(dS), ptr(spatial_pos), ptr(d_sp_table), ptr(d_virt), ptr(ws),
+                                         nbytes), "mdt_attn_bias_grad_ordered")
+    return d_sp_table, d_virt
 
 
 def bert_embed_sum(ids, types, word, pos, type_emb, out, *, out_seq_stride, out_off):

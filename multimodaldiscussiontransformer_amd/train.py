@@ -61,6 +61,9 @@ def build_parser():
     p.add_argument("--fp8", action="store_true", default=False,
                    help="BASELINE.json configs[4] (not a reference flag): bf16 run with per-tensor-scaled fp8 operands in the blocks' big GEMMs (fp8.py)")
     p.add_argument("--fp8-sites", default=None, help="preset (all | fast4 | grads) or comma list of fp8 sites (fp8.PRESETS); default all")
+    p.add_argument("--deterministic", action="store_true", default=False,
+                   help="not a reference flag: ordered gradient reductions instead of fp32 atomics (engine.set_deterministic) — loss, "
+                        "gradients and parameters are bit-for-bit reproducible in one process on one GPU; bf16 / fp32 only, not with --fp8")
     p.add_argument("--log-interval", type=int, default=10)
     # criterion flags: every field of every registered criterion's config dataclass (FairSeq derives them the same way)
     from .registry import CRITERION_REGISTRY as _CR
@@ -147,6 +150,14 @@ def main(argv=None):
     if args.required_batch_size_multiple != 1:
         print("[mdt-train] --required-batch-size-multiple: ignored — batches hold exactly --batch-size trees (the last one of an epoch may be smaller)",
               file=sys.stderr)
+    from . import engine
+    was_deterministic = engine.deterministic()
+    if args.deterministic:
+        if args.fp8:
+            raise SystemExit("[mdt-train] --deterministic with --fp8: the fp8 path has no ordered reductions")
+        engine.set_deterministic(True)
+        print("[mdt-train] --deterministic: ordered gradient reductions, no float atomics, one stream (one process, one GPU: "
+              "the all-reduce order of several ranks is not fixed)", file=sys.stderr)
     import torch.distributed as dist
     from .ddp import DataParallel
     from .optim import FusedAdam, PolynomialDecayLR
@@ -390,6 +401,8 @@ def main(argv=None):
     if fp8_state is not None:
         from . import fp8 as _fp8
         _fp8.ACTIVE = None                           # process-wide switch: a later model in this process starts in bf16
+    if args.deterministic:
+        engine.set_deterministic(was_deterministic)  # the same: a later run in this process starts as this one found the switch
     if world > 1:
         dist.destroy_process_group()
     return history
