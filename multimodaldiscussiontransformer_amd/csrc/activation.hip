@@ -42,7 +42,6 @@ __device__ __forceinline__ void act_pair(float x, float s, float& h, float& u) {
 template <typename T, int VN, int KIND>
 __global__ __launch_bounds__(256) void act_fwd_kernel(int64_t rows, int N, const T* pre, int64_t ld_pre, T* h, int64_t ld_h,
                                                       T* u, int64_t ld_u, DropCfg d) {
-  typedef __attribute__((ext_vector_type(VN))) T vec;
   const int64_t nv = N / VN;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t sr = stride / nv, sc = stride % nv;
@@ -60,9 +59,9 @@ __global__ __launch_bounds__(256) void act_fwd_kernel(int64_t rows, int N, const
       x[0] = to_f32(pre[r * ld_pre + c]);
       s[0] = drop ? drop_scale(d, (uint64_t)r * N + c) : 1.0f;
     } else {
-      const vec v = *(const vec*)(pre + r * ld_pre + c);
+      const Vec<T> v = *(const Vec<T>*)(pre + r * ld_pre + c);
 #pragma unroll
-      for (int e = 0; e < VN; ++e) x[e] = to_f32((T)v[e]);
+      for (int e = 0; e < VN; ++e) x[e] = v.get(e);
 #pragma unroll
       for (int e = 0; e < VN; e += 2) {      // N is even here, so every vector starts on an even counter
         if (drop) drop_scale2(d, (uint64_t)r * N + c + e, s[e], s[e + 1]);
@@ -75,11 +74,11 @@ __global__ __launch_bounds__(256) void act_fwd_kernel(int64_t rows, int N, const
       h[r * ld_h + c] = from_f32<T>(hv[0]);
       if (u) u[r * ld_u + c] = from_f32<T>(uv[0]);
     } else {
-      vec ho, uo;
+      Vec<T> ho, uo;
 #pragma unroll
-      for (int e = 0; e < VN; ++e) { ho[e] = from_f32<T>(hv[e]); uo[e] = from_f32<T>(uv[e]); }
-      *(vec*)(h + r * ld_h + c) = ho;
-      if (u) *(vec*)(u + r * ld_u + c) = uo;
+      for (int e = 0; e < VN; ++e) { ho.set(e, hv[e]); uo.set(e, uv[e]); }
+      *(Vec<T>*)(h + r * ld_h + c) = ho;
+      if (u) *(Vec<T>*)(u + r * ld_u + c) = uo;
     }
   }
 }
@@ -122,12 +121,10 @@ extern "C" int mdt_act_fwd(void* stream, int dtype, int kind, int64_t rows, int 
   MDT_CHECK_ARG(rows * N < DROP_MAX_ELEMS, "mdt_act_fwd: site of %lld elements (limit 2^33)", (long long)(rows * N));
   hipStream_t st = (hipStream_t)stream;
   const DropCfg d = make_drop(drop_p, drop_seed);
-  const int vn = dtype == MDT_BF16 ? 8 : 4;
-  const bool vec = N % vn == 0 && ld_pre % vn == 0 && ld_h % vn == 0 && (!u || ld_u % vn == 0) &&
-                   (((uintptr_t)pre | (uintptr_t)h | (uintptr_t)u) & 15) == 0;
-  if (dtype == MDT_F32)
-    return vec ? launch_act_kind<float, 4>(kind, st, rows, N, pre, ld_pre, h, ld_h, u, ld_u, d)
-               : launch_act_kind<float, 1>(kind, st, rows, N, pre, ld_pre, h, ld_h, u, ld_u, d);
-  return vec ? launch_act_kind<bf16_t, 8>(kind, st, rows, N, pre, ld_pre, h, ld_h, u, ld_u, d)
-             : launch_act_kind<bf16_t, 1>(kind, st, rows, N, pre, ld_pre, h, ld_h, u, ld_u, d);
+  const bool vec = vec16_ok(dtype, N, {ld_pre, ld_h, u ? ld_u : 0}, {pre, h, u});
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return vec ? launch_act_kind<T, Vec<T>::N>(kind, st, rows, N, pre, ld_pre, h, ld_h, u, ld_u, d)
+               : launch_act_kind<T, 1>(kind, st, rows, N, pre, ld_pre, h, ld_h, u, ld_u, d);
+  });
 }

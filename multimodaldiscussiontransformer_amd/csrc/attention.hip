@@ -683,9 +683,9 @@ extern "C" int mdt_attention_mean_probs(void* stream, const mdt_attn_fwd_args* a
   MDT_CHECK_ARG(!a->seq_offsets, "attention_mean_probs: ragged sequences are not supported (module-level API only)");
   const int64_t n = (int64_t)a->nseq * a->S * a->S;
   const int grid = (int)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
-  if (a->dtype == MDT_F32) hipLaunchKernelGGL((attn_mean_probs_kernel<float>), grid, 256, 0, (hipStream_t)stream, *a, out);
-  else hipLaunchKernelGGL((attn_mean_probs_kernel<bf16_t>), grid, 256, 0, (hipStream_t)stream, *a, out);
-  return check_launch("attention_mean_probs");
+  return with_dtype(a->dtype, [&](auto t) {
+    return launch_plain<attn_mean_probs_kernel<typename decltype(t)::type>>("attention_mean_probs", grid, 256, (hipStream_t)stream, *a, out);
+  });
 }
 
 // Per-head attention weights (modules/multihead_attention.py:91-102,186-214: ``need_head_weights`` — the softmax probabilities
@@ -725,14 +725,11 @@ extern "C" int mdt_attention_head_weights(void* stream, const mdt_attn_fwd_args*
   const int64_t n = (int64_t)a->nseq * a->H * a->S * a->S;
   const int grid = (int)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  if (a->dtype == MDT_F32) {
-    if (raw_scores) hipLaunchKernelGGL((attn_head_weights_kernel<float, true>), grid, 256, 0, st, *a, out);
-    else hipLaunchKernelGGL((attn_head_weights_kernel<float, false>), grid, 256, 0, st, *a, out);
-  } else {
-    if (raw_scores) hipLaunchKernelGGL((attn_head_weights_kernel<bf16_t, true>), grid, 256, 0, st, *a, out);
-    else hipLaunchKernelGGL((attn_head_weights_kernel<bf16_t, false>), grid, 256, 0, st, *a, out);
-  }
-  return check_launch("attention_head_weights");
+  return with_dtype(a->dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return raw_scores ? launch_plain<attn_head_weights_kernel<T, true>>("attention_head_weights", grid, 256, st, *a, out)
+                      : launch_plain<attn_head_weights_kernel<T, false>>("attention_head_weights", grid, 256, st, *a, out);
+  });
 }
 
 extern "C" int mdt_graph_attn_bias(void* stream, int dtype, int nseq, int S, int H, const float* attn_bias,
@@ -742,8 +739,8 @@ extern "C" int mdt_graph_attn_bias(void* stream, int dtype, int nseq, int S, int
   const int64_t n = (int64_t)nseq * H * S * S;
   const int grid = (int)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDT_F32) hipLaunchKernelGGL((graph_attn_bias_kernel<float>), grid, 256, 0, st, nseq, S, H, attn_bias, spatial_pos, (const float*)sp_table, (const float*)virt, out);
-  else if (dtype == MDT_BF16) hipLaunchKernelGGL((graph_attn_bias_kernel<bf16_t>), grid, 256, 0, st, nseq, S, H, attn_bias, spatial_pos, (const bf16_t*)sp_table, (const bf16_t*)virt, out);
-  else MDT_UNSUPPORTED("graph_attn_bias: dtype %d", dtype);
-  return check_launch("graph_attn_bias");
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_plain<graph_attn_bias_kernel<T>>("graph_attn_bias", grid, 256, st, nseq, S, H, attn_bias, spatial_pos, (const T*)sp_table, (const T*)virt, out);
+  });
 }

@@ -6,6 +6,8 @@
 #include <string.h>
 
 #include <atomic>
+#include <initializer_list>
+#include <type_traits>
 
 #include "../../include/mdt_hip.h"
 
@@ -259,5 +261,73 @@ template <> struct DType<float> { static constexpr int id = MDT_F32; };
 template <> struct DType<bf16_t> { static constexpr int id = MDT_BF16; };
 
 static inline size_t dtype_size(int dt) { return dt == MDT_BF16 ? 2 : 4; }
+
+// ---------------------------------------------------------------- dtype dispatch and plain launches
+// The one place a runtime MDT_F32 / MDT_BF16 becomes a type: calls f(TypeTag<float>{}) or f(TypeTag<bf16_t>{}) and returns
+// what it returns; anything else is MDT_ERR_UNSUPPORTED.  Argument checks come before the call, as with_layout's do.
+template <typename T> struct TypeTag { using type = T; };
+template <class F>
+static int with_dtype(int dtype, F&& f) {
+  if (dtype == MDT_F32) return f(TypeTag<float>{});
+  if (dtype == MDT_BF16) return f(TypeTag<bf16_t>{});
+  MDT_UNSUPPORTED("dtype %d is neither MDT_F32 nor MDT_BF16", dtype);
+}
+// source and destination types (mdt_cast, mdt_transpose2d): f(TypeTag<TS>{}, TypeTag<TD>{})
+template <class F>
+static int with_dtypes(int src_dtype, int dst_dtype, F&& f) {
+  return with_dtype(src_dtype, [&](auto s) { return with_dtype(dst_dtype, [&](auto d) { return f(s, d); }); });
+}
+// A kernel without dynamic LDS and without a route of its own: launch, then check_launch(name).  mdt_last_route() is left alone
+// (launch_route above is for the launches that report one).
+template <auto Kern, typename... Args>
+int launch_plain(const char* name, dim3 grid, dim3 block, hipStream_t st, Args... args) {
+  hipLaunchKernelGGL(Kern, grid, block, 0, st, args...);
+  return check_launch(name);
+}
+
+// ---------------------------------------------------------------- 16-byte vectors
+template <typename T> struct Vec;  // 16-byte vector of T
+template <> struct Vec<float> {
+  static constexpr int N = 4;
+  f32x4 v;
+  __device__ __forceinline__ float get(int i) const { return v[i]; }
+  __device__ __forceinline__ void set(int i, float x) { v[i] = x; }
+};
+template <> struct Vec<bf16_t> {
+  static constexpr int N = 8;
+  bf16x8 v;
+  __device__ __forceinline__ float get(int i) const { return (float)v[i]; }
+  __device__ __forceinline__ void set(int i, float x) { v[i] = (bf16_t)x; }
+};
+// 8-byte vectors: D = 768 is 64 lanes x 12 elements = three 8-byte vectors per lane with EVERY lane busy; as 16-byte vectors it is one
+// and a half (the second one on lanes 0-31 only: a quarter of the row's arithmetic slots idle).  Wave instructions still cover
+// 512 contiguous bytes.
+template <typename T> struct VecH;
+template <> struct VecH<bf16_t> {
+  static constexpr int N = 4;
+  bf16x4 v;
+  __device__ __forceinline__ float get(int i) const { return (float)v[i]; }
+  __device__ __forceinline__ void set(int i, float x) { v[i] = (bf16_t)x; }
+};
+// Host side: rows of `width` elements of `dtype` at these row strides (0 for an absent operand) and base pointers (null for
+// an absent one) allow 16-byte access — what decides between the vector and the scalar form of a kernel.
+static inline bool vec16_ok(int dtype, int64_t width, std::initializer_list<int64_t> strides, std::initializer_list<const void*> ptrs) {
+  const int vn = 16 / (int)dtype_size(dtype);
+  bool ok = width % vn == 0;
+  for (const int64_t s : strides) ok = ok && s % vn == 0;
+  for (const void* p : ptrs) ok = ok && ((uintptr_t)p & 15) == 0;
+  return ok;
+}
+
+// BERT embeddings of one token, from the vectors a lane holds of its three table rows: word + type + pos in that order in
+// fp32, ONE rounding to the storage type.  The only place the sum is written (rowops.hip bert_embed_kernel, layernorm.hip
+// bert_embed_ln_rows_kernel), so the fused and the separate forms agree bit for bit.
+template <typename V>
+__device__ __forceinline__ V bert_embed_vec(const V& w, const V& t, const V& p) {
+  V o;
+#pragma unroll
+  for (int j = 0; j < V::N; ++j) o.set(j, w.get(j) + t.get(j) + p.get(j));
+  return o;
+}
 
 }  // namespace mdt

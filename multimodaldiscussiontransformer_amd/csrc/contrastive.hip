@@ -159,14 +159,12 @@ extern "C" int mdt_contrastive_loss(void* stream, int dtype, int B, int D, const
   float* G = n + (size_t)B * D;
   float* inv = G + (size_t)B * B;
   float* extra = inv + B;
-  if (dtype == MDT_F32) hipLaunchKernelGGL((cl_normalize_kernel<float>), B, 64, 0, st, B, D, (const float*)emb, ld, n, inv);
-  else hipLaunchKernelGGL((cl_normalize_kernel<bf16_t>), B, 64, 0, st, B, D, (const bf16_t*)emb, ld, n, inv);
-  hipLaunchKernelGGL(cl_rowstats_kernel, (B + 255) / 256, 256, 0, st, B, y, hard_y, adaptive, soft_negative_weight, extra);
-  hipLaunchKernelGGL(cl_pair_kernel, 1, 1024, 0, st, B, D, n, y, hard_y, extra, scale, G, out_loss, counters);
-  if (d_emb) {
-    const size_t lds = (size_t)(D + 256) * sizeof(float);
-    if (dtype == MDT_F32) hipLaunchKernelGGL((cl_grad_kernel<float>), B, 256, lds, st, B, D, n, inv, G, scale, grad_scale, (float*)d_emb, ldd);
-    else hipLaunchKernelGGL((cl_grad_kernel<bf16_t>), B, 256, lds, st, B, D, n, inv, G, scale, grad_scale, (bf16_t*)d_emb, ldd);
-  }
-  return check_launch("contrastive_loss");
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((cl_normalize_kernel<T>), B, 64, 0, st, B, D, (const T*)emb, ld, n, inv);
+    hipLaunchKernelGGL(cl_rowstats_kernel, (B + 255) / 256, 256, 0, st, B, y, hard_y, adaptive, soft_negative_weight, extra);
+    hipLaunchKernelGGL(cl_pair_kernel, 1, 1024, 0, st, B, D, n, y, hard_y, extra, scale, G, out_loss, counters);
+    if (d_emb) hipLaunchKernelGGL((cl_grad_kernel<T>), B, 256, (size_t)(D + 256) * sizeof(float), st, B, D, n, inv, G, scale, grad_scale, (T*)d_emb, ldd);
+    return check_launch("contrastive_loss");
+  });
 }

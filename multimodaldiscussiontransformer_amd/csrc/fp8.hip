@@ -93,11 +93,14 @@ extern "C" int mdt_fp8_quantize(void* stream, int src_dtype, int fmt, int64_t ro
   hipStream_t st = (hipStream_t)stream;
   const int64_t work = rows * (cols >> 3);
   const unsigned grid = (unsigned)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256);     // 8 workgroups per CU, grid-stride
-#define Q_(T, F) hipLaunchKernelGGL((fp8_quantize_kernel<T, F>), grid, 256, 0, st, rows, cols, (const T*)src, ld_src, (uint8_t*)dst, ld_dst, scale_dev, amax_dev)
-  if (src_dtype == MDT_BF16) { if (fmt == 0) Q_(bf16_t, 0); else Q_(bf16_t, 1); }
-  else { if (fmt == 0) Q_(float, 0); else Q_(float, 1); }
-#undef Q_
-  return check_launch("fp8_quantize");
+  return with_dtype(src_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto launch = [&](auto f) {
+      return launch_plain<fp8_quantize_kernel<T, decltype(f)::value>>("fp8_quantize", grid, 256, st, rows, cols, (const T*)src, ld_src, (uint8_t*)dst, ld_dst,
+                                                                     scale_dev, amax_dev);
+    };
+    return fmt == 0 ? launch(std::integral_constant<int, 0>{}) : launch(std::integral_constant<int, 1>{});
+  });
 }
 
 extern "C" int mdt_fp8_scale_update(void* stream, int n, float* amax, float* scale, float* inv_scale, const float* fmt_max, float margin) {

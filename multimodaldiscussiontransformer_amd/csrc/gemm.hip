@@ -840,107 +840,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #undef W4_MF
 }
 
-// ------------------------------------------------------------------ helpers
-template <typename TIn, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void colsum_kernel(int64_t M, int64_t N, const TIn* X, int64_t ldx, float* out,
-                                                        int rows_per_block, const int32_t* row_weight) {
-  // block = 256 threads: 64 columns x 4 row-lanes; grid.x = column groups, grid.y = row chunks
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int rl = threadIdx.x >> 6;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-  const int64_t r1 = (r0 + rows_per_block < M) ? r0 + rows_per_block : M;
-  float s = 0.f;
-  if (c < N)
-    for (int64_t r = r0 + rl; r < r1; r += 4) {
-      const float w = row_weight ? (float)row_weight[r] : 1.f;
-      s += w * to_f32(X[r * ldx + c]);
-    }
-  __shared__ float red[4][64];
-  red[rl][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (rl == 0 && c < N) atomicAdd(out + c, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-
-// 16-byte-vectorised column sum: lane = VN consecutive columns, the 4 waves of a block interleave rows
-template <typename TIn, int VN>
-__global__ __launch_bounds__(256) void colsum_vec_kernel(int64_t M, int64_t N, const TIn* X, int64_t ldx, float* out,
-                                                         int rows_per_block, const int32_t* row_weight) {
-  typedef __attribute__((ext_vector_type(VN))) TIn vec;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t c = ((int64_t)blockIdx.x * 64 + lane) * VN;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-  const int64_t r1 = (r0 + rows_per_block < M) ? r0 + rows_per_block : M;
-  float acc[VN];
-#pragma unroll
-  for (int e = 0; e < VN; ++e) acc[e] = 0.f;
-  if (c < N) {
-    for (int64_t r = r0 + wave; r < r1; r += 4) {
-      const vec v = *(const vec*)(X + r * ldx + c);
-      const float w = row_weight ? (float)row_weight[r] : 1.f;
-#pragma unroll
-      for (int e = 0; e < VN; ++e) acc[e] += w * to_f32((TIn)v[e]);
-    }
-  }
-  __shared__ float red[4][64 * VN];
-#pragma unroll
-  for (int e = 0; e < VN; ++e) red[wave][lane * VN + e] = acc[e];
-  __syncthreads();
-  for (int i = threadIdx.x; i < 64 * VN; i += 256) {
-    const int64_t col = (int64_t)blockIdx.x * 64 * VN + i;
-    if (col < N) atomicAdd(out + col, red[0][i] + red[1][i] + red[2][i] + red[3][i]);
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void dropout_kernel(int64_t rows, int D, const T* x, int64_t ldx, T* y, int64_t ldy, DropCfg d) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4)
-    for (int c = lane; c < D; c += 64)
-      y[r * ldy + c] = from_f32<T>(to_f32(x[r * ldx + c]) * drop_scale(d, (uint64_t)r * D + c));
-}
-// 16-byte vector variant (D, strides multiples of VN; D even so every vector starts on an even counter)
-template <typename T, int VN>
-__global__ __launch_bounds__(256) void dropout_vec_kernel(int64_t rows, int D, const T* x, int64_t ldx, T* y, int64_t ldy, DropCfg d) {
-  typedef __attribute__((ext_vector_type(VN))) T vec;
-  const int lane = threadIdx.x & 63;
-  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4)
-    for (int c = lane * VN; c < D; c += 64 * VN) {
-      const vec v = *(const vec*)(x + r * ldx + c);
-      vec o;
-#pragma unroll
-      for (int e = 0; e < VN; e += 2) {
-        float s0, s1;
-        drop_scale2(d, (uint64_t)r * D + c + e, s0, s1);
-        o[e] = from_f32<T>(to_f32((T)v[e]) * s0);
-        o[e + 1] = from_f32<T>(to_f32((T)v[e + 1]) * s1);
-      }
-      *(vec*)(y + r * ldy + c) = o;
-    }
-}
-__global__ void dropout_mask_kernel(int64_t n, DropCfg d, uint8_t* mask) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    mask[i] = drop_scale(d, (uint64_t)i) != 0.f;
-}
-
-template <typename TS, typename TD>
-__global__ void cast_kernel(int64_t n, const TS* s, TD* d) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    d[i] = from_f32<TD>(to_f32(s[i]));
-}
-
-template <typename TS, typename TD>
-__global__ __launch_bounds__(256) void transpose_kernel(int64_t rows, int64_t cols, const TS* s, int64_t lds_, TD* d,
-                                                        int64_t ldd) {
-  __shared__ float tile[32][33];
-  const int64_t r0 = (int64_t)blockIdx.y * 32, c0 = (int64_t)blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int i = ty; i < 32; i += 8)
-    if (r0 + i < rows && c0 + tx < cols) tile[i][tx] = to_f32(s[(r0 + i) * lds_ + c0 + tx]);
-  __syncthreads();
-  for (int i = ty; i < 32; i += 8)
-    if (c0 + i < cols && r0 + tx < rows) d[(c0 + i) * ldd + r0 + tx] = from_f32<TD>(tile[tx][i]);
-}
-
 // MDT_GEMM_STAMP=1: every ping-pong launch is followed by a device sync and one stderr line with the median
 // in-kernel clock and shader cycles per 64-deep K-tile of its main loop (tools/kbench.py; never in production).
 static void report_stamps(unsigned long long* dev, size_t nwg, const GemmParams& p) {
@@ -1250,8 +1149,7 @@ extern "C" int mdt_gemm(void* stream, int dtype, int out_dtype, int trans_a, int
   switch (pl.route) {
     case GemmRoute::generic:
       if (dtype == MDT_F32) return launch_generic<float, float>(st, p, pl.grid, trans_a, trans_b);
-      return out_dtype == MDT_F32 ? launch_generic<bf16_t, float>(st, p, pl.grid, trans_a, trans_b)
-                                  : launch_generic<bf16_t, bf16_t>(st, p, pl.grid, trans_a, trans_b);
+      return with_dtype(out_dtype, [&](auto t) { return launch_generic<bf16_t, typename decltype(t)::type>(st, p, pl.grid, trans_a, trans_b); });
     case GemmRoute::w4s: return launch_w4s(st, p, pl.grid, trans_a, trans_b);
     case GemmRoute::pp256p:
       // MDT_GEMM_DYNAMIC=1: dynamic tile queue instead of the static round-robin walk (in-call A/B on an otherwise idle
@@ -1275,8 +1173,7 @@ extern "C" int mdt_gemm(void* stream, int dtype, int out_dtype, int trans_a, int
       break;
     default: break;
   }
-  const int e = out_dtype == MDT_F32 ? launch_gemm<float>(st, p, pl.route, pl.grid, trans_a, trans_b)
-                                     : launch_gemm<bf16_t>(st, p, pl.route, pl.grid, trans_a, trans_b);
+  const int e = with_dtype(out_dtype, [&](auto t) { return launch_gemm<typename decltype(t)::type>(st, p, pl.route, pl.grid, trans_a, trans_b); });
   if (p.stamps) {
     if (e == MDT_OK) report_stamps(p.stamps, (size_t)pl.grid.x * pl.grid.z, p);
     (void)hipFree(p.stamps);
@@ -1395,85 +1292,4 @@ extern "C" int mdt_gemm_fp8_q8(void* stream, int a_format, int64_t M, int64_t N,
   // only the block-MFMA kernel writes the fp8 copy (and only for the epilogues a training step asks it for): the caller quantises the bf16 output itself
   if (q8_out) MDT_UNSUPPORTED("mdt_gemm_fp8_q8: no kernel writes an fp8 copy for epilogue %d, K = %lld (MDT_GEMM_F8W=%d)", epilogue, (long long)K, switches().gemm_f8w);
   return a_format == 0 ? launch_pp256p_f8<1>((hipStream_t)stream, p) : launch_pp256p_f8<2>((hipStream_t)stream, p);
-}
-
-extern "C" int mdt_colsum(void* stream, int dtype, int64_t M, int64_t N, const void* X, int64_t ldx, float* out,
-                          const int32_t* row_weight) {
-  MDT_CHECK_ARG(dtype == MDT_F32 || dtype == MDT_BF16, "mdt_colsum: dtype %d", dtype);
-  if (M == 0 || N == 0) return MDT_OK;           // nothing to add (an empty X has no address)
-  MDT_CHECK_ARG(X && out, "mdt_colsum: null pointer");
-  note_float_atomic_launch();
-  hipStream_t st = (hipStream_t)stream;
-  const int vn = dtype == MDT_BF16 ? 8 : 4;
-  if (N % vn == 0 && ldx % vn == 0 && ((uintptr_t)X & 15) == 0) {
-    const unsigned gx = (unsigned)((N + 64 * vn - 1) / (64 * vn));
-    int64_t chunks = 2048 / gx;
-    if (chunks < 1) chunks = 1;
-    int rows_per_block = (int)((M + chunks - 1) / chunks);
-    if (rows_per_block < 32) rows_per_block = 32;
-    dim3 grid(gx, (unsigned)((M + rows_per_block - 1) / rows_per_block));
-    if (dtype == MDT_F32) hipLaunchKernelGGL((colsum_vec_kernel<float, 4>), grid, 256, 0, st, M, N, (const float*)X, ldx, out, rows_per_block, row_weight);
-    else hipLaunchKernelGGL((colsum_vec_kernel<bf16_t, 8>), grid, 256, 0, st, M, N, (const bf16_t*)X, ldx, out, rows_per_block, row_weight);
-    return check_launch("colsum_vec");
-  }
-  const int rows_per_block = 512;
-  dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + rows_per_block - 1) / rows_per_block));
-  if (dtype == MDT_F32) hipLaunchKernelGGL((colsum_kernel<float, 256>), grid, 256, 0, st, M, N, (const float*)X, ldx, out, rows_per_block, row_weight);
-  else hipLaunchKernelGGL((colsum_kernel<bf16_t, 256>), grid, 256, 0, st, M, N, (const bf16_t*)X, ldx, out, rows_per_block, row_weight);
-  return check_launch("colsum");
-}
-
-extern "C" int mdt_dropout(void* stream, int dtype, int64_t rows, int D, const void* x, int64_t ldx, void* y, int64_t ldy,
-                           float p_, uint64_t seed) {
-  if (rows == 0 || D == 0) return MDT_OK;
-  MDT_CHECK_ARG(x && y && p_ >= 0.f && p_ < 1.f, "mdt_dropout: bad arguments (p=%f)", p_);
-  hipStream_t st = (hipStream_t)stream;
-  MDT_CHECK_ARG(rows * D < DROP_MAX_ELEMS, "mdt_dropout: site of %lld elements (limit 2^33)", (long long)(rows * D));
-  const DropCfg d = make_drop(p_, seed);
-  const unsigned grid = (unsigned)((rows + 3) / 4 > 8192 ? 8192 : (rows + 3) / 4);
-  const int vn = dtype == MDT_BF16 ? 8 : 4;
-  if (D % vn == 0 && ldx % vn == 0 && ldy % vn == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
-    if (dtype == MDT_F32) hipLaunchKernelGGL((dropout_vec_kernel<float, 4>), grid, 256, 0, st, rows, D, (const float*)x, ldx, (float*)y, ldy, d);
-    else if (dtype == MDT_BF16) hipLaunchKernelGGL((dropout_vec_kernel<bf16_t, 8>), grid, 256, 0, st, rows, D, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, d);
-    else MDT_UNSUPPORTED("mdt_dropout: dtype %d", dtype);
-    return check_launch("dropout_vec");
-  }
-  if (dtype == MDT_F32) hipLaunchKernelGGL((dropout_kernel<float>), grid, 256, 0, st, rows, D, (const float*)x, ldx, (float*)y, ldy, d);
-  else if (dtype == MDT_BF16) hipLaunchKernelGGL((dropout_kernel<bf16_t>), grid, 256, 0, st, rows, D, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, d);
-  else MDT_UNSUPPORTED("mdt_dropout: dtype %d", dtype);
-  return check_launch("dropout");
-}
-
-extern "C" int mdt_dropout_mask(void* stream, int64_t n, float p_, uint64_t seed, uint8_t* mask) {
-  if (n == 0) return MDT_OK;
-  MDT_CHECK_ARG(mask && p_ >= 0.f && p_ < 1.f && n < DROP_MAX_ELEMS, "mdt_dropout_mask: bad arguments");
-  hipLaunchKernelGGL(dropout_mask_kernel, (unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256), 256, 0,
-                     (hipStream_t)stream, n, make_drop(p_, seed), mask);
-  return check_launch("dropout_mask");
-}
-
-extern "C" int mdt_cast(void* stream, int src_dtype, int dst_dtype, int64_t n, const void* src, void* dst) {
-  if (n == 0) return MDT_OK;
-  MDT_CHECK_ARG(src && dst, "mdt_cast: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-  if (src_dtype == MDT_F32 && dst_dtype == MDT_BF16) hipLaunchKernelGGL((cast_kernel<float, bf16_t>), grid, 256, 0, st, n, (const float*)src, (bf16_t*)dst);
-  else if (src_dtype == MDT_BF16 && dst_dtype == MDT_F32) hipLaunchKernelGGL((cast_kernel<bf16_t, float>), grid, 256, 0, st, n, (const bf16_t*)src, (float*)dst);
-  else if (src_dtype == MDT_F32 && dst_dtype == MDT_F32) hipLaunchKernelGGL((cast_kernel<float, float>), grid, 256, 0, st, n, (const float*)src, (float*)dst);
-  else if (src_dtype == MDT_BF16 && dst_dtype == MDT_BF16) hipLaunchKernelGGL((cast_kernel<bf16_t, bf16_t>), grid, 256, 0, st, n, (const bf16_t*)src, (bf16_t*)dst);
-  else MDT_UNSUPPORTED("mdt_cast: dtypes %d -> %d", src_dtype, dst_dtype);
-  return check_launch("cast");
-}
-
-extern "C" int mdt_transpose2d(void* stream, int src_dtype, int dst_dtype, int64_t rows, int64_t cols, const void* src,
-                               int64_t lds_, void* dst, int64_t ldd) {
-  if (rows == 0 || cols == 0) return MDT_OK;
-  MDT_CHECK_ARG(src && dst, "mdt_transpose2d: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32));
-  if (src_dtype == MDT_F32 && dst_dtype == MDT_BF16) hipLaunchKernelGGL((transpose_kernel<float, bf16_t>), grid, 256, 0, st, rows, cols, (const float*)src, lds_, (bf16_t*)dst, ldd);
-  else if (src_dtype == MDT_BF16 && dst_dtype == MDT_BF16) hipLaunchKernelGGL((transpose_kernel<bf16_t, bf16_t>), grid, 256, 0, st, rows, cols, (const bf16_t*)src, lds_, (bf16_t*)dst, ldd);
-  else if (src_dtype == MDT_F32 && dst_dtype == MDT_F32) hipLaunchKernelGGL((transpose_kernel<float, float>), grid, 256, 0, st, rows, cols, (const float*)src, lds_, (float*)dst, ldd);
-  else MDT_UNSUPPORTED("mdt_transpose2d: dtypes %d -> %d", src_dtype, dst_dtype);
-  return check_launch("transpose2d");
 }

@@ -86,7 +86,8 @@ extern "C" int mdt_image_preprocess(void* stream, int n_images, int max_h, const
   dim3 gh((unsigned)((hwork + 255) / 256), (unsigned)n_images);
   hipLaunchKernelGGL(image_resize_h_kernel, gh, 256, 0, st, pixels, desc, plan, tmp, out_size);
   dim3 gv((unsigned)((out_size * out_size + 255) / 256), (unsigned)n_images);
-  if (out_dtype == MDT_F32) hipLaunchKernelGGL((image_resize_v_kernel<float>), gv, 256, 0, st, desc, plan, (const uint8_t*)tmp, lut, (float*)out, out_u8, out_size);
-  else hipLaunchKernelGGL((image_resize_v_kernel<bf16_t>), gv, 256, 0, st, desc, plan, (const uint8_t*)tmp, lut, (bf16_t*)out, out_u8, out_size);
-  return check_launch("image_preprocess");
+  return with_dtype(out_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_plain<image_resize_v_kernel<T>>("image_preprocess", gv, 256, st, desc, plan, (const uint8_t*)tmp, lut, (T*)out, out_u8, out_size);
+  });
 }

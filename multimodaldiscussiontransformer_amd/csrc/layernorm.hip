@@ -16,31 +16,6 @@
 
 namespace mdt {
 
-template <typename T> struct Vec;  // 16-byte vector of T
-template <> struct Vec<float> {
-  static constexpr int N = 4;
-  f32x4 v;
-  __device__ __forceinline__ float get(int i) const { return v[i]; }
-  __device__ __forceinline__ void set(int i, float x) { v[i] = x; }
-};
-template <> struct Vec<bf16_t> {
-  static constexpr int N = 8;
-  bf16x8 v;
-  __device__ __forceinline__ float get(int i) const { return (float)v[i]; }
-  __device__ __forceinline__ void set(int i, float x) { v[i] = (bf16_t)x; }
-};
-
-// 8-byte vectors: D = 768 is 64 lanes x 12 elements = three 8-byte vectors per lane with EVERY lane busy; as 16-byte vectors it is one
-// and a half (the second one on lanes 0-31 only: a quarter of the row's arithmetic slots idle).  Wave instructions still cover
-// 512 contiguous bytes.
-template <typename T> struct VecH;
-template <> struct VecH<bf16_t> {
-  static constexpr int N = 4;
-  bf16x4 v;
-  __device__ __forceinline__ float get(int i) const { return (float)v[i]; }
-  __device__ __forceinline__ void set(int i, float x) { v[i] = (bf16_t)x; }
-};
-
 // One row forward, from the vectors xv a lane holds of it (vector i starts at column (i * 64 + lane) * V::N; vectors past D
 // are absent): mean, variance and rstd over the wave, mean[row] / rstd[row], and y = (x - mean) * rstd * gamma + beta stored
 // to yr.  The one place this arithmetic is written: the plain and the embedding-fused forward agree bit for bit because both
@@ -215,8 +190,7 @@ __global__ __launch_bounds__(256) void bert_embed_ln_rows_kernel(int64_t rows, i
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * VN;
       if (c < D) {
-#pragma unroll
-        for (int j = 0; j < VN; ++j) xv[i].set(j, wv[i].get(j) + tv[i].get(j) + pv[i].get(j));      // the order and the rounding of bert_embed_rows_kernel
+        xv[i] = bert_embed_vec(wv[i], tv[i], pv[i]);
         if (xs) *(V*)(xs + row * ldxs + c) = xv[i];
       }
     }
@@ -662,8 +636,9 @@ extern "C" int mdt_layernorm_fwd(void* stream, int dtype, int64_t rows, int D, c
   if (int e = ln_check(dtype, D, ldx, ldy, x, y)) return e;
   MDT_CHECK_ARG((((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0, "layernorm_fwd: gamma/beta must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  return dtype == MDT_F32 ? ln_fwd_dispatch<float>(st, rows, D, x, ldx, gamma, beta, eps, y, ldy, mean, rstd)
-                          : ln_fwd_dispatch<bf16_t>(st, rows, D, x, ldx, gamma, beta, eps, y, ldy, mean, rstd);
+  return with_dtype(dtype, [&](auto t) {
+    return ln_fwd_dispatch<typename decltype(t)::type>(st, rows, D, x, ldx, gamma, beta, eps, y, ldy, mean, rstd);
+  });
 }
 
 extern "C" int mdt_layernorm_fwd_q8(void* stream, int dtype, int64_t rows, int D, const void* x, int64_t ldx,
@@ -691,8 +666,9 @@ extern "C" int mdt_bert_embed_ln_rows(void* stream, int dtype, int64_t rows, con
   MDT_CHECK_ARG((((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)word | (uintptr_t)pos | (uintptr_t)type) & 15) == 0,
                 "bert_embed_ln_rows: tables, gamma and beta must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  return dtype == MDT_F32 ? embed_ln_dispatch<float>(st, rows, D, ids, types, pos_ids, word, pos, type, gamma, beta, eps, xs, ldxs, y, ldy, mean, rstd)
-                          : embed_ln_dispatch<bf16_t>(st, rows, D, ids, types, pos_ids, word, pos, type, gamma, beta, eps, xs, ldxs, y, ldy, mean, rstd);
+  return with_dtype(dtype, [&](auto t) {
+    return embed_ln_dispatch<typename decltype(t)::type>(st, rows, D, ids, types, pos_ids, word, pos, type, gamma, beta, eps, xs, ldxs, y, ldy, mean, rstd);
+  });
 }
 
 extern "C" int mdt_layernorm_bwd(void* stream, int dtype, int64_t rows, int D, const void* dy, int64_t lddy,
@@ -708,9 +684,9 @@ extern "C" int mdt_layernorm_bwd(void* stream, int dtype, int64_t rows, int D, c
   if (int e = ln_check(dtype, D, lddx, add ? ldadd : lddx, dx, add ? add : dx)) return e;
   if (dgamma || dbeta || colsum) note_float_atomic_launch();
   hipStream_t st = (hipStream_t)stream;
-  return dtype == MDT_F32
-             ? ln_bwd_dispatch<float>(st, rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, dgamma, dbeta, dxd, lddxd, drop, colsum)
-             : ln_bwd_dispatch<bf16_t>(st, rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, dgamma, dbeta, dxd, lddxd, drop, colsum);
+  return with_dtype(dtype, [&](auto t) {
+    return ln_bwd_dispatch<typename decltype(t)::type>(st, rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, dgamma, dbeta, dxd, lddxd, drop, colsum);
+  });
 }
 
 extern "C" size_t mdt_layernorm_bwd_ordered_workspace_bytes(int64_t rows, int D) {
@@ -744,9 +720,9 @@ extern "C" int mdt_layernorm_bwd_ordered(void* stream, int dtype, int64_t rows, 
   float* pb = dbeta ? (float*)workspace + slice : nullptr;
   float* pc = colsum ? (float*)workspace + 2 * slice : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  const int e = dtype == MDT_F32
-                    ? ln_bwd_ordered_dispatch<float>(st, rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, pg, pb, dxd, lddxd, drop, pc)
-                    : ln_bwd_ordered_dispatch<bf16_t>(st, rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, pg, pb, dxd, lddxd, drop, pc);
+  const int e = with_dtype(dtype, [&](auto t) {
+    return ln_bwd_ordered_dispatch<typename decltype(t)::type>(st, rows, D, dy, lddy, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, pg, pb, dxd, lddxd, drop, pc);
+  });
   if (e) return e;
   // workgroup w's partial row is slice w: rows = 1, cols = D, slice stride D
   if (pg) if (int e2 = sum_slices_f32(st, 1, D, (int)grid, pg, D, D, dgamma, D, 1)) return e2;

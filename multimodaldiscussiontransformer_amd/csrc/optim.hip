@@ -211,10 +211,11 @@ static int adam_step_multi(const char* what, void* stream, int dtype, int n_tens
   const float step_size = adam_step_size(lr, beta1, beta2, step);
   const unsigned grid = (unsigned)(total_chunks > 65536 ? 65536 : total_chunks);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDT_F32) hipLaunchKernelGGL((adam_multi_kernel<float, GUARD>), grid, 256, 0, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale, guard);
-  else if (dtype == MDT_BF16) hipLaunchKernelGGL((adam_multi_kernel<bf16_t, GUARD>), grid, 256, 0, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale, guard);
-  else MDT_UNSUPPORTED("%s: dtype %d", what, dtype);
-  return check_launch(what);
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_plain<adam_multi_kernel<T, GUARD>>(what, grid, 256, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay, step_size,
+                                                     grad_scale, guard);
+  });
 }
 
 template <bool GUARD>
@@ -226,10 +227,11 @@ static int adam_step_one(const char* what, void* stream, int dtype, int64_t n, v
   const float step_size = adam_step_size(lr, beta1, beta2, step);
   const unsigned grid = (unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDT_F32) hipLaunchKernelGGL((adam_kernel<float, GUARD>), grid, 256, 0, st, n, (float*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale, guard);
-  else if (dtype == MDT_BF16) hipLaunchKernelGGL((adam_kernel<bf16_t, GUARD>), grid, 256, 0, st, n, (bf16_t*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale, guard);
-  else MDT_UNSUPPORTED("%s: dtype %d", what, dtype);
-  return check_launch(what);
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_plain<adam_kernel<T, GUARD>>(what, grid, 256, st, n, (T*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale,
+                                               guard);
+  });
 }
 
 extern "C" int mdt_adam_step_multi(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,

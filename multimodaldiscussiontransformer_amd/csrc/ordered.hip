@@ -3,10 +3,10 @@
 // stores and ends in ONE fixed-order reducer, sum_slices: the result is a function of the operands alone — not of timing,
 // of the workgroup that ran first, or of another tenant on the card.
 //   sum_slices_kernel         out = (accumulate ? out : 0) + (((ws[0] + ws[1]) + ws[2]) + ...)       one thread per element
-//   colsum_blocks_kernel      column sums of blocks of 256 rows, one partial row per block           (mdt_colsum_ordered)
 //   row_segment_sum_kernel    embedding gradients from CSR segments, one thread per column           (mdt_row_segment_sum_f32)
 //   attn_bias_hist_kernel     structural-bias histograms of a dense dS, one workgroup per (seq, h)   (mdt_attn_bias_grad_ordered)
-// The ordered split-K GEMM and LayerNorm backward live beside their kernels (gemm.hip, gemm_wgrad.hip, layernorm.hip).
+// The ordered split-K GEMM, LayerNorm backward and column sums live beside their kernels (gemm.hip, gemm_wgrad.hip,
+// layernorm.hip, elementwise.hip colsum_kernel<.., ORD>).
 // The build runs with -ffp-contract=off: every add below is one fp32 rounding, no multiply is fused into it.
 #include "common.hpp"
 
@@ -35,29 +35,6 @@ int sum_slices_f32(hipStream_t st, int64_t rows, int64_t cols, int slices, const
   hipLaunchKernelGGL(sum_slices_kernel, (unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, st, rows, cols, slices, ws, ld_ws,
                      slice_stride, out, ldo, accumulate);
   return check_launch("sum_slices");
-}
-
-// Block b = rows 256 b .. 256 b + 255: row lane j (of 4) adds rows j, j + 4, ... of the block in ascending order (each term
-// w * x rounded before its add), the block's partial is ((lane 0 + lane 1) + lane 2) + lane 3.  A fixed tree: 64 columns x 4
-// row lanes per workgroup.
-constexpr int CS_BLOCK_ROWS = 256;
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_blocks_kernel(int64_t M, int64_t N, const T* __restrict__ X, int64_t ldx,
-                                                            const int32_t* __restrict__ row_weight, float* __restrict__ part) {
-  const int64_t c = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
-  const int rl = threadIdx.x >> 6;
-  const int64_t r0 = (int64_t)blockIdx.y * CS_BLOCK_ROWS;
-  const int64_t r1 = r0 + CS_BLOCK_ROWS < M ? r0 + CS_BLOCK_ROWS : M;
-  float s = 0.f;
-  if (c < N)
-    for (int64_t r = r0 + rl; r < r1; r += 4) {
-      const float w = row_weight ? (float)row_weight[r] : 1.f;
-      s += w * to_f32(X[r * ldx + c]);
-    }
-  __shared__ float red[4][64];
-  red[rl][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (rl == 0 && c < N) part[(int64_t)blockIdx.y * N + c] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
 // One thread per (segment, column).  Sources of a segment are taken in the order `order` lists them, in chunks of
@@ -136,28 +113,6 @@ extern "C" int mdt_sum_slices_f32(void* stream, int64_t rows, int64_t cols, int 
   return sum_slices_f32((hipStream_t)stream, rows, cols, slices, ws, ld_ws, slice_stride, out, ldo, accumulate);
 }
 
-extern "C" size_t mdt_colsum_ordered_workspace_bytes(int64_t M, int64_t N) {
-  if (M <= 0 || N <= 0) return 0;
-  return (size_t)((M + CS_BLOCK_ROWS - 1) / CS_BLOCK_ROWS) * (size_t)N * sizeof(float);
-}
-
-extern "C" int mdt_colsum_ordered(void* stream, int dtype, int64_t M, int64_t N, const void* X, int64_t ldx, float* out,
-                                  const int32_t* row_weight, void* workspace, size_t workspace_bytes) {
-  MDT_CHECK_ARG(dtype == MDT_F32 || dtype == MDT_BF16, "mdt_colsum_ordered: dtype %d", dtype);
-  if (M <= 0 || N <= 0) return MDT_OK;
-  MDT_CHECK_ARG(X && out, "mdt_colsum_ordered: null pointer");
-  const size_t need = mdt_colsum_ordered_workspace_bytes(M, N);
-  MDT_CHECK_ARG(workspace && workspace_bytes >= need, "mdt_colsum_ordered: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-  const int64_t blocks = (M + CS_BLOCK_ROWS - 1) / CS_BLOCK_ROWS;
-  MDT_CHECK_ARG(blocks <= 65535, "mdt_colsum_ordered: %lld rows (limit %d)", (long long)M, 65535 * CS_BLOCK_ROWS);
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((N + 63) / 64), (unsigned)blocks);
-  if (dtype == MDT_F32) hipLaunchKernelGGL((colsum_blocks_kernel<float>), grid, 256, 0, st, M, N, (const float*)X, ldx, row_weight, (float*)workspace);
-  else hipLaunchKernelGGL((colsum_blocks_kernel<bf16_t>), grid, 256, 0, st, M, N, (const bf16_t*)X, ldx, row_weight, (float*)workspace);
-  if (int e = check_launch("colsum_ordered")) return e;
-  return sum_slices_f32(st, 1, N, (int)blocks, (const float*)workspace, N, N, out, N, 1);
-}
-
 extern "C" int mdt_row_segment_sum_f32(void* stream, int dtype, int nseg, int D, float* table, int64_t ldt, const int32_t* seg_row,
                                        const int32_t* seg_off, const int32_t* order, const void* src, int64_t lds_,
                                        int64_t s_stride, int64_t s_off) {
@@ -167,9 +122,10 @@ extern "C" int mdt_row_segment_sum_f32(void* stream, int dtype, int nseg, int D,
   MDT_CHECK_ARG((D + 255) / 256 <= 65535, "mdt_row_segment_sum: D=%d too wide", D);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)nseg, (unsigned)((D + 255) / 256));
-  if (dtype == MDT_F32) hipLaunchKernelGGL((row_segment_sum_kernel<float>), grid, 256, 0, st, D, table, ldt, seg_row, seg_off, order, (const float*)src, lds_, s_stride, s_off);
-  else hipLaunchKernelGGL((row_segment_sum_kernel<bf16_t>), grid, 256, 0, st, D, table, ldt, seg_row, seg_off, order, (const bf16_t*)src, lds_, s_stride, s_off);
-  return check_launch("row_segment_sum");
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_plain<row_segment_sum_kernel<T>>("row_segment_sum", grid, 256, st, D, table, ldt, seg_row, seg_off, order, (const T*)src, lds_, s_stride, s_off);
+  });
 }
 
 extern "C" size_t mdt_attn_bias_grad_ordered_workspace_bytes(int nseq, int H, int num_spatial) {

@@ -7,9 +7,13 @@
 
 namespace mdt {
 
-template <typename T> struct V16;
-template <> struct V16<float> { static constexpr int N = 4; typedef f32x4 type; };
-template <> struct V16<bf16_t> { static constexpr int N = 8; typedef bf16x8 type; };
+// The skeleton of every row mover: a 256-thread workgroup is four wavefronts, one row each.  Returns the wave's row, or -1
+// when it lies past the last one, and the lane within the wave.
+__device__ __forceinline__ int64_t wave_row(int64_t nrows, int& lane) {
+  lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  return r < nrows ? r : -1;
+}
 
 __device__ __forceinline__ int64_t pick_row(const int32_t* idx, int64_t inner, int64_t stride, int64_t off, int64_t r) {
   if (idx) return (int64_t)idx[r];
@@ -18,59 +22,43 @@ __device__ __forceinline__ int64_t pick_row(const int32_t* idx, int64_t inner, i
   return q * stride + (r - q * inner) + off;
 }
 
-// scalar variant for rows that are not 16-byte vectorisable (e.g. the [M, 2] logits)
-template <typename T>
-__global__ __launch_bounds__(256) void row_axpby_scalar_kernel(int64_t nrows, int D, T* dst, int64_t ldd, const int32_t* di,
-                                                               int64_t d_inner, int64_t d_stride, int64_t d_off, const T* a,
-                                                               int64_t lda, const int32_t* ai, int64_t a_inner,
-                                                               int64_t a_stride, int64_t a_off, float alpha, const T* b,
-                                                               int64_t ldb, const int32_t* bi, int64_t b_inner,
-                                                               int64_t b_stride, int64_t b_off, float beta, int accumulate) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= nrows) return;
-  const int64_t dr = pick_row(di, d_inner, d_stride, d_off, r);
-  if (dr < 0) return;
-  const int64_t ar = a ? pick_row(ai, a_inner, a_stride, a_off, r) : -1;
-  const int64_t br = b ? pick_row(bi, b_inner, b_stride, b_off, r) : -1;
-  for (int c = lane; c < D; c += 64) {
-    float v = 0.f;
-    if (ar >= 0) v += alpha * to_f32(a[ar * lda + c]);
-    if (br >= 0) v += beta * to_f32(b[br * ldb + c]);
-    if (accumulate) v += to_f32(dst[dr * ldd + c]);
-    dst[dr * ldd + c] = from_f32<T>(v);
-  }
-}
-
-template <typename T>
+// dst[dr] = alpha * a[ar] + beta * b[br] (+ dst[dr]): VN = Vec<T>::N with 16-byte accesses, VN = 1 for rows that are not
+// vectorisable (e.g. the [M, 2] logits).  Both forms add the terms of an element in the same order.
+template <typename T, int VN>
 __global__ __launch_bounds__(256) void row_axpby_kernel(int64_t nrows, int D, T* dst, int64_t ldd, const int32_t* di,
                                                         int64_t d_inner, int64_t d_stride, int64_t d_off, const T* a, int64_t lda,
                                                         const int32_t* ai, int64_t a_inner, int64_t a_stride, int64_t a_off, float alpha,
                                                         const T* b, int64_t ldb, const int32_t* bi, int64_t b_inner, int64_t b_stride,
                                                         int64_t b_off, float beta, int accumulate) {
-  constexpr int VN = V16<T>::N;
-  typedef typename V16<T>::type vec;
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= nrows) return;
+  int lane;
+  const int64_t r = wave_row(nrows, lane);
+  if (r < 0) return;
   const int64_t dr = pick_row(di, d_inner, d_stride, d_off, r);
   if (dr < 0) return;
   const int64_t ar = a ? pick_row(ai, a_inner, a_stride, a_off, r) : -1;
   const int64_t br = b ? pick_row(bi, b_inner, b_stride, b_off, r) : -1;
   for (int c = lane * VN; c < D; c += 64 * VN) {
-    vec va, vb, vd, o;
-    if (ar >= 0) va = *(const vec*)(a + ar * lda + c);
-    if (br >= 0) vb = *(const vec*)(b + br * ldb + c);
-    if (accumulate) vd = *(const vec*)(dst + dr * ldd + c);
-#pragma unroll
-    for (int j = 0; j < VN; ++j) {
+    if constexpr (VN == 1) {
       float v = 0.f;
-      if (ar >= 0) v += alpha * to_f32((T)va[j]);
-      if (br >= 0) v += beta * to_f32((T)vb[j]);
-      if (accumulate) v += to_f32((T)vd[j]);
-      o[j] = from_f32<T>(v);
+      if (ar >= 0) v += alpha * to_f32(a[ar * lda + c]);
+      if (br >= 0) v += beta * to_f32(b[br * ldb + c]);
+      if (accumulate) v += to_f32(dst[dr * ldd + c]);
+      dst[dr * ldd + c] = from_f32<T>(v);
+    } else {
+      Vec<T> va, vb, vd, o;
+      if (ar >= 0) va = *(const Vec<T>*)(a + ar * lda + c);
+      if (br >= 0) vb = *(const Vec<T>*)(b + br * ldb + c);
+      if (accumulate) vd = *(const Vec<T>*)(dst + dr * ldd + c);
+#pragma unroll
+      for (int j = 0; j < VN; ++j) {
+        float v = 0.f;
+        if (ar >= 0) v += alpha * va.get(j);
+        if (br >= 0) v += beta * vb.get(j);
+        if (accumulate) v += vd.get(j);
+        o.set(j, v);
+      }
+      *(Vec<T>*)(dst + dr * ldd + c) = o;
     }
-    *(vec*)(dst + dr * ldd + c) = o;
   }
 }
 
@@ -78,59 +66,42 @@ template <typename T>
 __global__ __launch_bounds__(256) void row_scatter_add_kernel(int64_t nrows, int D, float* table, int64_t ldt,
                                                               const int32_t* idx, const T* src, int64_t lds_,
                                                               int64_t s_stride, int64_t s_off) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= nrows) return;
+  int lane;
+  const int64_t r = wave_row(nrows, lane);
+  if (r < 0) return;
   const int64_t t = idx[r];
   if (t < 0) return;
   const T* s = src + (r * s_stride + s_off) * lds_;
   for (int c = lane; c < D; c += 64) atomicAdd(table + t * ldt + c, to_f32(s[c]));
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void bert_embed_sum_kernel(int64_t M, int L, const int32_t* ids, const int32_t* types,
-                                                             const T* word, const T* pos, const T* type, int D, T* out,
-                                                             int64_t ldo, int64_t out_seq_stride, int64_t out_off) {
-  constexpr int VN = V16<T>::N;
-  typedef typename V16<T>::type vec;
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= M * L) return;
-  const int64_t m = r / L;
-  const int l = (int)(r - m * L);
-  const int64_t w = ids[r], t = types[r];
-  T* o = out + (m * out_seq_stride + out_off + l) * ldo;
-  for (int c = lane * VN; c < D; c += 64 * VN) {
-    const vec vw = *(const vec*)(word + w * D + c);
-    const vec vp = *(const vec*)(pos + (int64_t)l * D + c);
-    const vec vt = *(const vec*)(type + t * D + c);
-    vec ov;
-#pragma unroll
-    for (int j = 0; j < VN; ++j) ov[j] = from_f32<T>(to_f32((T)vw[j]) + to_f32((T)vt[j]) + to_f32((T)vp[j]));
-    *(vec*)(o + c) = ov;
+// BERT embeddings, one token per wave: out row = word[ids] + type[types] + pos[l] (bert_embed_vec).
+//   RAGGED = false: token r = (m, l) of M padded sequences of L, out row m * out_seq_stride + out_off + l   (mdt_bert_embed_sum)
+//   RAGGED = true:  one packed row per VALID token, l = pos_ids[r], out row r                                (mdt_bert_embed_rows)
+template <typename T, bool RAGGED>
+__global__ __launch_bounds__(256) void bert_embed_kernel(int64_t rows, int L, const int32_t* ids, const int32_t* types,
+                                                         const int32_t* pos_ids, const T* word, const T* pos, const T* type, int D,
+                                                         T* out, int64_t ldo, int64_t out_seq_stride, int64_t out_off) {
+  typedef Vec<T> V;
+  int lane;
+  const int64_t r = wave_row(rows, lane);
+  if (r < 0) return;
+  int64_t l, orow;
+  if constexpr (RAGGED) {
+    l = pos_ids[r];
+    orow = r;
+  } else {
+    const int64_t m = r / L;
+    l = r - m * L;
+    orow = m * out_seq_stride + out_off + l;
   }
-}
-
-// ragged form: one packed row per VALID token, explicit position ids
-template <typename T>
-__global__ __launch_bounds__(256) void bert_embed_rows_kernel(int64_t rows, const int32_t* ids, const int32_t* types,
-                                                              const int32_t* pos_ids, const T* word, const T* pos, const T* type,
-                                                              int D, T* out, int64_t ldo) {
-  constexpr int VN = V16<T>::N;
-  typedef typename V16<T>::type vec;
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const int64_t w = ids[r], t = types[r], l = pos_ids[r];
-  T* o = out + r * ldo;
-  for (int c = lane * VN; c < D; c += 64 * VN) {
-    const vec vw = *(const vec*)(word + w * D + c);
-    const vec vp = *(const vec*)(pos + l * D + c);
-    const vec vt = *(const vec*)(type + t * D + c);
-    vec ov;
-#pragma unroll
-    for (int j = 0; j < VN; ++j) ov[j] = from_f32<T>(to_f32((T)vw[j]) + to_f32((T)vt[j]) + to_f32((T)vp[j]));
-    *(vec*)(o + c) = ov;
+  const int64_t w = ids[r], t = types[r];
+  T* o = out + orow * ldo;
+  for (int c = lane * V::N; c < D; c += 64 * V::N) {
+    const V vw = *(const V*)(word + w * D + c);
+    const V vp = *(const V*)(pos + l * D + c);
+    const V vt = *(const V*)(type + t * D + c);
+    *(V*)(o + c) = bert_embed_vec(vw, vt, vp);
   }
 }
 
@@ -156,9 +127,9 @@ template <typename T>
 __global__ __launch_bounds__(256) void vit_assemble_kernel(int I, int np, int D, const T* patches, int64_t ldp,
                                                            const T* cls, const T* pos, T* tokens, int64_t ldt,
                                                            int64_t seq_stride, int64_t off) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= (int64_t)I * (np + 1)) return;
+  int lane;
+  const int64_t r = wave_row((int64_t)I * (np + 1), lane);
+  if (r < 0) return;
   const int64_t i = r / (np + 1);
   const int j = (int)(r - i * (np + 1));
   T* o = tokens + (i * seq_stride + off + j) * ldt;
@@ -172,9 +143,9 @@ __global__ __launch_bounds__(256) void graph_node_feature_kernel(int B, int Tn, 
                                                                  const int32_t* out_degree,
                                                                  const T* in_emb, const T* out_emb, const T* graph_token,
                                                                  T* x, int64_t ldx) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= (int64_t)B * Tn) return;
+  int lane;
+  const int64_t r = wave_row((int64_t)B * Tn, lane);
+  if (r < 0) return;
   const int64_t b = r / Tn;
   const int t = (int)(r - b * Tn);
   T* o = x + r * ldx;
@@ -320,16 +291,10 @@ __global__ __launch_bounds__(256) void node_ce_kernel(int64_t M, int nlab, const
 
 using namespace mdt;
 
-#define DISPATCH_T(dtype, NAME, ...)                                  \
-  if ((dtype) == MDT_F32) { NAME(float, __VA_ARGS__); }               \
-  else if ((dtype) == MDT_BF16) { NAME(bf16_t, __VA_ARGS__); }        \
-  else MDT_UNSUPPORTED("dtype %d", (dtype))
-
-static int vec_ok(int dtype, int D, int64_t ld, const void* p) {
-  const int vn = dtype == MDT_BF16 ? 8 : 4;
-  MDT_CHECK_ARG(D % vn == 0 && ld % vn == 0 && ((uintptr_t)p & 15) == 0,
-                "row op: D=%d / ld=%lld / pointer not 16-byte vectorisable", D, (long long)ld);
-  return MDT_OK;
+// the launch that goes with wave_row: four rows per 256-thread workgroup
+template <auto Kern, typename... Args>
+static int launch_rows(const char* name, hipStream_t st, int64_t nrows, Args... args) {
+  return launch_plain<Kern>(name, (unsigned)((nrows + 3) / 4), 256, st, args...);
 }
 
 extern "C" int mdt_row_axpby(void* stream, int dtype, int64_t nrows, int D, void* dst, int64_t ldd, const int32_t* di,
@@ -339,22 +304,16 @@ extern "C" int mdt_row_axpby(void* stream, int dtype, int64_t nrows, int D, void
   if (nrows == 0) return MDT_OK;
   MDT_CHECK_ARG(dst, "row_axpby: null dst");
   MDT_CHECK_ARG(dtype == MDT_F32 || dtype == MDT_BF16, "row_axpby: bad dtype %d", dtype);
-  const int vn = dtype == MDT_BF16 ? 8 : 4;
-  bool vec = D % vn == 0 && ldd % vn == 0 && ((uintptr_t)dst & 15) == 0;
-  if (a) vec = vec && lda % vn == 0 && ((uintptr_t)a & 15) == 0;
-  if (b) vec = vec && ldb % vn == 0 && ((uintptr_t)b & 15) == 0;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((nrows + 3) / 4);
-#define ARGS_(T) nrows, D, (T*)dst, ldd, di, d_inner, d_stride, d_off, (const T*)a, lda, ai, a_inner, a_stride, a_off, alpha, (const T*)b, ldb, bi, b_inner, b_stride, b_off, beta, accumulate
-  if (vec) {
-    if (dtype == MDT_F32) hipLaunchKernelGGL((row_axpby_kernel<float>), grid, 256, 0, st, ARGS_(float));
-    else hipLaunchKernelGGL((row_axpby_kernel<bf16_t>), grid, 256, 0, st, ARGS_(bf16_t));
-  } else {
-    if (dtype == MDT_F32) hipLaunchKernelGGL((row_axpby_scalar_kernel<float>), grid, 256, 0, st, ARGS_(float));
-    else hipLaunchKernelGGL((row_axpby_scalar_kernel<bf16_t>), grid, 256, 0, st, ARGS_(bf16_t));
-  }
-#undef ARGS_
-  const int e = check_launch("row_axpby");
+  const bool vec = vec16_ok(dtype, D, {ldd, a ? lda : 0, b ? ldb : 0}, {dst, a, b});
+  const int e = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto launch = [&](auto vn) {
+      return launch_rows<row_axpby_kernel<T, decltype(vn)::value>>("row_axpby", (hipStream_t)stream, nrows, nrows, D, (T*)dst, ldd, di, d_inner, d_stride,
+                                                                   d_off, (const T*)a, lda, ai, a_inner, a_stride, a_off, alpha, (const T*)b, ldb, bi,
+                                                                   b_inner, b_stride, b_off, beta, accumulate);
+    };
+    return vec ? launch(std::integral_constant<int, Vec<T>::N>{}) : launch(std::integral_constant<int, 1>{});
+  });
   if (e == MDT_OK) set_last_route(vec ? "row_vec" : "row_scalar");
   return e;
 }
@@ -364,63 +323,58 @@ extern "C" int mdt_row_scatter_add_f32(void* stream, int dtype, int64_t nrows, i
   if (nrows == 0) return MDT_OK;
   MDT_CHECK_ARG(table && idx && src, "row_scatter_add: null pointer");
   note_float_atomic_launch();
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((nrows + 3) / 4);
-#define K_(T, ...) hipLaunchKernelGGL((row_scatter_add_kernel<T>), grid, 256, 0, st, nrows, D, table, ldt, idx, (const T*)src, lds_, s_stride, s_off)
-  DISPATCH_T(dtype, K_, 0);
-#undef K_
-  return check_launch("row_scatter_add");
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_rows<row_scatter_add_kernel<T>>("row_scatter_add", (hipStream_t)stream, nrows, nrows, D, table, ldt, idx, (const T*)src, lds_, s_stride, s_off);
+  });
+}
+
+// mdt_bert_embed_sum (padded: pos_ids null, rows = M * L) and mdt_bert_embed_rows (ragged: L, out_seq_stride, out_off unused)
+template <bool RAGGED>
+static int bert_embed(const char* name, void* stream, int dtype, int64_t rows, int L, const int32_t* ids, const int32_t* types,
+                      const int32_t* pos_ids, const void* word, const void* pos, const void* type, int D, void* out, int64_t ldo,
+                      int64_t out_seq_stride, int64_t out_off) {
+  MDT_CHECK_ARG(ids && types && (pos_ids || !RAGGED) && word && pos && type && out, "%s: null pointer", name);
+  MDT_CHECK_ARG(vec16_ok(dtype, D, {ldo}, {out}), "row op: D=%d / ld=%lld / pointer not 16-byte vectorisable", D, (long long)ldo);
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_rows<bert_embed_kernel<T, RAGGED>>(name, (hipStream_t)stream, rows, rows, L, ids, types, pos_ids, (const T*)word, (const T*)pos,
+                                                     (const T*)type, D, (T*)out, ldo, out_seq_stride, out_off);
+  });
 }
 
 extern "C" int mdt_bert_embed_sum(void* stream, int dtype, int64_t M, int L, const int32_t* ids, const int32_t* types,
                                   const void* word, const void* pos, const void* type, int D, void* out, int64_t ldo,
                                   int64_t out_seq_stride, int64_t out_off) {
   if (M == 0) return MDT_OK;
-  MDT_CHECK_ARG(ids && types && word && pos && type && out, "bert_embed_sum: null pointer");
-  if (int e = vec_ok(dtype, D, ldo, out)) return e;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((M * L + 3) / 4);
-#define K_(T, ...) hipLaunchKernelGGL((bert_embed_sum_kernel<T>), grid, 256, 0, st, M, L, ids, types, (const T*)word, (const T*)pos, (const T*)type, D, (T*)out, ldo, out_seq_stride, out_off)
-  DISPATCH_T(dtype, K_, 0);
-#undef K_
-  return check_launch("bert_embed_sum");
+  return bert_embed<false>("bert_embed_sum", stream, dtype, M * L, L, ids, types, nullptr, word, pos, type, D, out, ldo, out_seq_stride, out_off);
 }
 
 extern "C" int mdt_bert_embed_rows(void* stream, int dtype, int64_t rows, const int32_t* ids, const int32_t* types,
                                    const int32_t* pos_ids, const void* word, const void* pos, const void* type, int D,
                                    void* out, int64_t ldo) {
   if (rows == 0) return MDT_OK;
-  MDT_CHECK_ARG(ids && types && pos_ids && word && pos && type && out, "bert_embed_rows: null pointer");
-  if (int e = vec_ok(dtype, D, ldo, out)) return e;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)((rows + 3) / 4);
-#define K_(T, ...) hipLaunchKernelGGL((bert_embed_rows_kernel<T>), grid, 256, 0, st, rows, ids, types, pos_ids, (const T*)word, (const T*)pos, (const T*)type, D, (T*)out, ldo)
-  DISPATCH_T(dtype, K_, 0);
-#undef K_
-  return check_launch("bert_embed_rows");
+  return bert_embed<true>("bert_embed_rows", stream, dtype, rows, 0, ids, types, pos_ids, word, pos, type, D, out, ldo, 0, 0);
 }
 
 extern "C" int mdt_vit_patchify(void* stream, int dtype, int I, int C, int HW, int p, const float* img, void* cols, int64_t ldc) {
   if (I == 0) return MDT_OK;
   MDT_CHECK_ARG(img && cols && p > 0 && HW % p == 0, "vit_patchify: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(HW / p, I);
-#define K_(T, ...) hipLaunchKernelGGL((vit_patchify_kernel<T>), grid, 256, 0, st, I, C, HW, p, img, (T*)cols, ldc)
-  DISPATCH_T(dtype, K_, 0);
-#undef K_
-  return check_launch("vit_patchify");
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_plain<vit_patchify_kernel<T>>("vit_patchify", dim3(HW / p, I), 256, (hipStream_t)stream, I, C, HW, p, img, (T*)cols, ldc);
+  });
 }
 
 extern "C" int mdt_vit_assemble(void* stream, int dtype, int I, int np, int D, const void* patches, int64_t ldp,
                                 const void* cls, const void* pos, void* tokens, int64_t ldt, int64_t seq_stride, int64_t off) {
   if (I == 0) return MDT_OK;
   MDT_CHECK_ARG(patches && cls && pos && tokens, "vit_assemble: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)(((int64_t)I * (np + 1) + 3) / 4);
-#define K_(T, ...) hipLaunchKernelGGL((vit_assemble_kernel<T>), grid, 256, 0, st, I, np, D, (const T*)patches, ldp, (const T*)cls, (const T*)pos, (T*)tokens, ldt, seq_stride, off)
-  DISPATCH_T(dtype, K_, 0);
-#undef K_
-  return check_launch("vit_assemble");
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_rows<vit_assemble_kernel<T>>("vit_assemble", (hipStream_t)stream, (int64_t)I * (np + 1), I, np, D, (const T*)patches, ldp, (const T*)cls,
+                                               (const T*)pos, (T*)tokens, ldt, seq_stride, off);
+  });
 }
 
 extern "C" int mdt_graph_node_feature(void* stream, int dtype, int B, int T, int D, const void* src, int64_t lds_,
@@ -429,32 +383,30 @@ extern "C" int mdt_graph_node_feature(void* stream, int dtype, int B, int T, int
                                       int64_t ldx) {
   if (B == 0) return MDT_OK;
   MDT_CHECK_ARG(node_row && in_degree && out_degree && in_emb && out_emb && graph_token && x, "graph_node_feature: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = (unsigned)(((int64_t)B * T + 3) / 4);
-#define K_(T_, ...) hipLaunchKernelGGL((graph_node_feature_kernel<T_>), grid, 256, 0, st, B, T, D, (const T_*)src, lds_, node_row, in_degree, out_degree, (const T_*)in_emb, (const T_*)out_emb, (const T_*)graph_token, (T_*)x, ldx)
-  DISPATCH_T(dtype, K_, 0);
-#undef K_
-  return check_launch("graph_node_feature");
+  return with_dtype(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    return launch_rows<graph_node_feature_kernel<E>>("graph_node_feature", (hipStream_t)stream, (int64_t)B * T, B, T, D, (const E*)src, lds_, node_row,
+                                                     in_degree, out_degree, (const E*)in_emb, (const E*)out_emb, (const E*)graph_token, (E*)x, ldx);
+  });
 }
+
+// flat grid-stride launches of the pooler tanh: up to 2048 workgroups of 256
+static unsigned tanh_grid(int64_t n) { return (unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256); }
 
 extern "C" int mdt_tanh_fwd(void* stream, int dtype, int64_t n, const void* x, void* y) {
   if (n == 0) return MDT_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = (int)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-#define K_(T, ...) hipLaunchKernelGGL((tanh_fwd_kernel<T>), grid, 256, 0, st, n, (const T*)x, (T*)y)
-  DISPATCH_T(dtype, K_, 0);
-#undef K_
-  return check_launch("tanh_fwd");
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_plain<tanh_fwd_kernel<T>>("tanh_fwd", tanh_grid(n), 256, (hipStream_t)stream, n, (const T*)x, (T*)y);
+  });
 }
 
 extern "C" int mdt_tanh_bwd(void* stream, int dtype, int64_t n, const void* y, const void* dy, void* dx) {
   if (n == 0) return MDT_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = (int)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-#define K_(T, ...) hipLaunchKernelGGL((tanh_bwd_kernel<T>), grid, 256, 0, st, n, (const T*)y, (const T*)dy, (T*)dx)
-  DISPATCH_T(dtype, K_, 0);
-#undef K_
-  return check_launch("tanh_bwd");
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_plain<tanh_bwd_kernel<T>>("tanh_bwd", tanh_grid(n), 256, (hipStream_t)stream, n, (const T*)y, (const T*)dy, (T*)dx);
+  });
 }
 
 extern "C" int mdt_node_ce(void* stream, int dtype, int64_t M, int nlab, const void* logits, const int32_t* rows,
@@ -470,8 +422,9 @@ extern "C" int mdt_node_ce(void* stream, int dtype, int64_t M, int nlab, const v
       return MDT_ERR_LAUNCH;
     }
   }
-#define K_(T, ...) hipLaunchKernelGGL((node_ce_kernel<T>), 1, 256, 0, st, M, nlab, (const T*)logits, rows, targets, w_neg, w_pos, fp16_loss, grad_scale, out_loss, counters, (T*)dlogits)
-  DISPATCH_T(dtype, K_, 0);
-#undef K_
-  return check_launch("node_ce");
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_plain<node_ce_kernel<T>>("node_ce", 1, 256, st, M, nlab, (const T*)logits, rows, targets, w_neg, w_pos, fp16_loss, grad_scale, out_loss,
+                                           counters, (T*)dlogits);
+  });
 }

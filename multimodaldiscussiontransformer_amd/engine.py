@@ -223,6 +223,18 @@ class Tape:
         if not self.inference:                     # the closure keeps every saved activation alive
             self.ops.append(bwd)
 
+    def adjoint(self, o: "Var", bwd: Callable[[torch.Tensor], None], take: bool = True):
+        """Record ``bwd(g)`` as the adjoint of the op that made ``o``.  The backward pass calls it with ``g = o.grad``, taken
+        out of ``o`` first (``take=False``: left there), and skips it when nothing contributed a gradient to ``o``."""
+        def run():
+            g = o.grad
+            if take:
+                o.grad = None
+            if g is not None:
+                bwd(g)
+
+        self.record(run)
+
     def pgrad(self, p: torch.nn.Parameter) -> Optional[torch.Tensor]:
         """fp32 accumulation buffer of a parameter, or None when it is frozen."""
         if p is None or not p.requires_grad:
@@ -541,11 +553,7 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
         wgrad(tape, dqkv, a_in, P.qkv_w, P.qkv_b)
         return dgrad(dqkv, P.qkv_w, residual=None if dres is None else spread(dres)) if want_dx else None
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         ride = _WGRAD_ASUM and dyd_rides(g)     # bias gradients ride on the weight-gradient GEMMs (wgrad) where they can
         if not pre_ln:
             dy, dyd = _ln_bwd_dense(tape, g, y, P.ln2_w, P.ln2_b, m2, r2, None if ride else P.fc2_b, p_hidden, s_f2)
@@ -566,7 +574,7 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
         if tape.on_params_ready:
             tape.on_params_ready(P.all())
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -617,18 +625,14 @@ def attention_layer(tape: Tape, x: Var, qkv_w, qkv_b, o_w, o_b, spec: AttnSpec, 
     out = ops.gemm(ctx, o_w.data, bias=None if o_b is None else o_b.data)
     o = Var(out)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         wgrad(tape, g, ctx, o_w, o_b)
         dqkv = _attention_bwd(tape, spec, kw, ops.gemm(g, o_w.data, trans_b=True), qkv, ctx, lse)
         wgrad(tape, dqkv, xd, qkv_w, qkv_b)
         if x.needs_grad:
             tape.add_grad(x, ops.gemm(dqkv, qkv_w.data, trans_b=True))
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -636,15 +640,11 @@ def layernorm(tape: Tape, x: Var, w, b, eps: float) -> Var:
     y, mean, rstd = ops.layernorm_fwd(x.data, w.data, b.data, eps)
     o = Var(y)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         dx = _ln_bwd(tape, g, x.data, w, b, mean, rstd)
         tape.add_grad(x, dx)
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -655,14 +655,10 @@ def dropout(tape: Tape, x: Var, p: float) -> Var:
     seed = tape.next_seed()
     o = Var(ops.dropout(x.data, p, seed))
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         tape.add_grad(x, ops.dropout(g, p, seed))
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -674,40 +670,39 @@ def bert_embeddings(tape: Tape, ids, types, word, pos, typ) -> Var:
     ops.bert_embed_sum(ids, types, word.data, pos.data, typ.data, out, out_seq_stride=Lq, out_off=0)
     o = Var(out)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
-        gw, gp, gt = tape.pgrad(word), tape.pgrad(pos), tape.pgrad(typ)
+    def bwd(g):
+        gw, gp = tape.pgrad(word), tape.pgrad(pos)
         if gw is not None:
             scatter_add(gw, ids.view(-1), g, M * Lq)
         if gp is not None:
             colsum(g.view(M, Lq * D), out=gp[:Lq].view(-1))
-        if gt is not None:
-            assert typ.shape[0] == 2, "token-type gradient is implemented for type_vocab_size == 2"
-            tot = colsum(g)
-            one = colsum(g, row_weight=types.view(-1))
-            ops.row_axpby(gt, 1, d_off=1, a=one.view(1, D), accumulate=True)
-            ops.row_axpby(gt, 1, d_off=0, a=tot.view(1, D), b=one.view(1, D), beta=-1.0, accumulate=True)
+        _type_emb_grad(tape, g, types.view(-1), typ)
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
+def _type_emb_grad(tape: Tape, g, types, typ):
+    """Token-type embedding gradient of the rows ``g`` (``types`` i32[rows], two types): row 1 gets the column sums of the
+    type-1 rows, row 0 the column sums of all rows minus those."""
+    gt = tape.pgrad(typ)
+    if gt is None:
+        return
+    assert typ.shape[0] == 2, "token-type gradient is implemented for type_vocab_size == 2"
+    D = g.shape[1]
+    tot = colsum(g)
+    one = colsum(g, row_weight=types)
+    ops.row_axpby(gt, 1, d_off=1, a=one.view(1, D), accumulate=True)
+    ops.row_axpby(gt, 1, d_off=0, a=tot.view(1, D), b=one.view(1, D), beta=-1.0, accumulate=True)
+
+
 def _embed_rows_grads(tape: Tape, g, rows, ids, types, pos_ids, word, pos, typ):
-    gw, gp, gt = tape.pgrad(word), tape.pgrad(pos), tape.pgrad(typ)
-    D = word.shape[1]
+    gw, gp = tape.pgrad(word), tape.pgrad(pos)
     if gw is not None:
         scatter_add(gw, ids, g, rows)
     if gp is not None:
         scatter_add(gp, pos_ids, g, rows)
-    if gt is not None:
-        assert typ.shape[0] == 2, "token-type gradient is implemented for type_vocab_size == 2"
-        tot = colsum(g)
-        one = colsum(g, row_weight=types)
-        ops.row_axpby(gt, 1, d_off=1, a=one.view(1, D), accumulate=True)
-        ops.row_axpby(gt, 1, d_off=0, a=tot.view(1, D), b=one.view(1, D), beta=-1.0, accumulate=True)
+    _type_emb_grad(tape, g, types, typ)
 
 
 def bert_embeddings_rows(tape: Tape, ids, types, pos_ids, word, pos, typ) -> Var:
@@ -718,14 +713,10 @@ def bert_embeddings_rows(tape: Tape, ids, types, pos_ids, word, pos, typ) -> Var
     ops.bert_embed_rows(ids, types, pos_ids, word.data, pos.data, typ.data, out)
     o = Var(out)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         _embed_rows_grads(tape, g, rows, ids, types, pos_ids, word, pos, typ)
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -737,15 +728,11 @@ def bert_embeddings_ln_rows(tape: Tape, ids, types, pos_ids, word, pos, typ, w, 
                                                keep_sum=not tape.inference)
     o = Var(y)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         dx = _ln_bwd(tape, g, xs, w, b, mean, rstd)
         _embed_rows_grads(tape, dx, rows, ids, types, pos_ids, word, pos, typ)
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -777,11 +764,7 @@ def vit_embeddings(tape: Tape, images, proj_w, proj_b, cls, pos, patch: int) -> 
                          seq_stride=npatch + 1, off=0)
     o = Var(tokens)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         gw, gb, gc, gp = tape.pgrad(proj_w), tape.pgrad(proj_b), tape.pgrad(cls), tape.pgrad(pos)
         if gw is not None or gb is not None:
             dpatch = torch.empty(I * npatch, D, dtype=g.dtype, device=g.device)
@@ -799,7 +782,7 @@ def vit_embeddings(tape: Tape, images, proj_w, proj_b, cls, pos, patch: int) -> 
         if gc is not None:
             colsum(g.view(I, (npatch + 1) * D)[:, :D], out=gc.view(-1))
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -818,11 +801,7 @@ def expand_sequences(tape: Tape, x: Var, nseq: int, s_in: int, n_front: int, fro
         ops.row_axpby(out, nseq * n_front, d_inner=n_front, d_stride=S, d_off=0)
     o = Var(out)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         if front is not None and tape.pgrad(front) is not None:
             colsum(g.view(nseq, S * D)[:, : n_front * D], out=tape.pgrad(front).view(-1))
         if x.needs_grad:
@@ -830,7 +809,7 @@ def expand_sequences(tape: Tape, x: Var, nseq: int, s_in: int, n_front: int, fro
             ops.row_axpby(dx, nseq * s_in, a=g, a_inner=s_in, a_stride=S, a_off=n_front)
             tape.add_grad(x, dx)
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -847,11 +826,7 @@ def expand_rows(tape: Tape, x: Var, rows_out: int, body_idx, front_idx, n_front:
     ops.row_axpby(out, nfront, di=front_idx, a=front.data, a_inner=n_front, a_stride=0, a_off=0)
     o = Var(out)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         gf = tape.pgrad(front)
         if gf is not None:
             fr = torch.empty(nfront, D, dtype=g.dtype, device=g.device)
@@ -862,7 +837,7 @@ def expand_rows(tape: Tape, x: Var, rows_out: int, body_idx, front_idx, n_front:
             ops.row_axpby(dx, rows_in, a=g, ai=body_idx)
             tape.add_grad(x, dx)
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -878,10 +853,7 @@ def rows_mix(tape: Tape, dst: Var, src: Var, nrows: int, *, alpha: float, beta: 
                   a=src.data, ai=s_idx, a_inner=si, a_stride=ss, a_off=so, alpha=alpha,
                   b=dst.data if beta != 0.0 else None, bi=d_idx, b_inner=di, b_stride=ds_, b_off=do, beta=beta)
 
-    def bwd():
-        g = dst.grad
-        if g is None:
-            return
+    def bwd(g):
         if src.needs_grad:
             gs = tape.grad_buf(src)
             ops.row_axpby(gs, nrows, di=s_idx, d_inner=si, d_stride=ss, d_off=so,
@@ -889,7 +861,7 @@ def rows_mix(tape: Tape, dst: Var, src: Var, nrows: int, *, alpha: float, beta: 
         ops.row_axpby(g, nrows, di=d_idx, d_inner=di, d_stride=ds_, d_off=do,
                       a=g if beta != 0.0 else None, ai=d_idx, a_inner=di, a_stride=ds_, a_off=do, alpha=beta)
 
-    tape.record(bwd)
+    tape.adjoint(dst, bwd, take=False)      # in place: dst's gradient stays where it is, for the ops before this one
     return dst
 
 
@@ -906,11 +878,7 @@ def graph_node_features(tape: Tape, text: Var, text_row_of_node, in_degree, out_
     o = Var(x)
     D = x.shape[1]
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         if text.needs_grad:
             gt = tape.grad_buf(text)
             ops.row_axpby(gt, M, di=src_rows_of_comment, a=g, ai=graph_rows_of_comment, accumulate=True)
@@ -922,7 +890,7 @@ def graph_node_features(tape: Tape, text: Var, text_row_of_node, in_degree, out_
         if gk is not None:
             colsum(g.view(B, T * D)[:, :D], out=gk.view(-1))
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -945,11 +913,7 @@ def classifier_head(tape: Tape, text: Var, M: int, cls_rows, bn0_rows, pool_w, p
     ops.row_axpby(logits, M, a=l2, alpha=0.5, b=l2, b_off=M, beta=0.5)
     o = Var(logits)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def bwd(g):
         dl2 = torch.empty_like(l2)
         ops.row_axpby(dl2, M, d_off=0, a=g, alpha=0.5)
         ops.row_axpby(dl2, M, d_off=M, a=g, alpha=0.5)
@@ -967,7 +931,7 @@ def classifier_head(tape: Tape, text: Var, M: int, cls_rows, bn0_rows, pool_w, p
         if tape.on_params_ready:
             tape.on_params_ready([pool_w, pool_b, cls_w, cls_b])
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -978,15 +942,13 @@ def take_rows(tape: Tape, src: Var, nrows: int, s_map=(1, 1, 0), s_idx=None) -> 
     ops.row_axpby(out, nrows, a=src.data, ai=s_idx, a_inner=si, a_stride=ss, a_off=so)
     o = Var(out)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None or not src.needs_grad:
+    def bwd(g):
+        if not src.needs_grad:
             return
         gs = tape.grad_buf(src)
         ops.row_axpby(gs, nrows, di=s_idx, d_inner=si, d_stride=ss, d_off=so, a=g, accumulate=True)
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 
@@ -997,15 +959,13 @@ def scatter_rows(tape: Tape, src: Var, rows_out: int, d_idx, s_idx) -> Var:
     ops.row_axpby(out, n, di=d_idx, a=src.data, ai=s_idx)
     o = Var(out)
 
-    def bwd():
-        g = o.grad
-        o.grad = None
-        if g is None or not src.needs_grad:
+    def bwd(g):
+        if not src.needs_grad:
             return
         gs = tape.grad_buf(src)
         ops.row_axpby(gs, n, di=s_idx, a=g, ai=d_idx, accumulate=True)
 
-    tape.record(bwd)
+    tape.adjoint(o, bwd)
     return o
 
 

@@ -63,6 +63,31 @@ def test_standalone_dropout_statistics_and_determinism(ops):
     assert float((col - 0.7).abs().max()) < 0.05
 
 
+@pytest.mark.parametrize("dtype,D", [(torch.bfloat16, 8), (torch.bfloat16, 520), (torch.float32, 4), (torch.float32, 260)],
+                         ids=["bf16-D8", "bf16-D520", "f32-D4", "f32-D260"])
+def test_standalone_dropout_vector_and_scalar_forms_agree_bit_for_bit(ops, dtype, D):
+    """dropout_kernel<T, VN> (csrc/elementwise.hip) in its 16-byte form (row stride D) and, forced by a row stride of D + 1
+    on input and output, in its scalar form: 5 rows (a second workgroup with one row), D of one vector per lane and of a
+    second lane sweep with a partial wave.  Element (r, c) takes counter r * D + c in both, the vector form two counters
+    per hash: the outputs agree bit for bit and equal x * keep / (1 - p) with the keep bits of mdt_dropout_mask."""
+    rows, p, seed = 5, 0.3, 2024
+    bits = torch.int16 if dtype == torch.bfloat16 else torch.int32
+    vn = 16 // torch.empty(0, dtype=dtype).element_size()
+    x = rnd(rows, D, seed=3).to(dtype)
+    xv = x.cuda()
+    yv = torch.empty_like(xv)
+    xs = torch.zeros(rows, D + 1, dtype=dtype, device="cuda")[:, :D]
+    xs.copy_(xv)
+    ys = torch.zeros(rows, D + 1, dtype=dtype, device="cuda")[:, :D]
+    assert D % vn == 0 and xv.stride(0) == D and yv.stride(0) == D and xs.stride(0) == D + 1 and ys.stride(0) == D + 1
+    ops.dropout(xv, p, seed, out=yv)
+    ops.dropout(xs, p, seed, out=ys)
+    want = (x.float() * mask(ops, (rows, D), p, seed)).to(dtype)
+    assert torch.equal(yv.cpu().view(bits), ys.cpu().contiguous().view(bits)), "the vector and the scalar dropout kernel differ"
+    assert torch.equal(yv.cpu(), want) and torch.equal(ys.cpu(), want)
+    assert 0 < int((want == 0).sum()) < want.numel()
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_gemm_epilogue_dropout(ops, dtype):
     M, N, K = (50, 40, 36) if dtype == torch.float32 else (33000, 256, 128)

@@ -367,6 +367,35 @@ def test_colsum_cast_transpose(ops):
     assert torch.equal(ops.transpose2d(dev(x), torch.bfloat16).cpu(), xb.t().contiguous())
 
 
+@pytest.mark.parametrize("weighted", [False, True], ids=["plain", "row_weight"])
+@pytest.mark.parametrize("dtype,N", [(torch.bfloat16, 72), (torch.float32, 36)], ids=["bf16-N72", "f32-N36"])
+def test_colsum_vector_and_scalar_forms_agree_bit_for_bit(ops, dtype, N, weighted):
+    """colsum_kernel<T, VN> (csrc/elementwise.hip) in its 16-byte form (contiguous rows) and, forced by a row stride of
+    N + 1 elements, in its scalar form.  M = 30 rows are one row block in either form, so every column receives exactly
+    one atomic add into a zeroed output and its bits are determined: row lane j adds rows j, j + 4, ..., the four lanes
+    are added in order.  N is nine vectors: a partial last group of lanes, and in the scalar form a second column group.
+    Both forms must agree bit for bit, and each must meet the fp64 bound of tests/gemm_reference.py for an fp32 sum of
+    30 terms in any order (a term w * x carries one fp32 rounding where the product is no fp32 number)."""
+    M = 30
+    vn = 16 // torch.empty(0, dtype=dtype).element_size()
+    x = rnd(M, N, seed=11).to(dtype)
+    w = torch.randint(0, 4, (M,), generator=torch.Generator().manual_seed(12), dtype=torch.int32) if weighted else None
+    xv = dev(x)
+    xs = torch.zeros(M, N + 1, dtype=dtype, device="cuda")[:, :N]
+    xs.copy_(xv)
+    assert xv.stride(0) % vn == 0 and xv.data_ptr() % 16 == 0 and N % vn == 0 and xs.stride(0) % vn != 0
+    wd = None if w is None else dev(w)
+    vec = ops.colsum(xv, row_weight=wd).cpu()
+    sca = ops.colsum(xs, row_weight=wd).cpu()
+    terms = x.double() if w is None else x.double() * w.double()[:, None]
+    d = torch.where(GR._rep32(terms), torch.zeros_like(terms), terms.abs() * GR.U32)
+    ref = terms.sum(0)
+    bnd = GR.bound(ref, GR._sum_bound(terms, d, torch.zeros(N, dtype=torch.float64), M, 0), torch.float32)
+    for name, got in (("vector", vec), ("scalar", sca)):
+        GR.assert_within(got, ref, bnd, what=f"colsum {name} form", dtype=torch.float32, median_limit=2.0 ** -7)
+    assert torch.equal(vec.view(torch.int32), sca.view(torch.int32)), "the vector and the scalar colsum kernel differ"
+
+
 def test_empty_inputs_are_no_ops(ops):
     """A batch may carry no image, a rank no labelled comment, a length bin no sequence: every entry point the step calls takes
     zero rows / sequences / images as a no-op (MDT_OK, nothing launched, outputs of the right — empty — shape)."""

@@ -279,7 +279,7 @@ def test_bert_embed_sum_and_rows(dtype, D):
 
 
 def test_embed_sums_refuse_rows_they_cannot_vectorise():
-    """vec_ok: D no multiple of the vector, an output stride no multiple of it, an output pointer off the 16-byte grid;
+    """vec16_ok: D no multiple of the vector, an output stride no multiple of it, an output pointer off the 16-byte grid;
     M = 0 / rows = 0 are no-ops."""
     M, Lq = 2, 3
     for dtype, D in ((f32, 8), (bf16, 16)):
