@@ -69,7 +69,7 @@ int mdt_abi_version(void);
 const char* mdt_last_error_string(void);
 /* The route of the calling thread's last successful GEMM, attention, LayerNorm or mdt_row_axpby launch ("" before the first): mdt_gemm "generic",
  * "tile128", "tile256x128", "pp256", "pp256p", "w4p", "w4s"; mdt_gemm_fp8 "f8_w4", "f8_pp256p"; attention "v1" ... "v5", "v4x",
- * "long"; mdt_layernorm_fwd "ln_fwd", mdt_layernorm_fwd_q8 with an fp8 copy "ln_fwd_q8", mdt_layernorm_bwd "ln_rows" (the
+ * "long" (forward and backward; mdt_attention_route names the route of an argument block without launching); mdt_layernorm_fwd "ln_fwd", mdt_layernorm_fwd_q8 with an fp8 copy "ln_fwd_q8", mdt_layernorm_bwd "ln_rows" (the
  * scalar-address kernel) or "ln_generic"; mdt_row_axpby "row_vec" (16-byte vectors) or "row_scalar" (D, a row stride or a base pointer
  * of dst / a / b not vectorisable); mdt_act_fwd "act_vec" or "act_scalar".  What MDT_GEMM_ROUTE / MDT_ATTN_BWD force is checked against it (a forced route whose preconditions fail runs the default). */
 const char* mdt_last_route(void);
@@ -222,6 +222,15 @@ typedef struct {
   float* d_virt;              /* f32[H], atomically accumulated, or NULL */
 } mdt_attn_bwd_args;
 int mdt_attention_bwd(void* stream, const mdt_attn_bwd_args* a);
+/* What mdt_attention_fwd (bwd = 0: only a->f is read) or mdt_attention_bwd (bwd = 1) would do with this argument block, without
+ * launching anything: the same argument checks and the same plan (attn_plan, csrc/attention.hip — the routing table is
+ * documented there).  route receives the name mdt_last_route() would report after the launch ("v1" ... "v5", "v4x", "long");
+ * geometry what tells two launches of one route apart: {key-tile rung, 0} for "v1" and the "v2" backward, {rung, waves} for
+ * the "v2" forward, {padded length, threads} for "v3", {waves, 0} for "v4" / "v4x", {0, 0} for "v5" / "long".  Returns what
+ * the launch would return: for a refused block the error code, with the message in mdt_last_error_string(), route "" and
+ * geometry {0, 0}.  MDT_ATTN_BWD is honoured as a launch honours it.  Pointers in the block are looked at for null-ness and
+ * alignment only and never dereferenced, so any non-null, 16-byte aligned values will do; no device is needed. */
+int mdt_attention_route(const mdt_attn_bwd_args* a, int bwd, char* route, size_t route_bytes, int32_t geometry[2]);
 /* Head-averaged attention probabilities, fp32 [nseq, S, S] (modules/multihead_attention.py:205-214, need_weights=True):
  * recomputed from the qkv buffer and the log-sum-exp mdt_attention_fwd wrote (same args struct; out / dropout fields are
  * not read).  Masked keys give 0. */

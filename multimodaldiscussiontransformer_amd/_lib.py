@@ -62,6 +62,7 @@ _SIGS = {
                            _vp, _i64, _f, C.c_uint64, _vp], _i),
     "mdt_attention_fwd": ([_vp, C.POINTER(AttnFwdArgs)], _i),
     "mdt_attention_bwd": ([_vp, C.POINTER(AttnBwdArgs)], _i),
+    "mdt_attention_route": ([C.POINTER(AttnBwdArgs), _i, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)], _i),
     "mdt_attention_mean_probs": ([_vp, C.POINTER(AttnFwdArgs), _vp], _i),
     "mdt_attention_head_weights": ([_vp, C.POINTER(AttnFwdArgs), _i, _vp], _i),
     "mdt_graph_attn_bias": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),

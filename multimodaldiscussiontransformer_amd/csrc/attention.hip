@@ -92,7 +92,7 @@ __device__ __forceinline__ typename MM<T>::frag frag_km(const Src<T>& s, int c0,
 // 96 / 128: 208- and 272-byte rows.  frag_km's rows k0 .. k0 + 3 and k0 + 8 .. k0 + 11 are 2-way at every stride that is a
 // multiple of 16 bytes (8 rows apart is 0 or 128 bytes mod 256), so no padding makes these kernels conflict-free; + 8 is the
 // one with which the 17-tile rung of 96-wide heads still fits LDS (attn_v1_fits, attention_common.hpp).
-template <int HD> constexpr int IMG_LD = HD >= 32 ? HD + 8 : HD;
+template <int HD> constexpr int IMG_LD = attn_v1_ld(HD);
 
 // Stage a [S][HD] bf16 operand (rows = sequence positions) into an LDS image, zero padded
 // to rows_pad rows.
@@ -536,90 +536,163 @@ __global__ __launch_bounds__(256) void attn_mean_probs_kernel(mdt_attn_fwd_args 
   }
 }
 
-template <typename T, int HD, int NT, bool STRUCT, bool DROP>
-static int launch_fwd(hipStream_t st, const AttnParams& p) {
-  constexpr int s_pad32 = (NT * 16 + 31) & ~31;
-  constexpr bool BF = !std::is_same<T, float>::value;
-  const int sld = s_pad32 + (BF ? 8 : 1);
-  const size_t lds = (size_t)4 * 16 * sld * sizeof(T) + (BF ? (size_t)2 * s_pad32 * IMG_LD<HD> * 2 : 0);
-  if (lds > 160 * 1024) { set_error("attention (v1): S=%d with head_dim %d needs %zu bytes of LDS", p.f.S, HD, lds); return MDT_ERR_UNSUPPORTED; }
-  return launch_route<attn_fwd_kernel<T, HD, NT, STRUCT, DROP>>("v1", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
-}
+// ---------------------------------------------------------------------------- the plan of a launch
+// The routing table of the attention family: which kernel a launch takes and at which geometry, as a pure host function of
+// the argument block.  Everything else reads it: dispatch() below switches on the route, the three launchers turn the numbers
+// into template arguments, mdt_attention_route reports it without launching (tests/test_attention_plan_cpu.py holds it
+// against tests/attention_reference.py over the whole domain).  S <= 272 is what one workgroup holds of a (sequence, head).
+//
+// Refused before any route: seq_ids / s_cap (the length bins of a ragged set) on anything but a ragged bf16 launch with
+// head_dim 64 and S <= 272; a head width other than 16, 64, 96 or 128.
+// Forward and backward, in order:
+//   S > 272                                              -> long (attention_long.hip: key-chunked, any length; takes neither
+//                                                           ragged sequences nor q_limit and refuses them)
+//   fp32                                                 -> v1 (attention.hip: the exact-fp32 parity path), but the backward
+//                                                           of head_dim 96 | 128, S 209 .. 272 (the 17-tile rung) with structural
+//                                                           bias AND dropout -> long: that v1 instantiation needs 512
+//                                                           registers and 15-17 more in scratch memory and is not built
+//                                                           (a structural bias is never ragged; q_limit is ignored there as v1 ignores it)
+//   bf16, a dense bias without structural terms          -> v1 (the only bf16 kernels that take one); 128-wide heads of more
+//                                                           than 208 tokens -> long (the v1 images do not fit LDS: attn_v1_fits)
+// The bf16 forward otherwise                             -> v2 (attention_v2.hip: P stays in registers; length bins too), on
+//                                                           the rung of the launch's longest sequence (cap: s_cap, else S)
+// The bf16 backward otherwise (head_dim 16, 64, 96 or 128; S <= 272; length-binned launches, 64 only: s_cap <= 272), in order:
+//   length-binned launches (seq_ids / s_cap)              -> the family below
+//   S > 256 (ViT-L/14: 4 + 257 tokens)                   -> family
+//   S <= 80, q_limit == 0, structural bias               -> v1 (LDS-scratch kernel: tiny graphs)
+//   no dropout, q_limit == 0, S <= 112                   -> v2 (whole row in registers; with dropout it falls to 1 wave / SIMD)
+//   otherwise                                            -> family
+// The family, without a structural bias, where the one-pass dS image fits LDS (S <= 208): v5 (9-13 key tiles, persistent),
+// v4x (<= 6 key tiles: delta = sum P o dP summed in the kernel, in fp32), v4 (7-8 key tiles); past that, and with a
+// structural bias: the two-pass v3.  Measured at C2 shapes: profiles/round1_attention_v2.txt, tools/attn_onepass_ab.py.
+// The one-pass kernels are written for 64-wide heads: with head_dim 16, 96 or 128 the family is always v3.
+// MDT_ATTN_BWD=<kernel> takes that kernel for a bf16 backward wherever its preconditions (ok() below) hold.  v1 and v2 never
+// see q_limit or length bins (they would read the out / lse rows the v2 forward skipped — unwritten memory; tests:
+// ..._never_reads_what_forward_did_not_write), v2 takes S <= 112 only, the one-pass kernels take no structural bias.
+// Runs on every attention launch: no allocation, no getenv, no HIP call but the cached device_cus().
+static AttnPlan refuse(AttnPlan pl) { pl.status = MDT_ERR_UNSUPPORTED; return pl; }
 
-template <typename T, int HD, int NT, bool STRUCT, bool DROP>
-static int launch_bwd(hipStream_t st, const AttnParams& p) {
-  constexpr int s_pad32 = (NT * 16 + 31) & ~31;
-  constexpr bool BF = !std::is_same<T, float>::value;
-  const int sld = s_pad32 + (BF ? 8 : 1);
-  const int nhist = STRUCT ? attn_hist_size(p.f.num_spatial) : 0;
-  const size_t lds = (size_t)(2 * s_pad32 + nhist) * 4 + (size_t)4 * 16 * sld * sizeof(T) +
-               (BF ? (size_t)2 * s_pad32 * IMG_LD<HD> * 2 : 0);
-  if (lds > 160 * 1024) { set_error("attention_bwd (v1): S=%d with head_dim %d needs %zu bytes of LDS", p.f.S, HD, lds); return MDT_ERR_UNSUPPORTED; }
-  if constexpr (!BF && HD > 64 && NT == 17 && STRUCT && DROP) {
-    // fp32, wide heads, 17 key tiles with structural bias and dropout: 512 registers and 15-17 more in scratch memory (as the
-    // 16- and 64-wide instantiations have) — not instantiated; the key-chunked path instead (a structural bias is never ragged)
-    return attention_long_dispatch(st, p, true);
-  } else
-  return launch_route<attn_bwd_kernel<T, HD, NT, STRUCT, DROP>>("v1", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
-}
-
-template <typename T, int HD, bool STRUCT, bool BWD>
-static int dispatch_nt(hipStream_t st, const AttnParams& p) {
-  const int nt = (p.f.S + 15) / 16;
-#define ATT_CASE(N_)                                                                              \
-  if (nt <= N_) {                                                                                 \
-    if (p.f.drop_p > 0.f) return BWD ? launch_bwd<T, HD, N_, STRUCT, true>(st, p) : launch_fwd<T, HD, N_, STRUCT, true>(st, p); \
-    return BWD ? launch_bwd<T, HD, N_, STRUCT, false>(st, p) : launch_fwd<T, HD, N_, STRUCT, false>(st, p);                    \
+static AttnPlan plan_long(AttnPlan pl, const mdt_attn_fwd_args& a) {
+  // S <= 272 comes here for a plain dense bias on 128-wide heads and for the fp32 backward above: never ragged, and q_limit
+  // is ignored as the kernels of this file ignore it — every row is computed
+  if (a.seq_offsets || (a.q_limit > 0 && a.S > 272)) {
+    set_error("attention: S=%d exceeds the 272-token limit of the single-pass kernels and the key-chunked path takes neither "
+              "ragged sequences nor q_limit (text / image sequences are always shorter)", a.S);
+    return refuse(pl);
   }
-  ATT_CASE(2) ATT_CASE(5) ATT_CASE(7) ATT_CASE(9) ATT_CASE(13) ATT_CASE(17)      // 17 tiles: ViT-L/14, 4 + 257 tokens
-#undef ATT_CASE
-  set_error("attention: S=%d exceeds the 272-token limit of the single-pass kernel", p.f.S);
-  return MDT_ERR_UNSUPPORTED;
+  if (!attn_head_dim_ok(a.hd)) { set_error("attention (long sequences): head_dim %d unsupported (16, 64, 96 or 128)", a.hd); return refuse(pl); }
+  pl.route = AttnRoute::long_;
+  return pl;
 }
 
-template <typename T, int HD, bool BWD>
-static int dispatch_hd(hipStream_t st, const AttnParams& p) {
-  return p.f.attn_bias ? dispatch_nt<T, HD, true, BWD>(st, p) : dispatch_nt<T, HD, false, BWD>(st, p);
-}
-
-template <typename T, bool BWD>
-static int dispatch_width(hipStream_t st, const AttnParams& p) {
-  switch (p.f.hd) {
-    case 16: return dispatch_hd<T, 16, BWD>(st, p);
-    case 64: return dispatch_hd<T, 64, BWD>(st, p);
-    case 96: return dispatch_hd<T, 96, BWD>(st, p);
-    case 128: return dispatch_hd<T, 128, BWD>(st, p);
-  }
-  set_error("attention: head_dim %d unsupported (16, 64, 96 or 128)", p.f.hd);
-  return MDT_ERR_UNSUPPORTED;
-}
-
-template <bool BWD>
-static int dispatch(hipStream_t st, const AttnParams& p) {
+AttnPlan attn_plan(const AttnParams& p, bool bwd) {
   const mdt_attn_fwd_args& a = p.f;
-  const bool st_bias = a.attn_bias != nullptr;
-  if (a.seq_ids != nullptr || a.s_cap > 0) {                     // length bins of a ragged set: the v2 forward / v3-v5 backward only
-    if (a.S > 272 || a.dtype != MDT_BF16 || a.hd != 64 || !a.seq_offsets) {
+  AttnPlan pl{};
+  pl.bwd = bwd;
+  pl.st_bias = a.attn_bias != nullptr;
+  pl.drop = a.drop_p > 0.f;
+  pl.binned = a.seq_ids != nullptr || a.s_cap > 0;
+  pl.dense_only = (a.dense_bias != nullptr || p.d_dense_bias != nullptr) && !pl.st_bias;
+  pl.cap = a.s_cap > 0 ? a.s_cap : a.S;
+  pl.n_t = (pl.cap + 15) / 16;
+  pl.nhist = (bwd && pl.st_bias) ? attn_hist_size(a.num_spatial) : 0;
+  const bool bf = a.dtype == MDT_BF16;
+  if (pl.binned) {
+    if (a.S > 272 || !bf || a.hd != 64 || !a.seq_offsets) {
       set_error("attention: seq_ids / s_cap are for ragged bf16 launches with head_dim 64 and S <= 272");
-      return MDT_ERR_UNSUPPORTED;
+      return refuse(pl);
     }
-  } else if (a.S > 272) return attention_long_dispatch(st, p, BWD);      // discussion trees with more than 271 comments
-  if (a.dtype == MDT_BF16) {
-    if (a.hd != 64 && a.hd != 16 && a.hd != 96 && a.hd != 128) {
-      set_error("attention(bf16): head_dim %d unsupported (16, 64, 96 or 128)", a.hd);
-      return MDT_ERR_UNSUPPORTED;
-    }
-    // forward: register-resident P (v2) unless a plain dense bias (no structural terms), which only the kernels in this file
-    // take; backward: attn_bwd_route (attention_v2.hip)
-    const bool dense_only = (a.dense_bias != nullptr || p.d_dense_bias != nullptr) && !st_bias;
-    // ... whose images do not fit LDS for 128-wide heads of more than 208 tokens: the key-chunked path, forward and backward
-    if (dense_only && !attn_v1_fits(a.hd, a.S)) return attention_long_dispatch(st, p, BWD);
-    const AttnRoute r = BWD ? attn_bwd_route(p) : dense_only ? AttnRoute::v1 : AttnRoute::v2;
-    if (r == AttnRoute::v2) return attention_v2_dispatch(st, p, BWD);
-    if (r != AttnRoute::v1) return attention_v3_bwd_dispatch(st, p, r);
-    return dispatch_width<bf16_t, BWD>(st, p);
+  } else if (a.S > 272) return plan_long(pl, a);      // discussion trees with more than 271 comments
+  if (!attn_head_dim_ok(a.hd)) {
+    set_error(bf ? "attention(bf16): head_dim %d unsupported (16, 64, 96 or 128)" : "attention: head_dim %d unsupported (16, 64, 96 or 128)", a.hd);
+    return refuse(pl);
   }
-  return dispatch_width<float, BWD>(st, p);
+  if (bf && pl.dense_only && !attn_v1_fits(a.hd, a.S)) return plan_long(pl, a);
+  const bool one_pass = a.hd == 64 && !pl.st_bias && !pl.dense_only && attn_one_pass_lds_bytes(pl.n_t) <= ATTN_LDS_MAX && pl.n_t <= 16;
+  pl.rows_img = attn_one_pass_rows(pl.n_t);
+  pl.ldq = attn_one_pass_ldq(pl.n_t);
+  auto ok = [&](AttnRoute r) {
+    switch (r) {
+      case AttnRoute::v1: return !pl.binned && a.q_limit == 0 && attn_v1_fits(a.hd, a.S);
+      case AttnRoute::v2: return !pl.binned && !pl.dense_only && a.q_limit == 0 && a.S <= 112;
+      case AttnRoute::v3: return !pl.dense_only;
+      case AttnRoute::v4: return one_pass;
+      case AttnRoute::v4x: return one_pass && pl.n_t <= 2 * V4_EXACT_PAIRS;
+      case AttnRoute::v5: return one_pass && pl.n_t > 8 && pl.rows_img * 8 <= 4 * 512;     // long rows (one workgroup per CU by LDS)
+      default: return false;
+    }
+  };
+  if (!bf) pl.route = AttnRoute::v1;
+  else if (!bwd) pl.route = pl.dense_only ? AttnRoute::v1 : AttnRoute::v2;
+  else {
+    const AttnRoute family = ok(AttnRoute::v5) ? AttnRoute::v5 : ok(AttnRoute::v4x) ? AttnRoute::v4x : one_pass ? AttnRoute::v4 : AttnRoute::v3;
+    if (pl.binned) pl.route = family;
+    else if (pl.dense_only) pl.route = AttnRoute::v1;
+    else if (a.S > 256) pl.route = family;
+    else if (a.S <= 80 && a.q_limit == 0 && pl.st_bias) pl.route = AttnRoute::v1;
+    else if (!pl.drop && ok(AttnRoute::v2)) pl.route = AttnRoute::v2;
+    else pl.route = family;
+    const AttnRoute forced = switches().attn_bwd;
+    if (forced != AttnRoute::none && ok(forced)) pl.route = forced;
+  }
+  switch (pl.route) {
+    case AttnRoute::v1: {
+      pl.rung = attn_rung<2, 5, 7, 9, 13, 17>((a.S + 15) / 16);      // 17 tiles: ViT-L/14, 4 + 257 tokens
+      if (!pl.rung) { set_error("attention: S=%d exceeds the 272-token limit of the single-pass kernel", a.S); return refuse(pl); }
+      const size_t lds = attn_v1_lds_bytes(bf, a.hd, pl.rung, bwd, pl.nhist);
+      if (lds > ATTN_LDS_MAX) {
+        set_error(bwd ? "attention_bwd (v1): S=%d with head_dim %d needs %zu bytes of LDS" : "attention (v1): S=%d with head_dim %d needs %zu bytes of LDS", a.S, a.hd, lds);
+        return refuse(pl);
+      }
+      if (!bf && bwd && a.hd > 64 && pl.rung == 17 && pl.st_bias && pl.drop) return plan_long(pl, a);      // the fp32 line of the table
+      break;
+    }
+    case AttnRoute::v2:
+      pl.rung = attn_rung<2, 4, 5, 7, 9, 13, 17>(pl.n_t);
+      if (!pl.rung) { set_error("attention_v2: S=%d exceeds 272", a.S); return refuse(pl); }
+      // the whole-row backward runs out of registers past 112 keys; ok(v2) sends those to the v3 family
+      if (bwd && pl.rung > 7) { set_error("attention_v2: backward supports S <= 112 (got %d)", a.S); return refuse(pl); }
+      if (!bwd) pl.waves = attn_v2_fwd_waves(pl.rung, pl.st_bias);
+      break;
+    case AttnRoute::v3: {
+      pl.tight = attn_v3_tight(a.hd, pl.cap);
+      pl.s_pad = attn_v3_s_pad(pl.cap, pl.tight);
+      const size_t lds = attn_v3_lds_bytes(a.hd, pl.s_pad, pl.tight, pl.nhist);
+      if (lds > ATTN_LDS_MAX) { set_error("attention_bwd_v3: S=%d needs %zu bytes of LDS", pl.cap, lds); return refuse(pl); }
+      // 64- and 16-wide heads without a structural bias, long sequences (ViT: 13 tiles): LDS allows two workgroups per CU; 8 waves
+      // each in the 128-register build = 4 waves per SIMD instead of 2 (in-call A/B at the ViT shape: +0.7 % on the step)
+      pl.threads = (a.hd <= 64 && !pl.st_bias && pl.s_pad > 128) ? 512 : 256;
+      break;
+    }
+    case AttnRoute::v5:
+      pl.items = (int)((int64_t)a.H * a.nseq);
+      pl.wgs = pl.items < device_cus() ? pl.items : device_cus();      // persistent: at most one workgroup per CU
+      break;
+    case AttnRoute::v4:
+    case AttnRoute::v4x:
+      pl.waves = pl.n_t <= 4 ? 4 : pl.n_t <= 8 ? 8 : 16;          // two 16-byte chunks per thread and image, one key tile per wave
+      break;
+    default: break;
+  }
+  return pl;
+}
+
+// v1: the kernels of this file
+int attention_v1_launch(hipStream_t st, const AttnParams& p, const AttnPlan& pl) {
+  return with_dtype(p.f.dtype, [&](auto t) { return with_head_dim(p.f.hd, [&](auto hd) { return with_flags(pl, [&](auto s, auto d) {
+    return with_rung<2, 5, 7, 9, 13, 17>(pl.rung, [&](auto nt) {
+      using T = typename decltype(t)::type;
+      constexpr int HD = decltype(hd)::value, NT = decltype(nt)::value;
+      constexpr bool STRUCT = decltype(s)::value, DROP = decltype(d)::value, BF = !std::is_same<T, float>::value;
+      const size_t lds = attn_v1_lds_bytes(BF, HD, NT, pl.bwd, pl.nhist);
+      const dim3 grid(p.f.H, p.f.nseq);
+      if (!pl.bwd) return launch_route<attn_fwd_kernel<T, HD, NT, STRUCT, DROP>>("v1", grid, 256, lds, st, p);
+      // fp32, wide heads, 17 key tiles with structural bias and dropout: 512 registers and 15-17 more in scratch memory (as the
+      // 16- and 64-wide instantiations have) — not instantiated; attn_plan sends them to the key-chunked path
+      if constexpr (!BF && HD > 64 && NT == 17 && STRUCT && DROP) return attn_unplanned("the fp32 v1 backward of wide heads at 17 tiles with structural bias and dropout");
+      else return launch_route<attn_bwd_kernel<T, HD, NT, STRUCT, DROP>>("v1", grid, 256, lds, st, p);
+    });
+  }); }); });
 }
 
 static int check_args(const mdt_attn_fwd_args& a) {
@@ -643,6 +716,35 @@ static int check_args(const mdt_attn_fwd_args& a) {
   return MDT_OK;
 }
 
+// check_args and the backward block's own checks (b: null for a forward), then the kernels' argument block
+static int checked_params(const mdt_attn_fwd_args& f, const mdt_attn_bwd_args* b, AttnParams& p) {
+  if (int e = check_args(f)) return e;
+  memset(&p, 0, sizeof(p));
+  p.f = f;
+  p.drop = make_drop(f.drop_p, f.drop_seed);
+  if (!b) return MDT_OK;
+  MDT_CHECK_ARG(b->dout && b->dqkv, "attention_bwd: null dout / dqkv");
+  MDT_CHECK_ARG(b->ld_dqkv >= 3 * f.H * f.hd, "attention_bwd: ld_dqkv too small");
+  if (f.dtype == MDT_BF16)
+    MDT_CHECK_ARG(b->ld_dout % 8 == 0 && ((uintptr_t)b->dout & 15) == 0, "attention_bwd(bf16): dout must be 16-byte aligned rows");
+  p.dout = b->dout; p.ld_dout = b->ld_dout; p.dqkv = b->dqkv; p.ld_dqkv = b->ld_dqkv;
+  p.d_dense_bias = b->d_dense_bias; p.d_sp_table = b->d_sp_table; p.d_virt = b->d_virt;
+  return MDT_OK;
+}
+
+static int dispatch(hipStream_t st, const mdt_attn_fwd_args& f, const mdt_attn_bwd_args* b) {
+  AttnParams p;
+  if (int e = checked_params(f, b, p)) return e;
+  if (p.d_sp_table || p.d_virt) note_float_atomic_launch();     // the structural-bias gradient (attn_bias_grad_add / _flush)
+  const AttnPlan pl = attn_plan(p, b != nullptr);
+  if (pl.status != MDT_OK) return pl.status;
+  switch (pl.route) {
+    case AttnRoute::v1: return attention_v1_launch(st, p, pl);
+    case AttnRoute::long_: return attention_long_launch(st, p, pl);
+    default: return attention_v2_launch(st, p, pl);      // v2 .. v5
+  }
+}
+
 }  // namespace mdt
 
 using namespace mdt;
@@ -650,30 +752,33 @@ using namespace mdt;
 extern "C" int mdt_attention_fwd(void* stream, const mdt_attn_fwd_args* a) {
   MDT_CHECK_ARG(a, "attention_fwd: null args");
   if (a->nseq == 0) return MDT_OK;
-  if (int e = check_args(*a)) return e;
-  MDT_CHECK_ARG(a->drop_p >= 0.f && a->drop_p < 1.f, "attention_fwd: dropout p=%f out of [0,1)", a->drop_p);
-  AttnParams p;
-  memset(&p, 0, sizeof(p));
-  p.f = *a;
-  p.drop = make_drop(a->drop_p, a->drop_seed);
-  return dispatch<false>((hipStream_t)stream, p);
+  return dispatch((hipStream_t)stream, *a, nullptr);
 }
 
 extern "C" int mdt_attention_bwd(void* stream, const mdt_attn_bwd_args* a) {
   MDT_CHECK_ARG(a, "attention_bwd: null args");
   if (a->f.nseq == 0) return MDT_OK;
-  if (int e = check_args(a->f)) return e;
-  MDT_CHECK_ARG(a->dout && a->dqkv, "attention_bwd: null dout / dqkv");
-  MDT_CHECK_ARG(a->ld_dqkv >= 3 * a->f.H * a->f.hd, "attention_bwd: ld_dqkv too small");
-  if (a->f.dtype == MDT_BF16)
-    MDT_CHECK_ARG(a->ld_dout % 8 == 0 && ((uintptr_t)a->dout & 15) == 0, "attention_bwd(bf16): dout must be 16-byte aligned rows");
+  return dispatch((hipStream_t)stream, a->f, a);
+}
+
+extern "C" int mdt_attention_route(const mdt_attn_bwd_args* a, int bwd, char* route, size_t route_bytes, int32_t geometry[2]) {
+  MDT_CHECK_ARG(a && route && route_bytes > 0 && geometry, "attention_route: null args");
+  route[0] = 0;
+  geometry[0] = geometry[1] = 0;
   AttnParams p;
-  p.f = a->f;
-  p.drop = make_drop(a->f.drop_p, a->f.drop_seed);
-  p.dout = a->dout; p.ld_dout = a->ld_dout; p.dqkv = a->dqkv; p.ld_dqkv = a->ld_dqkv;
-  p.d_dense_bias = a->d_dense_bias; p.d_sp_table = a->d_sp_table; p.d_virt = a->d_virt;
-  if (p.d_sp_table || p.d_virt) note_float_atomic_launch();     // the structural-bias gradient (attn_bias_grad_add / _flush)
-  return dispatch<true>((hipStream_t)stream, p);
+  if (int e = checked_params(a->f, bwd ? a : nullptr, p)) return e;
+  const AttnPlan pl = attn_plan(p, bwd != 0);
+  if (pl.status != MDT_OK) return pl.status;
+  snprintf(route, route_bytes, "%s", route_name(pl.route));
+  switch (pl.route) {
+    case AttnRoute::v1:
+    case AttnRoute::v2: geometry[0] = pl.rung; geometry[1] = pl.waves; break;      // waves: the v2 forward's
+    case AttnRoute::v3: geometry[0] = pl.s_pad; geometry[1] = pl.threads; break;
+    case AttnRoute::v4:
+    case AttnRoute::v4x: geometry[0] = pl.waves; break;
+    default: break;
+  }
+  return MDT_OK;
 }
 
 extern "C" int mdt_attention_mean_probs(void* stream, const mdt_attn_fwd_args* a, float* out) {

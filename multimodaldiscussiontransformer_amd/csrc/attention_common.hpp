@@ -1,4 +1,5 @@
-// Shared pieces of the two attention kernel families (attention.hip, attention_v2.hip).
+// Shared pieces of the attention kernel families (attention.hip, attention_v2.hip, attention_long.hip): device helpers, the LDS
+// sizes, the plan of a launch (AttnPlan) and the helpers that turn a plan into template arguments.
 #pragma once
 #include "common.hpp"
 
@@ -158,13 +159,107 @@ __device__ __forceinline__ void attn_bias_grad_flush(const AttnParams& P, const 
   }
 }
 
-int attention_v2_dispatch(hipStream_t st, const AttnParams& p, bool bwd);
-AttnRoute attn_bwd_route(const AttnParams& p);                                   // bf16, head_dim 16 | 64 | 96 | 128: attention_v2.hip
-int attention_v3_bwd_dispatch(hipStream_t st, const AttnParams& p, AttnRoute r);   // r: v3 | v4 | v4x | v5
-int attention_long_dispatch(hipStream_t st, const AttnParams& p, bool bwd);     // S > 272: attention_long.hip
+// ---------------------------------------------------------------------------------------------- host: plan and launchers
+// LDS image row strides of the bf16 kernels, as functions of the head width (the kernels read them as IMG_LD<HD>,
+// attention.hip, and v2_ld<HD, TIGHT>, attention_v2.hip, which say why these numbers).
+constexpr int attn_v1_ld(int hd) { return hd >= 32 ? hd + 8 : hd; }
+constexpr int attn_v2_ld(int hd, bool tight) { return hd < 32 ? hd : (hd <= 64 || tight) ? hd + 8 : hd + 16; }
+template <int HD, bool TIGHT = false> constexpr int v2_ld = attn_v2_ld(HD, TIGHT);
+template <int HD, int NT> constexpr int v2_ld_nt = v2_ld<HD, (HD == 128 && NT > 16)>;      // a whole-row kernel's stride
+constexpr int V4_EXACT_PAIRS = 3;      // attn_bwd_v4x: key-tile pairs whose row sums it keeps (rows of up to 6 key tiles)
+constexpr size_t ATTN_LDS_MAX = 160 * 1024;
+
 // The bf16 kernels of attention.hip hold two [s_pad32][hd + 8] images and four score strips in LDS: with 128-wide heads the
 // 17-tile rung (S 209 .. 272: 2 x 288 x 136 x 2 + 4 x 16 x 296 x 2 = 194560 bytes) is past the 160 KiB of a workgroup; every
 // other (width, rung) fits.  A plain dense bias there takes the key-chunked long path in both directions.
-inline bool attn_v1_fits(int hd, int S) { return hd < 128 || S <= 208; }
+constexpr bool attn_v1_fits(int hd, int S) { return hd < 128 || S <= 208; }
+
+// Dynamic LDS of each family, written once: attn_plan sizes and refuses with these, the launchers pass what they return.
+// nhist: attn_hist_size(num_spatial) where the launch reduces a structural-bias gradient (backward), else 0.
+// v1 (attention.hip), rung nt: backward [delta][lse][hist], then (bf16) two images, then four waves' score strips
+constexpr size_t attn_v1_lds_bytes(bool bf, int hd, int nt, bool bwd, int nhist) {
+  const int s_pad32 = (nt * 16 + 31) & ~31, sld = s_pad32 + (bf ? 8 : 1);
+  return (bwd ? (size_t)(2 * s_pad32 + nhist) * 4 : 0) + (size_t)4 * 16 * sld * (bf ? 2 : 4) + (bf ? (size_t)2 * s_pad32 * attn_v1_ld(hd) * 2 : 0);
+}
+// v2 whole-row kernels, rung nt: two images, one (forward) or three (backward) rows of floats, the histogram; forward: + the staging's spare chunk
+constexpr size_t attn_v2_lds_bytes(int hd, int nt, bool bwd, int nhist) {
+  const int s_pad = ((nt + 1) / 2) * 32;
+  return (size_t)2 * s_pad * attn_v2_ld(hd, !bwd && hd == 128 && nt > 16) * 2 + (size_t)(bwd ? 3 : 1) * s_pad * 4 + (size_t)nhist * 4 + (bwd ? 0 : 16);
+}
+// v3: rows of up to cap keys are padded to s_pad (tight: 320 rows of 128-wide heads do not fit: 288 rows, 32-key chunks)
+constexpr bool attn_v3_tight(int hd, int cap) { return hd == 128 && cap > 256; }
+constexpr int attn_v3_s_pad(int cap, bool tight) { return tight ? (cap + 31) & ~31 : (cap + 63) & ~63; }
+constexpr size_t attn_v3_lds_bytes(int hd, int s_pad, bool tight, int nhist) {
+  return (size_t)2 * s_pad * attn_v2_ld(hd, tight) * 2 + (size_t)3 * s_pad * 4 + (size_t)nhist * 4;
+}
+// the one-pass kernels (v4, v4x, v5; 64-wide heads) for rows of n_t key tiles: two images of rows_img rows, three slabs of
+// floats (attn_bwd_v4x: seven more, of per-key-tile row sums) and the dS^T image of row stride ldq
+constexpr int attn_one_pass_rows(int n_t) { return ((n_t + 1) / 2) * 32; }
+constexpr int attn_one_pass_ldq(int n_t) { return (n_t & 1) ? 16 * n_t : 16 * n_t + 16; }   // ldq / 2 = 8 (mod 16) banks: rows 0-7 of a transposed read fall on distinct 8-bank groups
+constexpr size_t attn_one_pass_lds_bytes(int n_t) {
+  const size_t rows = attn_one_pass_rows(n_t), slabs = n_t <= 2 * V4_EXACT_PAIRS ? 7 : 0;
+  return 2 * rows * attn_v2_ld(64, false) * 2 + (3 + slabs) * rows * 4 + (size_t)16 * n_t * attn_one_pass_ldq(n_t) * 2;
+}
+// forward v2: 8 waves for the long (ViT) rows without a structural bias, 4 waves per SIMD
+constexpr int attn_v2_fwd_waves(int nt, bool st_bias) { return (nt >= 13 && !st_bias) ? 8 : 4; }
+
+// What one attention launch takes: the kernel family and every launch-geometry number that is no template body.  A pure
+// host function of the argument block (attn_plan, attention.hip, holds the routing table and says what each route is for);
+// mdt_attention_route reports it without launching.  status != MDT_OK: the launch is refused, the message is set.
+struct AttnPlan {
+  int status;
+  AttnRoute route;
+  bool bwd, st_bias, drop, binned, dense_only;
+  int cap, n_t;                  // the longest sequence of this launch (s_cap, else S) and its 16-key tiles
+  int nhist;                     // attn_hist_size(num_spatial) of a backward with a structural bias, else 0
+  int rung;                      // v1, v2: the key-tile count the kernel is instantiated for
+  int s_pad, threads; bool tight;   // v3
+  int rows_img, ldq, waves;      // v4, v4x, v5 (waves also: the v2 forward's)
+  int items, wgs;                // v5: (sequence, head) items and the persistent grid
+};
+AttnPlan attn_plan(const AttnParams& p, bool bwd);
+// The three launchers: each turns the plan's numbers into template arguments and launches; none decides anything.
+int attention_v1_launch(hipStream_t st, const AttnParams& p, const AttnPlan& pl);     // attention.hip
+int attention_v2_launch(hipStream_t st, const AttnParams& p, const AttnPlan& pl);     // attention_v2.hip: v2 .. v5
+int attention_long_launch(hipStream_t st, const AttnParams& p, const AttnPlan& pl);   // attention_long.hip
+// a combination a launcher's `if constexpr` keeps uninstantiated: attn_plan refuses or reroutes it before any launcher runs
+inline int attn_unplanned(const char* what) { set_error("attention: %s is not instantiated and attn_plan never plans it", what); return MDT_ERR_UNSUPPORTED; }
+
+// Runtime values of a plan as template arguments (with_dtype, common.hpp, is the fourth): f is called with
+// std::integral_constant / std::bool_constant tags.
+constexpr bool attn_head_dim_ok(int hd) { return hd == 16 || hd == 64 || hd == 96 || hd == 128; }
+template <typename F>
+static int with_head_dim(int hd, F&& f) {
+  switch (hd) {
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+    case 96: return f(std::integral_constant<int, 96>{});
+    case 128: return f(std::integral_constant<int, 128>{});
+  }
+  return attn_unplanned("this head width");
+}
+// (structural bias, dropout)
+template <typename F>
+static int with_flags(const AttnPlan& pl, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  if (pl.st_bias && pl.drop) return f(T{}, T{});
+  if (pl.st_bias) return f(T{}, N{});
+  if (pl.drop) return f(N{}, T{});
+  return f(N{}, N{});
+}
+// A ladder of key-tile rungs: attn_rung is the first that holds nt tiles (0: none does), with_rung hands a rung over as a type.
+template <int... RUNGS>
+constexpr int attn_rung(int nt) {
+  int r = 0;
+  ((r = (r == 0 && nt <= RUNGS) ? RUNGS : r), ...);
+  return r;
+}
+template <int... RUNGS, typename F>
+static int with_rung(int rung, F&& f) {
+  int e = MDT_ERR_UNSUPPORTED;
+  const bool hit = ((rung == RUNGS ? (e = f(std::integral_constant<int, RUNGS>{}), true) : false) || ...);
+  return hit ? e : attn_unplanned("this key-tile rung");
+}
 
 }  // namespace mdt

@@ -243,49 +243,19 @@ __global__ __launch_bounds__(64) void attn_long_dkv_kernel(AttnParams P) {
   }
 }
 
-template <typename T, int HD>
-static int long_launch(hipStream_t st, const AttnParams& p, bool bwd) {
-  const mdt_attn_fwd_args& a = p.f;
-  const bool st_bias = a.attn_bias != nullptr;
-  constexpr int per_wg = 64 / long_parts<HD>;      // queries (keys) of a workgroup
-  dim3 grid((unsigned)((a.S + per_wg - 1) / per_wg), (unsigned)a.H, (unsigned)a.nseq);
-  if (!bwd) {
-    if (st_bias) hipLaunchKernelGGL((attn_long_fwd_kernel<T, HD, true>), grid, 64, 0, st, p);
-    else hipLaunchKernelGGL((attn_long_fwd_kernel<T, HD, false>), grid, 64, 0, st, p);
-    if (int e = check_launch("attention_long_fwd")) return e;
-    set_last_route("long");
-    return MDT_OK;
-  }
-  if (st_bias) {
-    hipLaunchKernelGGL((attn_long_dq_kernel<T, HD, true>), grid, 64, 0, st, p);
-    hipLaunchKernelGGL((attn_long_dkv_kernel<T, HD, true>), grid, 64, 0, st, p);
-  } else {
-    hipLaunchKernelGGL((attn_long_dq_kernel<T, HD, false>), grid, 64, 0, st, p);
-    hipLaunchKernelGGL((attn_long_dkv_kernel<T, HD, false>), grid, 64, 0, st, p);
-  }
-  if (int e = check_launch("attention_long_bwd")) return e;
-  set_last_route("long");
-  return MDT_OK;
-}
-
-int attention_long_dispatch(hipStream_t st, const AttnParams& p, bool bwd) {
-  const mdt_attn_fwd_args& a = p.f;
-  // S <= 272 comes here for a plain dense bias on 128-wide heads (dispatch() in attention.hip): never ragged, and q_limit
-  // is ignored as the kernels of attention.hip ignore it — every row is computed
-  if (a.seq_offsets || (a.q_limit > 0 && a.S > 272)) {
-    set_error("attention: S=%d exceeds the 272-token limit of the single-pass kernels and the key-chunked path takes neither "
-              "ragged sequences nor q_limit (text / image sequences are always shorter)", a.S);
-    return MDT_ERR_UNSUPPORTED;
-  }
-  const bool bf = a.dtype == MDT_BF16;
-  switch (a.hd) {
-    case 16: return bf ? long_launch<bf16_t, 16>(st, p, bwd) : long_launch<float, 16>(st, p, bwd);
-    case 64: return bf ? long_launch<bf16_t, 64>(st, p, bwd) : long_launch<float, 64>(st, p, bwd);
-    case 96: return bf ? long_launch<bf16_t, 96>(st, p, bwd) : long_launch<float, 96>(st, p, bwd);
-    case 128: return bf ? long_launch<bf16_t, 128>(st, p, bwd) : long_launch<float, 128>(st, p, bwd);
-  }
-  set_error("attention (long sequences): head_dim %d unsupported (16, 64, 96 or 128)", a.hd);
-  return MDT_ERR_UNSUPPORTED;
+// The forward is one launch, the backward two (dQ with the bias gradients, then dK / dV).  attn_plan (attention.hip) has
+// refused what this path does not take: ragged sequences, and q_limit past 272 tokens.
+int attention_long_launch(hipStream_t st, const AttnParams& p, const AttnPlan& pl) {
+  return with_dtype(p.f.dtype, [&](auto t) { return with_head_dim(p.f.hd, [&](auto hd) { return with_flags(pl, [&](auto s, auto) {
+    using T = typename decltype(t)::type;
+    constexpr int HD = decltype(hd)::value;
+    constexpr bool STRUCT = decltype(s)::value;
+    constexpr int per_wg = 64 / long_parts<HD>;      // queries (keys) of a workgroup
+    const dim3 grid((unsigned)((p.f.S + per_wg - 1) / per_wg), (unsigned)p.f.H, (unsigned)p.f.nseq);
+    if (!pl.bwd) return launch_route<attn_long_fwd_kernel<T, HD, STRUCT>>("long", grid, 64, 0, st, p);
+    if (int e = launch_route<attn_long_dq_kernel<T, HD, STRUCT>>("long", grid, 64, 0, st, p)) return e;
+    return launch_route<attn_long_dkv_kernel<T, HD, STRUCT>>("long", grid, 64, 0, st, p);
+  }); }); });
 }
 
 }  // namespace mdt

@@ -38,8 +38,7 @@ namespace mdt {
 // With an odd number of 32-byte units per row (7 and 9) the eight rows of a transposed read fall on eight different 8-bank
 // groups, and the b128 slots are 14 r + chunk and 2 r + chunk: sixteen different ones, as for the 32-byte rows above.
 // TIGHT: the 272-byte rows all the same — two 288-row images of 128-wide heads (S 257 .. 272) fit 160 KiB with nothing wider.
-template <int HD, bool TIGHT = false> constexpr int v2_ld = HD < 32 ? HD : (HD <= 64 || TIGHT) ? HD + 8 : HD + 16;
-template <int HD, int NT> constexpr int v2_ld_nt = v2_ld<HD, (HD == 128 && NT > 16)>;      // a whole-row kernel's stride
+// (v2_ld<HD, TIGHT> and v2_ld_nt<HD, NT>, a whole-row kernel's stride: attention_common.hpp, next to the LDS sizes built on them)
 // K = 32 contraction steps over a head.  A 16-wide head is half a step: lanes with lane >> 4 >= 2 (k = 16 .. 31) feed zeros.
 template <int HD> constexpr int v2_ks = (HD + 31) / 32;
 
@@ -953,7 +952,6 @@ __device__ __forceinline__ void onepass_phase2(const bf16_t* img0, const bf16_t*
 // wave's 16 keys (four DPP row rotations) and stores the row sums in ITS slab of the delta image in LDS; behind a workgroup
 // barrier sweep B adds the slabs of all key tiles in tile order (bitwise reproducible) and forms dS.  The output of the forward is
 // not read at all.
-constexpr int V4_EXACT_PAIRS = 3;
 template <int HD, bool DROP, bool EXACT>
 __device__ __forceinline__ void attn_bwd_v4_body(const AttnParams& P, int rows_img, int ldq) {
   constexpr int ND = HD / 16;
@@ -1398,178 +1396,57 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-static int launch_cap(const mdt_attn_fwd_args& a) { return a.s_cap > 0 ? a.s_cap : a.S; }   // longest sequence of this launch
-
-// LDS of the one-pass kernel for rows of up to S keys; 0 = does not fit
-static size_t v4_lds_bytes(int S, int* rows_img, int* ldq) {
-  const int n_t = (S + 15) / 16;
-  *rows_img = ((n_t + 1) / 2) * 32;
-  *ldq = (n_t & 1) ? 16 * n_t : 16 * n_t + 16;        // ldq / 2 = 8 (mod 16) banks: rows 0-7 of a transposed read fall on distinct 8-bank groups
-  const size_t slabs = n_t <= 2 * V4_EXACT_PAIRS ? 7 : 0;      // attn_bwd_v4x: seven more slabs of per-key-tile row sums
-  const size_t b = (size_t)2 * *rows_img * v2_ld<64> * 2 + (size_t)(3 + slabs) * *rows_img * 4 + (size_t)16 * n_t * *ldq * 2;
-  return b <= 160 * 1024 ? b : 0;
-}
-
-// The backward kernel of a bf16 launch with head_dim 16, 64, 96 or 128 (S <= 272; length-binned launches, 64 only: s_cap <= 272).
-// Default, in order:
-//   length-binned launches (seq_ids / s_cap)              -> the family below
-//   a dense bias without structural terms                -> v1 (attention.hip: the only kernels that take one)
-//   S > 256 (ViT-L/14: 4 + 257 tokens)                   -> family
-//   S <= 80, q_limit == 0, structural bias               -> v1 (LDS-scratch kernel: tiny graphs)
-//   no dropout, q_limit == 0, S <= 112                   -> v2 (whole row in registers; with dropout it falls to 1 wave / SIMD)
-//   otherwise                                            -> family
-// The family, without a structural bias, where the one-pass dS image fits LDS (S <= 208): v5 (9-13 key tiles, persistent),
-// v4x (<= 6 key tiles: delta = sum P o dP summed in the kernel, in fp32), v4 (7-8 key tiles); past that, and with a
-// structural bias: the two-pass v3.  Measured at C2 shapes: profiles/round1_attention_v2.txt, tools/attn_onepass_ab.py.
-// The one-pass kernels are written for 64-wide heads: with head_dim 16, 96 or 128 the family is always v3.
-// A plain dense bias on 128-wide heads of more than 208 tokens never gets here: the v1 images do not fit LDS there and
-// dispatch() in attention.hip takes the key-chunked long path (attn_v1_fits).
-// MDT_ATTN_BWD=<kernel> takes that kernel wherever its preconditions (ok() below) hold.  v1 and v2 never see q_limit or
-// length bins (they would read the out / lse rows the v2 forward skipped — unwritten memory; tests:
-// ..._never_reads_what_forward_did_not_write), v2 takes S <= 112 only, the one-pass kernels take no structural bias.
-AttnRoute attn_bwd_route(const AttnParams& p) {
-  const mdt_attn_fwd_args& a = p.f;
-  const bool st_bias = a.attn_bias != nullptr, binned = a.seq_ids != nullptr || a.s_cap > 0;
-  const bool dense_only = (a.dense_bias != nullptr || p.d_dense_bias != nullptr) && !st_bias;
-  const int cap = launch_cap(a);
-  const int n_t = (cap + 15) / 16;
-  int rows_img = 0, ldq = 0;
-  const bool one_pass = a.hd == 64 && !st_bias && !dense_only && v4_lds_bytes(cap, &rows_img, &ldq) != 0 && n_t <= 16;
-  auto ok = [&](AttnRoute r) {
-    switch (r) {
-      case AttnRoute::v1: return !binned && a.q_limit == 0 && attn_v1_fits(a.hd, a.S);
-      case AttnRoute::v2: return !binned && !dense_only && a.q_limit == 0 && a.S <= 112;
-      case AttnRoute::v3: return !dense_only;
-      case AttnRoute::v4: return one_pass;
-      case AttnRoute::v4x: return one_pass && n_t <= 2 * V4_EXACT_PAIRS;
-      case AttnRoute::v5: return one_pass && n_t > 8 && rows_img * 8 <= 4 * 512;     // long rows (one workgroup per CU by LDS)
-      default: return false;
-    }
-  };
-  const AttnRoute family = ok(AttnRoute::v5) ? AttnRoute::v5 : ok(AttnRoute::v4x) ? AttnRoute::v4x : one_pass ? AttnRoute::v4 : AttnRoute::v3;
-  AttnRoute r;
-  if (binned) r = family;
-  else if (dense_only) r = AttnRoute::v1;
-  else if (a.S > 256) r = family;
-  else if (a.S <= 80 && a.q_limit == 0 && st_bias) r = AttnRoute::v1;
-  else if (!(a.drop_p > 0.f) && ok(AttnRoute::v2)) r = AttnRoute::v2;
-  else r = family;
-  const AttnRoute forced = switches().attn_bwd;
-  return forced != AttnRoute::none && ok(forced) ? forced : r;
-}
-
-// (structural bias, dropout) of a launch and its head width as template arguments (with_layout / with_epilogue in gemm.hip)
-template <typename F>
-static int with_flags(const AttnParams& p, F&& f) {
-  using T = std::true_type;
-  using N = std::false_type;
-  const bool s = p.f.attn_bias != nullptr, d = p.f.drop_p > 0.f;
-  if (s && d) return f(T{}, T{});
-  if (s) return f(T{}, N{});
-  if (d) return f(N{}, T{});
-  return f(N{}, N{});
-}
-// head_dim: 16, 64, 96 or 128 (dispatch() in attention.hip refuses every other width before it gets here)
-template <typename F>
-static int with_head_dim(int hd, F&& f) {
-  switch (hd) {
-    case 16: return f(std::integral_constant<int, 16>{});
-    case 96: return f(std::integral_constant<int, 96>{});
-    case 128: return f(std::integral_constant<int, 128>{});
-    default: return f(std::integral_constant<int, 64>{});
-  }
-}
-
-// the one-pass kernels (64-wide heads, no structural bias): r is v4 | v4x | v5
+// ---------------------------------------------------------------------------- launchers (the plan: attn_plan, attention.hip)
+// the one-pass kernels (64-wide heads, no structural bias): v4 | v4x | v5
 template <bool DROP>
-static int launch_one_pass(hipStream_t st, const AttnParams& p, AttnRoute r) {
+static int launch_one_pass(hipStream_t st, const AttnParams& p, const AttnPlan& pl) {
   // In-call A/B with dropout 0.1 (tools/attn_onepass_ab.py): ViT rows (512 x 201) 755 -> 525 us, padded BERT rows
   // (2048 x 104) 993 -> 792 us, ragged BERT rows (8-100 tokens) 592 -> 493 us; gradients equal to bf16 rounding of delta.
-  const int cap = launch_cap(p.f);
   const dim3 grid(p.f.H, p.f.nseq);
-  int rows_img = 0, ldq = 0;
-  const size_t lds4 = v4_lds_bytes(cap, &rows_img, &ldq);
-  const int n_t = (cap + 15) / 16;
-  if (r == AttnRoute::v5) {
-    const int64_t n_items = (int64_t)p.f.H * p.f.nseq;
-    const int cus = device_cus();
-    return launch_route<attn_bwd_v5_kernel<64, DROP>>("v5", dim3((unsigned)(n_items < cus ? n_items : cus)), 512, lds4, st, p,
-                                                      rows_img, ldq, (int)n_items);
-  }
-  const int waves = n_t <= 4 ? 4 : n_t <= 8 ? 8 : 16;          // two 16-byte chunks per thread and image, one key tile per wave
-  if (r == AttnRoute::v4x) return launch_route<attn_bwd_v4x_kernel<64, DROP>>("v4x", grid, waves * 64, lds4, st, p, rows_img, ldq);
-  return launch_route<attn_bwd_v4_kernel<64, DROP>>("v4", grid, waves * 64, lds4, st, p, rows_img, ldq);
+  const size_t lds = attn_one_pass_lds_bytes(pl.n_t);
+  if (pl.route == AttnRoute::v5) return launch_route<attn_bwd_v5_kernel<64, DROP>>("v5", dim3((unsigned)pl.wgs), 512, lds, st, p, pl.rows_img, pl.ldq, pl.items);
+  if (pl.route == AttnRoute::v4x) return launch_route<attn_bwd_v4x_kernel<64, DROP>>("v4x", grid, pl.waves * 64, lds, st, p, pl.rows_img, pl.ldq);
+  return launch_route<attn_bwd_v4_kernel<64, DROP>>("v4", grid, pl.waves * 64, lds, st, p, pl.rows_img, pl.ldq);
 }
 
 template <int HD, bool STRUCT, bool DROP>
-static int launch_v3(hipStream_t st, const AttnParams& p, AttnRoute r) {
+static int launch_v3(hipStream_t st, const AttnParams& p, const AttnPlan& pl) {
   if constexpr (HD == 64 && !STRUCT) {
-    if (r != AttnRoute::v3) return launch_one_pass<DROP>(st, p, r);
+    if (pl.route != AttnRoute::v3) return launch_one_pass<DROP>(st, p, pl);
   }
-  const int cap = launch_cap(p.f);
-  const bool tight = HD == 128 && cap > 256;                  // 320 rows of 128-wide heads do not fit: 288 rows, 32-key chunks
-  const int s_pad = tight ? (cap + 31) & ~31 : (cap + 63) & ~63;
-  const int nhist = STRUCT ? attn_hist_size(p.f.num_spatial) : 0;
-  const size_t lds = (size_t)2 * s_pad * (tight ? v2_ld<HD, true> : v2_ld<HD>) * 2 + (size_t)3 * s_pad * 4 + (size_t)nhist * 4;
-  if (lds > 160 * 1024) { set_error("attention_bwd_v3: S=%d needs %zu bytes of LDS", cap, lds); return MDT_ERR_UNSUPPORTED; }
+  const size_t lds = attn_v3_lds_bytes(HD, pl.s_pad, pl.tight, pl.nhist);
   const dim3 grid(p.f.H, p.f.nseq);
   if constexpr (HD > 64) {
     // wide heads: dK / dV alone are 2 x HD / 16 accumulator tiles — the 128-register build below would spill them
-    if (tight) return launch_route<attn_bwd_v3_tight_kernel<HD, STRUCT, DROP>>("v3", grid, 256, lds, st, p, s_pad);
-    return launch_route<attn_bwd_v3_kernel<HD, STRUCT, DROP>>("v3", grid, 256, lds, st, p, s_pad);
-  } else if constexpr (STRUCT) return launch_route<attn_bwd_v3_kernel<HD, true, DROP>>("v3", grid, 256, lds, st, p, s_pad);
-  // long sequences (ViT: 13 tiles): LDS allows two workgroups per CU; 8 waves each in the 128-register build = 4 waves
-  // per SIMD instead of 2 (in-call A/B at the ViT shape: +0.7 % on the step)
-  else return launch_route<attn_bwd_v3_occ4_kernel<HD, DROP>>("v3", grid, s_pad <= 128 ? 256 : 512, lds, st, p, s_pad);
-}
-
-int attention_v3_bwd_dispatch(hipStream_t st, const AttnParams& p, AttnRoute r) {
-  return with_head_dim(p.f.hd, [&](auto hd) {
-    return with_flags(p, [&](auto s, auto d) { return launch_v3<decltype(hd)::value, decltype(s)::value, decltype(d)::value>(st, p, r); });
-  });
+    if (pl.tight) return launch_route<attn_bwd_v3_tight_kernel<HD, STRUCT, DROP>>("v3", grid, pl.threads, lds, st, p, pl.s_pad);
+    return launch_route<attn_bwd_v3_kernel<HD, STRUCT, DROP>>("v3", grid, pl.threads, lds, st, p, pl.s_pad);
+  } else if constexpr (STRUCT) return launch_route<attn_bwd_v3_kernel<HD, true, DROP>>("v3", grid, pl.threads, lds, st, p, pl.s_pad);
+  else return launch_route<attn_bwd_v3_occ4_kernel<HD, DROP>>("v3", grid, pl.threads, lds, st, p, pl.s_pad);      // 256 or 512 threads: attn_plan
 }
 
 template <int HD, int NT, bool STRUCT, bool DROP, bool BWD>
-static int launch_v2(hipStream_t st, const AttnParams& p) {
-  constexpr int S_PAD = ((NT + 1) / 2) * 32;
-  const int nhist = (STRUCT && BWD) ? attn_hist_size(p.f.num_spatial) : 0;
-  const size_t lds = (size_t)2 * S_PAD * (BWD ? v2_ld<HD> : v2_ld_nt<HD, NT>) * 2 + (size_t)(BWD ? 3 : 1) * S_PAD * 4 + (size_t)nhist * 4 + (BWD ? 0 : 16);   // forward: + the staging's spare chunk
-  if constexpr (BWD && NT > 7) {
-    // the whole-row backward runs out of registers past 112 keys; attn_bwd_route sends those to the v3 family
-    set_error("attention_v2: backward supports S <= 112 (got %d)", p.f.S);
-    return MDT_ERR_UNSUPPORTED;
-  } else {
-    constexpr int NWF = (NT >= 13 && !STRUCT) ? 8 : 4;     // forward: 8 waves for the long (ViT) rows, 4 waves per SIMD
-    if constexpr (BWD) return launch_route<attn_bwd_v2_kernel<HD, NT, STRUCT, DROP>>("v2", dim3(p.f.H, p.f.nseq), 256, lds, st, p);
-    else return launch_route<attn_fwd_v2_kernel<HD, NT, STRUCT, DROP, NWF>>("v2", dim3(p.f.H, p.f.nseq), NWF * 64, lds, st, p);
+static int launch_v2(hipStream_t st, const AttnParams& p, const AttnPlan& pl) {
+  const size_t lds = attn_v2_lds_bytes(HD, NT, BWD, pl.nhist);
+  const dim3 grid(p.f.H, p.f.nseq);
+  // the whole-row backward runs out of registers past 112 keys: not instantiated, attn_plan routes those to the v3 family
+  if constexpr (BWD && NT > 7) return attn_unplanned("the v2 backward past 112 keys");
+  else if constexpr (BWD) return launch_route<attn_bwd_v2_kernel<HD, NT, STRUCT, DROP>>("v2", grid, 256, lds, st, p);
+  else {
+    constexpr int NWF = attn_v2_fwd_waves(NT, STRUCT);
+    return launch_route<attn_fwd_v2_kernel<HD, NT, STRUCT, DROP, NWF>>("v2", grid, NWF * 64, lds, st, p);
   }
 }
 
-// the key-tile rung of a whole-row launch as a template argument: the first that holds the launch's longest sequence
-template <typename F>
-static int with_rung(const AttnParams& p, F&& f) {
-  const int nt = (launch_cap(p.f) + 15) / 16;
-  if (nt <= 2) return f(std::integral_constant<int, 2>{});
-  if (nt <= 4) return f(std::integral_constant<int, 4>{});
-  if (nt <= 5) return f(std::integral_constant<int, 5>{});
-  if (nt <= 7) return f(std::integral_constant<int, 7>{});
-  if (nt <= 9) return f(std::integral_constant<int, 9>{});
-  if (nt <= 13) return f(std::integral_constant<int, 13>{});
-  if (nt <= 17) return f(std::integral_constant<int, 17>{});
-  set_error("attention_v2: S=%d exceeds 272", p.f.S);
-  return MDT_ERR_UNSUPPORTED;
-}
-
-int attention_v2_dispatch(hipStream_t st, const AttnParams& p, bool bwd) {
-  return with_head_dim(p.f.hd, [&](auto hd) {
-    return with_flags(p, [&](auto s, auto d) {
-      return with_rung(p, [&](auto nt) {
-        constexpr int HD = decltype(hd)::value, NT = decltype(nt)::value;
-        constexpr bool STRUCT = decltype(s)::value, DROP = decltype(d)::value;
-        return bwd ? launch_v2<HD, NT, STRUCT, DROP, true>(st, p) : launch_v2<HD, NT, STRUCT, DROP, false>(st, p);
-      });
+int attention_v2_launch(hipStream_t st, const AttnParams& p, const AttnPlan& pl) {
+  return with_head_dim(p.f.hd, [&](auto hd) { return with_flags(pl, [&](auto s, auto d) {
+    constexpr int HD = decltype(hd)::value;
+    constexpr bool STRUCT = decltype(s)::value, DROP = decltype(d)::value;
+    if (pl.route != AttnRoute::v2) return launch_v3<HD, STRUCT, DROP>(st, p, pl);      // v3 | v4 | v4x | v5
+    return with_rung<2, 4, 5, 7, 9, 13, 17>(pl.rung, [&](auto nt) {
+      constexpr int NT = decltype(nt)::value;
+      return pl.bwd ? launch_v2<HD, NT, STRUCT, DROP, true>(st, p, pl) : launch_v2<HD, NT, STRUCT, DROP, false>(st, p, pl);
     });
-  });
+  }); });
 }
 
 }  // namespace mdt

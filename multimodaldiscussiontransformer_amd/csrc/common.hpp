@@ -46,7 +46,7 @@ void note_float_atomic_launch();
 int sum_slices_f32(hipStream_t st, int64_t rows, int64_t cols, int slices, const float* ws, int64_t ld_ws, int64_t slice_stride,
                    float* out, int64_t ldo, int accumulate);
 
-// Routes: the kernel a GEMM / attention-backward launch takes (gemm.hip plan_gemm, attention_v2.hip attn_bwd_route).
+// Routes: the kernel a GEMM / attention launch takes (gemm.hip plan_gemm, attention.hip attn_plan).
 // MDT_GEMM_ROUTE / MDT_ATTN_BWD name one to force it; mdt_last_route() reports the route of the last launch.
 enum class GemmRoute { none, generic, tile128, tile256x128, pp256, pp256p, w4p, w4s };
 inline constexpr const char* GEMM_ROUTE_NAMES[] = {"", "generic", "tile128", "tile256x128", "pp256", "pp256p", "w4p", "w4s"};
@@ -64,7 +64,7 @@ struct Switches {
   bool gemm_stamp;           // MDT_GEMM_STAMP
   int gemm_diag;             // MDT_GEMM_DIAG      (0: none)
   int gemm_f8w;              // MDT_GEMM_F8W       (default 1: 8-bit GEMMs on the 16x16x128 block-MFMA kernel where it has an instantiation; 0: the 8-wave kernel)
-  AttnRoute attn_bwd;        // MDT_ATTN_BWD       (none: the default kernel) v1 | v2 | v3 | v4 | v4x | v5 — bf16 backward (head_dim 16 / 96 / 128: v1 | v2 | v3)
+  AttnRoute attn_bwd;        // MDT_ATTN_BWD       (none: the default kernel) v1 | v2 | v3 | v4 | v4x | v5 — bf16 backward, where attn_plan's ok() holds (head_dim 16 / 96 / 128: v1 | v2 | v3)
   bool ln_generic;           // MDT_LN_GENERIC     (default 0; 1: bf16 rows of 256 / 512 / 768 / 1024 take the generic LayerNorm backward kernel — tests, A/B runs)
   int ln_bwd_wgs;            // MDT_LN_BWD_WGS     (workgroups a LayerNorm backward launch aims for; tuning)
 };

@@ -120,6 +120,11 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, add=None, dgamma=None, dbeta=None, d
 
 def _attn_args(qkv, out, lse, nseq, S, H, hd, seq_stride, pos_stride, scale, key_mask, dense_bias, attn_bias,
                spatial_pos, sp_table, virt, key_pad, drop_p=0.0, drop_seed=0, seq_offsets=None, q_limit=0, seq_ids=None, s_cap=0):
+    """The forward argument block of qkv [rows, 3 * H * hd].  The defaults every wrapper wants are taken here, for None:
+    hd = the row width / 3 / H, seq_stride = S rows per sequence, scale = hd ** -0.5."""
+    hd = qkv.shape[1] // 3 // H if hd is None else hd
+    seq_stride = S if seq_stride is None else seq_stride
+    scale = hd ** -0.5 if scale is None else scale
     a = L.AttnFwdArgs()
     a.q_limit = int(q_limit)
     a.drop_p, a.drop_seed = float(drop_p), int(drop_seed)
@@ -150,6 +155,23 @@ def _attn_args(qkv, out, lse, nseq, S, H, hd, seq_stride, pos_stride, scale, key
     return a
 
 
+def _attn_bins(bins, qkv, H, S):
+    """One (seq_ids, s_cap) per launch: the length bins of a ragged set where the library takes them (bf16, head width 64,
+    S <= 272: the rule attn_plan of csrc/attention.hip refuses everything else by), else the one launch of the whole set."""
+    if bins is None or qkv.dtype != torch.bfloat16 or qkv.shape[1] // 3 // H != 64 or S > 272:
+        return [(None, 0)]
+    return [(ids, cap) for ids, cap in bins if ids.numel() > 0]
+
+
+def attention_route(args, bwd):
+    """(route, (g0, g1)) of the launch mdt_attention_fwd / mdt_attention_bwd would make of the argument block ``args``
+    (L.AttnBwdArgs; the forward reads args.f only), by mdt_attention_route: nothing is launched and no pointer of the block
+    is dereferenced, so it runs without a device.  A refused block raises as the launch would."""
+    name, geo = C.create_string_buffer(16), (C.c_int32 * 2)()
+    check(lib.mdt_attention_route(C.byref(args), int(bool(bwd)), name, len(name), geo), "mdt_attention_route")
+    return name.value.decode(), (geo[0], geo[1])
+
+
 def attention_fwd(qkv, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None, key_mask=None, dense_bias=None,
                   attn_bias=None, spatial_pos=None, sp_table=None, virt=None, key_pad=None, drop_p=0.0, drop_seed=0,
                   seq_offsets=None, q_limit=0, bins=None):
@@ -160,21 +182,15 @@ def attention_fwd(qkv, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None,
     — a partition of the ragged set by length (no sequence of a bin longer than its cap): one launch per bin, each with
     the kernels that fit its cap; results are identical to the single launch."""
     D = qkv.shape[1] // 3
-    hd = D // H
     # No fill, also with q_limit: the kernels that honour it (bf16) write whole 16-row query tiles, and the backward
     # kernels dispatched for such a launch read exactly those rows of out / lse and nothing past them
     # (tests/test_kernels_gpu.py::test_attention_backward_never_reads_what_forward_did_not_write); every other kernel family ignores
     # q_limit and writes all rows.  Positions of lse past a ragged sequence's length are never read either.
     out = torch.empty(qkv.shape[0], D, dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(nseq, H, S, dtype=torch.float32, device=qkv.device)
-    if bins is not None and (qkv.dtype != torch.bfloat16 or hd != 64 or S > 272):
-        bins = None                      # the binned launches exist for the bf16 head-dim-64 kernels only
-    for ids, cap in (bins or [(None, 0)]):
-        if ids is not None and ids.numel() == 0:
-            continue
-        a = _attn_args(qkv, out, lse, nseq, S, H, hd, S if seq_stride is None else seq_stride, pos_stride,
-                       hd ** -0.5 if scale is None else scale, key_mask, dense_bias, attn_bias, spatial_pos, sp_table,
-                       virt, key_pad, drop_p, drop_seed, seq_offsets, q_limit, ids, cap)
+    for ids, cap in _attn_bins(bins, qkv, H, S):
+        a = _attn_args(qkv, out, lse, nseq, S, H, None, seq_stride, pos_stride, scale, key_mask, dense_bias, attn_bias, spatial_pos,
+                       sp_table, virt, key_pad, drop_p, drop_seed, seq_offsets, q_limit, ids, cap)
         check(lib.mdt_attention_fwd(stream(), C.byref(a)), "mdt_attention_fwd")
     return out, lse
 
@@ -182,11 +198,9 @@ def attention_fwd(qkv, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None,
 def attention_mean_probs(qkv, lse, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None, key_mask=None, dense_bias=None,
                          attn_bias=None, spatial_pos=None, sp_table=None, virt=None, key_pad=None):
     """Head-averaged attention probabilities f32[nseq, S, S] from the qkv buffer and the forward's lse."""
-    D = qkv.shape[1] // 3
-    hd = D // H
     out = torch.empty(nseq, S, S, dtype=torch.float32, device=qkv.device)
-    a = _attn_args(qkv, qkv, lse, nseq, S, H, hd, S if seq_stride is None else seq_stride, pos_stride,
-                   hd ** -0.5 if scale is None else scale, key_mask, dense_bias, attn_bias, spatial_pos, sp_table, virt, key_pad)
+    a = _attn_args(qkv, qkv, lse, nseq, S, H, None, seq_stride, pos_stride, scale, key_mask, dense_bias, attn_bias, spatial_pos, sp_table,
+                   virt, key_pad)
     check(lib.mdt_attention_mean_probs(stream(), C.byref(a), ptr(out)), "mdt_attention_mean_probs")
     return out
 
@@ -195,14 +209,12 @@ def attention_head_weights(qkv, lse, nseq, S, H, *, raw_scores=False, seq_stride
                            dense_bias=None, attn_bias=None, spatial_pos=None, sp_table=None, virt=None, key_pad=None):
     """Per-head attention weights f32[nseq, H, S, S]: the softmax probabilities before dropout (needs the forward's ``lse``), or
     with ``raw_scores`` the scores q k^T * scale + bias with masked keys at -inf (``lse`` may be None)."""
-    D = qkv.shape[1] // 3
-    hd = D // H
     out = torch.empty(nseq, H, S, S, dtype=torch.float32, device=qkv.device)
     if lse is None:            # raw scores do not read it; the argument check wants a buffer
         assert raw_scores
         lse = torch.empty(nseq * H * S, dtype=torch.float32, device=qkv.device)
-    a = _attn_args(qkv, qkv, lse, nseq, S, H, hd, S if seq_stride is None else seq_stride, pos_stride,
-                   hd ** -0.5 if scale is None else scale, key_mask, dense_bias, attn_bias, spatial_pos, sp_table, virt, key_pad)
+    a = _attn_args(qkv, qkv, lse, nseq, S, H, None, seq_stride, pos_stride, scale, key_mask, dense_bias, attn_bias, spatial_pos, sp_table,
+                   virt, key_pad)
     check(lib.mdt_attention_head_weights(stream(), C.byref(a), 1 if raw_scores else 0, ptr(out)), "mdt_attention_head_weights")
     return out
 
@@ -212,7 +224,6 @@ def attention_bwd(dout, qkv, out, lse, nseq, S, H, *, seq_stride=None, pos_strid
                   want_dense_dbias=False, d_sp_table=None, d_virt=None, drop_p=0.0, drop_seed=0, seq_offsets=None, q_limit=0,
                   bins=None):
     D = qkv.shape[1] // 3
-    hd = D // H
     # with q_limit the kernels skip the query rows beyond it: their dQ must read as zero (dK / dV are written for every row)
     dqkv = torch.empty_like(qkv)
     if q_limit:
@@ -220,15 +231,10 @@ def attention_bwd(dout, qkv, out, lse, nseq, S, H, *, seq_stride=None, pos_strid
     dbias = None
     if want_dense_dbias:
         dbias = torch.zeros(nseq, H, S, S, dtype=torch.float32, device=qkv.device)
-    if bins is not None and (qkv.dtype != torch.bfloat16 or hd != 64 or S > 272):
-        bins = None
-    for ids, cap in (bins or [(None, 0)]):
-        if ids is not None and ids.numel() == 0:
-            continue
+    for ids, cap in _attn_bins(bins, qkv, H, S):
         b = L.AttnBwdArgs()
-        b.f = _attn_args(qkv, out, lse, nseq, S, H, hd, S if seq_stride is None else seq_stride, pos_stride,
-                         hd ** -0.5 if scale is None else scale, key_mask, dense_bias, attn_bias, spatial_pos, sp_table,
-                         virt, key_pad, drop_p, drop_seed, seq_offsets, q_limit, ids, cap)
+        b.f = _attn_args(qkv, out, lse, nseq, S, H, None, seq_stride, pos_stride, scale, key_mask, dense_bias, attn_bias, spatial_pos,
+                         sp_table, virt, key_pad, drop_p, drop_seed, seq_offsets, q_limit, ids, cap)
         b.dout, b.ld_dout = ptr(dout), _2d(dout)
         b.dqkv, b.ld_dqkv = ptr(dqkv), _2d(dqkv)
         b.d_dense_bias = ptr(dbias)

@@ -352,7 +352,7 @@ def _one_pass_fits(cap):
 
 
 def bwd_ok(route, hd, S, mode, qlim=0, cap=0):
-    """ok() of attn_bwd_route (csrc/attention_v2.hip) for a bf16 launch of S <= 272: may MDT_ATTN_BWD=route be honoured."""
+    """ok() of attn_plan (csrc/attention.hip) for a bf16 launch of S <= 272: may MDT_ATTN_BWD=route be honoured."""
     binned = cap > 0
     c = cap or S
     n_t = (c + 15) // 16
@@ -367,11 +367,12 @@ def bwd_ok(route, hd, S, mode, qlim=0, cap=0):
 
 
 def bwd_route(dtype, hd, S, mode, p=0.0, qlim=0, cap=0, forced=None):
-    """The backward route of a launch (dispatch() of csrc/attention.hip and attn_bwd_route of csrc/attention_v2.hip)."""
+    """The backward route of a launch (attn_plan of csrc/attention.hip, restated independently: this module never asks the
+    library for a route; tests/test_attention_plan_cpu.py holds the two against each other over the whole domain)."""
     if S > 272:
         return "long"
     if dtype != BF:
-        return "v1"
+        return "long" if fp32_bwd_long(hd, S, mode, p) else "v1"
     if mode == "dense" and not v1_fits(hd, S):
         return "long"
     if forced and bwd_ok(forced, hd, S, mode, qlim, cap):
@@ -390,6 +391,12 @@ def bwd_route(dtype, hd, S, mode, p=0.0, qlim=0, cap=0, forced=None):
     return family
 
 
+def fp32_bwd_long(hd, S, mode, p):
+    """The fp32 v1 backward that is not built — wide heads, the 17-tile rung (14 .. 17 key tiles: S 209 .. 272), structural bias
+    and dropout (512 registers and scratch memory) — runs on the key-chunked path."""
+    return hd > 64 and v1_rung(S) == 17 and mode == "struct" and p > 0
+
+
 def fwd_route(dtype, hd, S, mode):
     if S > 272:
         return "long"
@@ -400,7 +407,34 @@ def fwd_route(dtype, hd, S, mode):
     return "v2"
 
 
-def bwd_rung(route, hd, S, cap=0):
+WIDTHS = (16, 64, 96, 128)
+
+
+def refusal(dtype, hd, S, qlim=0, ragged=False, cap=0):
+    """None, or why a launch that passed the argument checks is refused before any route (in the order the library decides):
+    "bins": seq_ids / s_cap on anything but a ragged bf16 launch of 64-wide heads with S <= 272; "long": the key-chunked path
+    (S > 272) takes neither ragged sequences nor q_limit; "head_dim": a width outside WIDTHS.  (A v3 launch whose structural-bias
+    histogram does not fit LDS beside its images is refused too: that depends on num_spatial, which no case here varies.)"""
+    if cap:
+        if S > 272 or dtype != BF or hd != 64 or not ragged:
+            return "bins"
+    elif S > 272 and (ragged or qlim):
+        return "long"
+    return None if hd in WIDTHS else "head_dim"
+
+
+def fwd_rung(route, S, mode, cap=0):
+    """The forward's counterpart of bwd_rung: the rung of v1, (rung, waves) of v2 — 8 waves for the long rows (13 key tiles
+    and more) without a structural bias — and nothing for long."""
+    if route == "v1":
+        return v1_rung(S)
+    if route == "v2":
+        r = v2_rung(cap or S)
+        return (r, 8 if r >= 13 and mode != "struct" else 4)
+    return 0
+
+
+def bwd_rung(route, hd, S, cap=0, mode="none"):
     """What distinguishes two launches of one route: the tile-count rung (v1, v2), the padded length and thread count (v3),
     the wave count (v4, v4x), nothing (v5, long)."""
     c = cap or S
@@ -412,7 +446,7 @@ def bwd_rung(route, hd, S, cap=0):
     if route == "v3":
         tight = hd == 128 and c > 256
         s_pad = (c + 31) & ~31 if tight else (c + 63) & ~63
-        return (s_pad, 512 if (hd <= 64 and s_pad > 128) else 256)           # 512 threads: the plain (no structural bias) build
+        return (s_pad, 512 if (hd <= 64 and s_pad > 128 and mode != "struct") else 256)   # 512 threads: the plain (no structural bias) build
     if route in ("v4", "v4x"):
         return 4 if n_t <= 4 else 8 if n_t <= 8 else 16
     return 0
@@ -506,7 +540,10 @@ def ar_(S):
 
 
 def is_long(c: Case):
-    return c.S > 272 or (c.dtype == BF and c.mode == "dense" and not v1_fits(c.hd, c.S))
+    """The key-chunked path runs: past 272 tokens, a dense bias on bf16 heads the v1 images do not fit, and — the backward
+    only, whose forward ran v1 in fp32 and is held to the looser of the two models' bounds — the fp32 launch of fp32_bwd_long."""
+    return c.S > 272 or (c.dtype == BF and c.mode == "dense" and not v1_fits(c.hd, c.S)) or \
+        (c.dtype == F32 and fp32_bwd_long(c.hd, c.S, c.mode, c.p))
 
 
 _REF = {}
@@ -548,5 +585,6 @@ LONG = tuple((dtype, 64, S, mode) for dtype in (F32, BF) for S in (273, 320) for
 WIDE = (  # (hd, S, mode): one case per reachable forward / backward route of the other widths
     (16, 33, "dense"), (16, 65, "struct"), (16, 97, "none"), (16, 129, "struct"), (16, 257, "mask"),
     (96, 33, "dense"), (96, 65, "struct"), (96, 97, "none"), (96, 129, "struct"), (96, 257, "mask"),
+    (96, 257, "struct"),          # fp32 with dropout: the backward v1 does not build (fp32_bwd_long) -> long; bf16: the v3 family
     (128, 33, "dense"), (128, 65, "struct"), (128, 97, "none"), (128, 129, "struct"), (128, 256, "none"), (128, 257, "none"),
 )

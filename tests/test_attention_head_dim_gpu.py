@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import tests.attention_reference as A
 from multimodaldiscussiontransformer_amd import _lib as L
 from tests.test_dropout_gpu import attn_mask
 from tests.test_kernels_gpu import dense_from_struct, dev, make_struct, ref_attention, rnd
@@ -44,17 +45,6 @@ def force_bwd(monkeypatch):
     yield set_
     monkeypatch.delenv("MDT_ATTN_BWD", raising=False)
     L.reload_env()
-
-
-def default_bwd_route(S, mode, p=0.0, qlim=0):
-    """attn_bwd_route for head_dim 16: the one-pass kernels are 64-only, so the family is always v3."""
-    if mode == "dense":
-        return "v1"
-    if mode == "struct" and S <= 80 and not qlim:
-        return "v1"
-    if p == 0.0 and S <= 112 and not qlim:
-        return "v2"
-    return "v3"
 
 
 # ----------------------------------------------------------------------------- forward + backward against torch fp32
@@ -110,7 +100,7 @@ def test_attention_head_dim_16_bf16(ops, nseq, S, H, mode, time_major):
         d2 = dev(dout.view(nseq * S, D))
         lay = dict(seq_stride=S, pos_stride=1)
     out, lse = ops.attention_fwd(q2, nseq, S, H, scale=scale, **lay, **kw)
-    assert L.last_route() == ("v1" if mode == "dense" else "v2"), L.last_route()
+    assert L.last_route() == A.fwd_route(BF, HD, S, mode), L.last_route()
 
     def unlay(t, width):
         t = t.float().cpu()
@@ -128,7 +118,7 @@ def test_attention_head_dim_16_bf16(ops, nseq, S, H, mode, time_major):
                      d_virt=torch.zeros(H, dtype=torch.float32).cuda())
     dqkv, dbias = ops.attention_bwd(d2, q2, out, lse, nseq, S, H, scale=scale, **lay, **kw,
                                     want_dense_dbias=(mode == "dense"), **extra)
-    assert L.last_route() == default_bwd_route(S, mode), L.last_route()
+    assert L.last_route() == A.bwd_route(BF, HD, S, mode), L.last_route()
     gtol = dict(atol=0.06, rtol=5e-2)
     print(f"[hd16 {mode} S={S}] dqkv |err| {float((unlay(dqkv, 3 * D) - qr.grad).abs().max()):.3e} on {L.last_route()}")
     torch.testing.assert_close(unlay(dqkv, 3 * D), qr.grad, **gtol)
@@ -147,7 +137,7 @@ def test_attention_head_dim_16_bf16(ops, nseq, S, H, mode, time_major):
 
 
 def test_cases_reach_every_backward_kernel():
-    routes = {default_bwd_route(S, mode) for _, S, _, mode, _ in CASES}
+    routes = {A.bwd_route(BF, HD, S, mode) for _, S, _, mode, _ in CASES}
     assert routes == {"v1", "v2", "v3"}
     assert {S for _, S, _, _, _ in CASES} == {8, 17, 33, 65, 104, 129, 201, 261}
 
@@ -343,7 +333,7 @@ def test_head_dim_16_equals_zero_padded_head_dim_64(ops, S, mode, p, bwd, force_
     g16, _ = ops.attention_bwd(d16, q16, o16, l16, nseq, S, H, **kw, **extra16)
     r16 = L.last_route()
     g64, _ = ops.attention_bwd(d64, q64, o64, l64, nseq, S, H, **kw, **extra64)
-    assert r16 == L.last_route() == (bwd or default_bwd_route(S, mode, p)), (r16, L.last_route())
+    assert r16 == L.last_route() == (bwd or A.bwd_route(BF, HD, S, mode, p)), (r16, L.last_route())
     tol = dict(rtol=2.0 ** -8, atol=1e-5)
     torch.testing.assert_close(o16.float().view(-1, H, 16), o64.float().view(-1, H, 64)[..., :16], **tol)
     fin = torch.isfinite(l64)

@@ -291,7 +291,7 @@ def test_vacuous_bound_is_refused():
 
 
 def test_matrix_reaches_every_route_and_rung():
-    """attn_bwd_route and the forward dispatch, mirrored in attention_reference, over the launches of the GPU matrix: every
+    """attn_plan (csrc/attention.hip), mirrored in attention_reference, over the launches of the GPU matrix: every
     (route, rung) pair a head-width-64 launch can take is reached, by default or forced."""
     fwd, bwd = set(), set()
     for dtype, mode, tm, S in A.main_cases():

@@ -5,7 +5,7 @@ inputs with the head_dim 64 gates, and against the head_dim 64 kernels themselve
 A 96-wide head is three K = 32 contraction steps and six 16-column output tiles, a 128-wide head four and eight.  Every case
 has H >= 3 heads with independent random data per head: a fragment that strayed into its neighbour would show.
 
-Routing of the backward (bf16), as attn_bwd_route states it for every width but 64 — the one-pass kernels are 64-only:
+Routing of the backward (bf16), as attn_plan (csrc/attention.hip) states it for every width but 64 — the one-pass kernels are 64-only:
     dense bias                                   v1, except head_dim 128 with S > 208: the two [288][136] images of the v1
                                                  kernels are past 160 KiB there, forward and backward take the long path
     structural bias, S <= 80, no q_limit         v1
@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+import tests.attention_reference as A
 from multimodaldiscussiontransformer_amd import _lib as L
 from tests.test_attention_head_dim_gpu import force_bwd, ops  # noqa: F401  (fixtures)
 from tests.test_dropout_gpu import attn_mask
@@ -30,22 +31,6 @@ pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
 WIDTHS = [96, 128]
-
-
-def default_fwd_route(hd, S, mode):
-    if mode == "dense":
-        return "long" if hd == 128 and S > 208 else "v1"
-    return "v2"
-
-
-def default_bwd_route(hd, S, mode, p=0.0, qlim=0):
-    if mode == "dense":
-        return "long" if hd == 128 and S > 208 else "v1"
-    if mode == "struct" and S <= 80 and not qlim:
-        return "v1"
-    if p == 0.0 and S <= 112 and not qlim:
-        return "v2"
-    return "v3"
 
 
 # ----------------------------------------------------------------------------- forward + backward against torch fp32
@@ -102,8 +87,7 @@ def run_case(ops, dtype, hd, nseq, S, H, mode, time_major, tag):
         d2 = dev(dout.view(nseq * S, D))
         lay = dict(seq_stride=S, pos_stride=1)
     out, lse = ops.attention_fwd(q2, nseq, S, H, scale=scale, **lay, **kw)
-    if bf:
-        assert L.last_route() == default_fwd_route(hd, S, mode), L.last_route()
+    assert L.last_route() == A.fwd_route(dtype, hd, S, mode), L.last_route()
 
     def unlay(t, width):
         t = t.float().cpu()
@@ -122,8 +106,7 @@ def run_case(ops, dtype, hd, nseq, S, H, mode, time_major, tag):
                      d_virt=torch.zeros(H, dtype=torch.float32).cuda())
     dqkv, dbias = ops.attention_bwd(d2, q2, out, lse, nseq, S, H, scale=scale, **lay, **kw,
                                     want_dense_dbias=(mode == "dense"), **extra)
-    if bf:
-        assert L.last_route() == default_bwd_route(hd, S, mode), L.last_route()
+    assert L.last_route() == A.bwd_route(dtype, hd, S, mode), L.last_route()
     gtol = dict(atol=0.06, rtol=5e-2) if bf else dict(atol=5e-4, rtol=1e-3)
     print(f"[{tag} hd{hd} {mode} S={S}] dqkv |err| {float((unlay(dqkv, 3 * D) - qr.grad).abs().max()):.3e} on {L.last_route()}")
     torch.testing.assert_close(unlay(dqkv, 3 * D), qr.grad, **gtol)
@@ -153,12 +136,12 @@ def test_attention_wide_heads_bf16(ops, hd, nseq, S, H, mode, time_major):
 
 def test_cases_reach_every_route_and_boundary():
     for hd in WIDTHS:
-        got = {(mode, default_bwd_route(hd, S, mode)) for _, S, _, mode, _ in CASES}
+        got = {(mode, A.bwd_route(BF, hd, S, mode)) for _, S, _, mode, _ in CASES}
         want = {("none", "v2"), ("none", "v3"), ("mask", "v2"), ("mask", "v3"), ("struct", "v1"), ("struct", "v2"), ("struct", "v3"),
                 ("dense", "v1")} | ({("dense", "long")} if hd == 128 else set())
         assert got == want, (hd, got ^ want)
         # every route the rule can return, over the whole domain
-        every = {default_bwd_route(hd, S, mode, p, q) for S in range(1, 273) for mode in ("none", "mask", "dense", "struct")
+        every = {A.bwd_route(BF, hd, S, mode, p, q) for S in range(1, 273) for mode in ("none", "mask", "dense", "struct")
                  for p in (0.0, 0.1) for q in (0, 9)}
         assert every == {r for _, r in want}
     sizes = {S for _, S, _, _, _ in CASES}
@@ -371,7 +354,7 @@ def test_wide_heads_equal_zero_padded_head_dim_64(ops, hd, S, mode, p, bwd, forc
     gw, _ = ops.attention_bwd(dw, qw, ow, lw, nseq, S, H, **kw, **extraw)
     rw = L.last_route()
     g64, _ = ops.attention_bwd(d64, q64, o64, l64, nseq, S, H, **kw, **extra64)
-    assert rw == L.last_route() == (bwd or default_bwd_route(hd, S, mode, p)), (rw, L.last_route())
+    assert rw == L.last_route() == (bwd or A.bwd_route(BF, hd, S, mode, p)), (rw, L.last_route())
     tol = dict(rtol=2.0 ** -8, atol=1e-5)
     torch.testing.assert_close(ow.float().view(-1, H, hd)[..., :64], o64.float().view(-1, H, 64), **tol)
     fin = torch.isfinite(l64)

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from multimodaldiscussiontransformer_amd import _lib as L
+from tests import attention_reference as A
 from tests import gemm_reference as GR
 
 pytestmark = pytest.mark.gpu
@@ -851,12 +852,6 @@ def test_node_ce_matches_torch_cpu_half(ops, n, near_tie):
 
 
 # ----------------------------------------------------------------------------- ragged attention
-def _family(S):
-    """The backward kernel the v3 family picks for rows of up to S tokens without a structural bias (attn_bwd_route)."""
-    n_t = (S + 15) // 16
-    return "v3" if n_t > 13 else "v5" if n_t > 8 else "v4" if n_t > 6 else "v4x"
-
-
 @pytest.mark.parametrize("dtype,bwd", [(torch.float32, None), (torch.bfloat16, None), (torch.bfloat16, "v1"), (torch.bfloat16, "v2")])
 @pytest.mark.parametrize("Smax,H", [(40, 2), (104, 3), (201, 2)])
 def test_attention_ragged_sequences_equal_masked_padding(ops, dtype, bwd, Smax, H, monkeypatch):
@@ -888,7 +883,7 @@ def test_attention_ragged_sequences_equal_masked_padding(ops, dtype, bwd, Smax, 
                                 key_mask=dev(km), drop_p=p, drop_seed=seed)
     out_r, lse_r = ops.attention_fwd(dev(qkv_r), nseq, Smax, H, seq_offsets=dev(off), drop_p=p, drop_seed=seed)
     dq_r, _ = ops.attention_bwd(dev(dout_r), dev(qkv_r), out_r, lse_r, nseq, Smax, H, seq_offsets=dev(off), drop_p=p, drop_seed=seed)
-    assert L.last_route() == (bwd or ("v1" if dtype == torch.float32 else _family(Smax))), L.last_route()
+    assert L.last_route() == A.bwd_route(dtype, hd, Smax, "none", p, forced=bwd), L.last_route()
     tol = dict(atol=1e-5, rtol=1e-5) if dtype == torch.float32 else dict(atol=2e-2, rtol=2e-2)
     out_p, dq_p = out_p.view(nseq, Smax, D).float().cpu(), dq_p.view(nseq, Smax, 3 * D).float().cpu()
     for s_, n in enumerate(lens):
@@ -942,7 +937,7 @@ def test_attention_backward_never_reads_what_forward_did_not_write(ops, route, S
         dq, _ = ops.attention_bwd(dout, qkv, out_p, lse_p, nseq, Smax, H, **kw)
         monkeypatch.setattr(torch, "empty_like", real_empty_like)
         # v1 / v2 never take q_limit: the family's default kernel runs instead
-        assert L.last_route() == (route if route == "v3" or (route and not qlim) else _family(Smax)), L.last_route()
+        assert L.last_route() == A.bwd_route(bf, hd, Smax, "none", p, qlim, forced=route), L.last_route()
         assert bool(torch.isfinite(dq.float()).all()), poison
         res.append(dq)
     for r in res[1:]:
@@ -1020,7 +1015,7 @@ def test_attention_backward_one_pass_equals_two_pass(ops, S, ragged, qlim, p, mo
     finally:
         monkeypatch.delenv("MDT_ATTN_BWD")
         L.reload_env()
-    assert _family(S) == one_pass
+    assert A.bwd_route(torch.bfloat16, hd, S, "none", cap=S) == one_pass      # a length bin of cap S takes the family as it is
     assert torch.isfinite(grads[1]).all()
     scale = grads[0].abs().max().item()
     assert (grads[0] - grads[1]).abs().max().item() <= 8e-3 * max(scale, 1.0)
