@@ -44,6 +44,12 @@ mdt_row_scatter_add_f32: table[t] += Σ src rows with idx = t, fp32 atomics in a
 terms plus the starting value taken in any order, γ_{n+1} (|start| + Σ |terms|) (_sum_err of the LayerNorm reference),
 0 where all of them sit on one power-of-two granule g with (|start| + Σ |terms|) / g < 2^24 — every partial sum in every
 order is then an fp32 number and the bits are determined.  A table row nothing is added to keeps its bits.
+
+Engine-level references (tests/test_engine_embeddings_gpu.py).  reference_type_split: the two-row token-type gradient of
+engine._type_emb_grad, two any-order column sums (all rows; the rows weighted by their type) and the row_axpby rule above for
+row 1 = one + old and row 0 = (tot - one) + old.  reference_patch_embed: mdt_vit_patch_embed, the fp64 value of the projection,
+bias and position add on the stored operands before its ONE rounding; δ = γ_K |A| |B| for the accumulation in any order plus one
+rounding of a partial sum for each of the two adds, in either order.
 """
 from __future__ import annotations
 
@@ -149,6 +155,51 @@ def reference_embed(out0, word, pos, typ, ids, types, pos_ids, out_rows):
     v, d = reference_embed_sum(word, pos, typ, ids.view(-1), types.view(-1), pos_ids.view(-1))
     V[out_rows], DL[out_rows], EX[out_rows] = v, d, d == 0
     return V, DL, EX
+
+
+def reference_type_split(table0, types, src):
+    """The two-row token-type table after engine._type_emb_grad on the rows ``src`` (``types`` 0 / 1 per row): two fp32 column
+    sums in any order, tot = Σ src and one = Σ types src (the products by 0 / 1 are exact; the zero terms are added too), then
+    row 1 = one + table[1] (one add) and row 0 = (tot - one) + table[0] (the row_axpby rule: 1 tot is the first term, the add
+    of -1 one rounds, the add of the old value rounds)."""
+    V, DL, EX = _whole(table0)
+    assert table0.shape[0] == 2, "the token-type split is written for two types"
+    G = src.double()
+    w = types.double().view(-1, 1)
+    assert G.shape[0] == w.shape[0] and bool(((w == 0) | (w == 1)).all())
+    zero = torch.zeros_like(G)
+    tot, d_tot = G.sum(0), _sum_err(G, zero, 0)
+    one, d_one = (G * w).sum(0), _sum_err(G * w, zero, 0)
+    t0 = table0.double()
+    v1 = one + t0[1]
+    V[1], DL[1] = v1, _rounded(d_one, v1, v1.abs() + d_one)
+    diff = tot - one
+    d_diff = _rounded(d_tot + d_one, diff, diff.abs() + d_tot + d_one)
+    v0 = diff + t0[0]
+    V[0], DL[0] = v0, _rounded(d_diff, v0, v0.abs() + d_diff)
+    return V, DL, DL == 0
+
+
+def reference_patch_embed(img, p, wmat, bias, cls, pos):
+    """tokens [I (np + 1), D] of mdt_vit_patch_embed: the fp64 value of Conv2d + bias + position (and [CLS] + position) on the
+    stored operands (pixels rounded to the weight's type, as the A loader rounds them) before its ONE rounding to T.  δ: the
+    K-term fp32 accumulation in any order, γ_K (|A| |B|), and the two adds (bias, position) in either order, each rounding a
+    partial sum of magnitude at most |A| |B| + |bias| + |pos| (+ what it carries); the [CLS] row is one add of stored values."""
+    I, C, HW, _ = img.shape
+    T = wmat.dtype
+    gw = HW // p
+    npatch, K, D = gw * gw, C * p * p, wmat.shape[0]
+    cols = reference_patchify(torch.zeros(I * npatch, K, dtype=T), img, p)[0]
+    W, b, P = wmat.double().view(D, K), bias.double().view(1, D), pos.double().view(npatch + 1, D)
+    S = cols.abs() @ W.abs().t()
+    g = LR._gamma(K)
+    body = P[1:].repeat(I, 1)
+    v = cols @ W.t() + b + body
+    d = g * S + 2.0 * U32 * (1.0 + g) * (S + b.abs() + body.abs())
+    vc, dc = _one_add(cls.double().view(1, D), P[:1], T)
+    v = torch.cat([vc.expand(I, 1, D), v.view(I, npatch, D)], 1).reshape(I * (npatch + 1), D)
+    d = torch.cat([dc.expand(I, 1, D), d.view(I, npatch, D)], 1).reshape(I * (npatch + 1), D)
+    return v, d, d == 0
 
 
 def reference_patchify(cols0, img, p):
@@ -409,6 +460,34 @@ def embed_operands(M, L, D, dtype, seed, device="cpu"):
     ids = torch.randint(0, V, (M, L), generator=g, dtype=torch.int32).to(device)
     types = torch.randint(0, 2, (M, L), generator=g, dtype=torch.int32).to(device)
     return word, pos, typ, ids, types
+
+
+TEXT_V, TEXT_P, TEXT_M, TEXT_L = 97, 40, 9, 24
+TEXT_LENS = (24, 1, 24, 17, 24, 9, 24, 24, 24)        # 171 valid tokens of the 216 padded rows
+
+
+def text_case(seed=77):
+    """The token layout of the engine's embedding suites (tests/test_engine_embeddings_gpu.py and its CPU companion): a padded
+    [M, L] id matrix whose padding is id 0, and the ragged view of its valid tokens (their flat rows m L + l and pos_ids l).
+    Id 0 sits on 130 of the valid tokens as well (the ragged form still has a segment of more than two 64-row chunks and a
+    heavily contended table row; 175 rows in the padded form), ids 1..12 occur exactly once, the other 29 valid tokens draw
+    from ids 13..59 and the table rows 60..96 are never referenced; token type 1 on the rows with r % 5 in (1, 3)."""
+    M, L = TEXT_M, TEXT_L
+    g = torch.Generator().manual_seed(seed)
+    lens = torch.tensor(TEXT_LENS)
+    l = torch.arange(L)[None].expand(M, L)
+    valid = (l < lens[:, None]).reshape(-1)
+    rows = torch.nonzero(valid).view(-1)
+    n = int(rows.numel())
+    perm = rows[torch.randperm(n, generator=g)]
+    ids = torch.zeros(M * L, dtype=torch.int64)
+    ids[perm[130:142]] = torch.arange(1, 13)
+    ids[perm[142:]] = torch.randint(13, 60, (n - 142,), generator=g)
+    r = torch.arange(M * L)
+    types = ((r % 5 == 1) | (r % 5 == 3)).long()
+    return dict(M=M, L=L, ids=ids.view(M, L).to(torch.int32), types=types.view(M, L).to(torch.int32), rows=rows,
+                pos_padded=(r % L).to(torch.int32), ids_rows=ids[rows].to(torch.int32), types_rows=types[rows].to(torch.int32),
+                pos_rows=(rows % L).to(torch.int32))
 
 
 def embed_rows(M, L, seq_stride, off, device="cpu"):
