@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from . import geometry as G
 
 
 def pack_structure(parents: List[np.ndarray], spatial_pos_max: int, nmax: Optional[int] = None, updown=None):
@@ -75,9 +76,9 @@ class PackedBatch:
     n_labels: int = 0
     extras: dict = field(default_factory=dict)
     ragged: Optional["RaggedText"] = None      # valid-token packing (built on the host by pack_batch; lazily otherwise)
-    host: Optional[dict] = None                # pack_batch only: numpy copies of what the encoder's index vectors are derived from
-    #                                            (token offsets, comment of every token row, node_row, img_comment, token mask),
-    #                                            so that those vectors are built on the HOST in the packer thread, not by eager kernels
+    host: Optional[dict] = None                # pack_batch only: int32 / uint8 numpy copies of what data/geometry.py derives the encoder's
+    #                                            index vectors from (token offsets, comment of every token row, node_row, img_comment,
+    #                                            token mask): those vectors are built on the HOST in the packer thread, not by eager kernels
 
     @property
     def T(self):
@@ -143,6 +144,12 @@ def ragged_text(ids: torch.Tensor, types: torch.Tensor, mask: torch.Tensor, devi
                       sorted_lens=sl.cpu().numpy().astype(np.int64))
 
 
+# what batched_data["_csr"] carries: these fields of the PackedBatch and, as "rt_" + name, of its RaggedText
+_CSR_FIELDS = ("B", "N", "M", "I", "L", "n_labels", "ids", "types", "text_mask", "node_row", "graph_row", "degree", "deg_scatter",
+               "key_pad", "img_comment", "label_rows", "targets")
+_CSR_RAGGED = ("rows", "max_len", "offsets", "ids", "types", "pos", "comment", "order", "sorted_lens")
+
+
 def pack_batch(trees: List[dict], spatial_pos_max: int = 10, device="cuda", non_blocking=True) -> PackedBatch:
     B = len(trees)
     n_nodes = [len(t["parent"]) for t in trees]
@@ -162,10 +169,6 @@ def pack_batch(trees: List[dict], spatial_pos_max: int = 10, device="cuda", non_
     ids = host((M, Lq), torch.int32)
     types = host((M, Lq), torch.int32)
     tmask = host((M, Lq), torch.uint8)
-    node_row = torch.full((B * N,), -1, dtype=torch.int32, pin_memory=pin)
-    graph_row = host((M,), torch.int32)
-    key_pad = host((B, N + 1), torch.uint8)
-    deg_scatter = torch.full((B, N + 1), -1, dtype=torch.int32, pin_memory=pin)
     img_index, images, ys, y_masks = [], [], [], []
     images_u8, u8_size = [], 224     # decoded RGB bytes at the images' own sizes (device front end, data/discussions.py)
     m = 0
@@ -174,9 +177,6 @@ def pack_batch(trees: List[dict], spatial_pos_max: int = 10, device="cuda", non_
         ii, ty, at = (torch.from_numpy(np.ascontiguousarray(t[k])) for k in ("input_ids", "token_type_ids", "attention_mask"))
         x[b, :n], tt[b, :n], am[b, :n] = ii, ty, at
         ids[m:m + n], types[m:m + n], tmask[m:m + n] = ii.int(), ty.int(), at.to(torch.uint8)
-        node_row[b * N:b * N + n] = torch.arange(m, m + n, dtype=torch.int32)
-        graph_row[m:m + n] = torch.arange(b * (N + 1) + 1, b * (N + 1) + 1 + n, dtype=torch.int32)
-        key_pad[b, n + 1:] = 1
         img_index.append(np.asarray(t["image_index"], dtype=bool))
         if t.get("images") is not None and len(t["images"]):
             images.append(t["images"])
@@ -229,8 +229,7 @@ def pack_batch(trees: List[dict], spatial_pos_max: int = 10, device="cuda", non_
         images_dev = _ops.image_preprocess(_ops.PackedImages(images_u8, u8_size, pin=pin), device=device)
 
     in_deg_t = torch.from_numpy(in_degree)
-    d32 = in_deg_t.int()
-    deg_scatter[:, 1:] = torch.where(d32 > 0, d32, torch.full_like(d32, -1))
+    csr = G.csr_view(token_mask, in_deg_t)         # host tensors: no device work
     bd = dict(
         idx=torch.arange(B, dtype=torch.int64),
         attn_bias=to(torch.from_numpy(attn_bias)),
@@ -249,29 +248,21 @@ def pack_batch(trees: List[dict], spatial_pos_max: int = 10, device="cuda", non_
     bd["out_degree"] = bd["in_degree"]            # collator.py:171 — the same tensor object
     pb = PackedBatch(
         B=B, N=N, M=M, I=int(img_comment.numel()), L=Lq, batched_data=bd,
-        ids=to(ids), types=to(types), text_mask=to(tmask), node_row=to(node_row), graph_row=to(graph_row),
-        degree=to(in_deg_t.reshape(-1).int()), deg_scatter=to(deg_scatter.view(-1)), key_pad=to(key_pad), attn_bias=bd["attn_bias"],
+        ids=to(ids), types=to(types), text_mask=to(tmask), degree=to(in_deg_t.reshape(-1).int()), attn_bias=bd["attn_bias"],
         spatial_pos=bd["spatial_pos"], img_comment=to(img_comment), images=bd["x_images"],
         label_rows=to(label_rows), targets=to(torch.from_numpy((y if node_task else y[:0]).astype(np.int32))),
-        n_labels=int(label_rows.numel()),
+        n_labels=int(label_rows.numel()), **G.place(csr, device, pin, non_blocking),
     )
     pb.ragged = ragged_text(ids, types, tmask, device=device, non_blocking=non_blocking)   # host-side: no device sync
-    lens_np = tmask.numpy().astype(np.int64).sum(1)
-    off_np = np.zeros(M + 1, dtype=np.int64)
-    np.cumsum(lens_np, out=off_np[1:])
-    pb.host = dict(offsets=off_np, comment=np.repeat(np.arange(M, dtype=np.int64), lens_np), node_row=node_row.numpy().astype(np.int64),
-                   img_comment=img_comment.numpy().astype(np.int64), text_mask=tmask.numpy(), pin=pin, non_blocking=non_blocking)
+    lens_np = tmask.numpy().sum(1, dtype=np.int32)
+    off_np = np.concatenate([np.zeros(1, np.int32), np.cumsum(lens_np, dtype=np.int32)])
+    pb.host = dict(offsets=off_np, comment=np.repeat(np.arange(M, dtype=np.int32), lens_np), node_row=csr["node_row"].numpy(),
+                   img_comment=img_comment.numpy(), text_mask=tmask.numpy(), pin=pin, non_blocking=non_blocking)
     bd["_packed"] = pb                             # lets model(**net_input) find the CSR view
     # the same view as plain tensors / ints: a sample that is moved between devices by a generic "apply to every tensor
     # of the nested dict" (FairSeq's utils.move_to_cuda) carries these along, and packed_from_batched_data rebuilds the
     # PackedBatch from them on the other side without any nonzero / host sync
-    rt = pb.ragged
-    bd["_csr"] = dict(
-        B=B, N=N, M=M, I=pb.I, L=Lq, n_labels=pb.n_labels, ids=pb.ids, types=pb.types, text_mask=pb.text_mask,
-        node_row=pb.node_row, graph_row=pb.graph_row, degree=pb.degree, deg_scatter=pb.deg_scatter, key_pad=pb.key_pad,
-        img_comment=pb.img_comment, label_rows=pb.label_rows, targets=pb.targets,
-        rt_rows=rt.rows, rt_max_len=rt.max_len, rt_offsets=rt.offsets, rt_ids=rt.ids, rt_types=rt.types, rt_pos=rt.pos,
-        rt_comment=rt.comment, rt_order=rt.order, rt_sorted_lens=rt.sorted_lens)
+    bd["_csr"] = {**{f: getattr(pb, f) for f in _CSR_FIELDS}, **{"rt_" + f: getattr(pb.ragged, f) for f in _CSR_RAGGED}}
     return pb
 
 
@@ -290,35 +281,16 @@ def packed_from_batched_data(bd: dict) -> PackedBatch:
         return bd["_packed"]
     if "_csr" in bd and bd["_csr"]["ids"].device == dev_now:
         c = bd["_csr"]
-        images = bd.get("x_images")
-        pb = PackedBatch(
-            B=c["B"], N=c["N"], M=c["M"], I=c["I"], L=c["L"], batched_data=bd, ids=c["ids"], types=c["types"],
-            text_mask=c["text_mask"], node_row=c["node_row"], graph_row=c["graph_row"], degree=c["degree"],
-            deg_scatter=c["deg_scatter"], key_pad=c["key_pad"], attn_bias=bd["attn_bias"], spatial_pos=bd["spatial_pos"],
-            img_comment=c["img_comment"], images=images, label_rows=c["label_rows"], targets=c["targets"],
-            n_labels=c["n_labels"])
-        pb.ragged = RaggedText(rows=c["rt_rows"], max_len=c["rt_max_len"], offsets=c["rt_offsets"], ids=c["rt_ids"],
-                               types=c["rt_types"], pos=c["rt_pos"], comment=c["rt_comment"], order=c.get("rt_order"),
-                               sorted_lens=c.get("rt_sorted_lens"))
+        pb = PackedBatch(batched_data=bd, attn_bias=bd["attn_bias"], spatial_pos=bd["spatial_pos"], images=bd.get("x_images"),
+                         **{f: c[f] for f in _CSR_FIELDS})
+        pb.ragged = RaggedText(**{f: c["rt_" + f] for f in _CSR_RAGGED})
         bd["_packed"] = pb
         return pb
     mask = bd["x_token_mask"]
     dev = mask.device
     B, N = mask.shape
     Lq = bd["x"].shape[2]
-    T = N + 1
-    flat = mask.reshape(-1)
-    real = torch.nonzero(flat).flatten()
-    M = int(real.numel())
-    node_row = torch.full((B * N,), -1, dtype=torch.int32, device=dev)
-    node_row[real] = torch.arange(M, dtype=torch.int32, device=dev)
-    b_of = torch.div(real, N, rounding_mode="floor")
-    graph_row = (b_of * T + 1 + (real - b_of * N)).to(torch.int32)
-    deg = bd["in_degree"].reshape(B, N).to(torch.int32)
-    deg_scatter = torch.full((B, T), -1, dtype=torch.int32, device=dev)
-    deg_scatter[:, 1:] = torch.where(deg > 0, deg, torch.full_like(deg, -1))
-    key_pad = torch.zeros(B, T, dtype=torch.uint8, device=dev)
-    key_pad[:, 1:] = (~mask).to(torch.uint8)
+    csr = G.csr_view(mask, bd["in_degree"])         # the single ``nonzero`` of the CSR view
     img_idx = bd.get("x_image_indexes")
     images = bd.get("x_images")
     img_comment = (torch.nonzero(img_idx).flatten().to(torch.int32) if images is not None
@@ -328,10 +300,10 @@ def packed_from_batched_data(bd: dict) -> PackedBatch:
                   else torch.zeros(0, dtype=torch.int32, device=dev))
     y = bd.get("y")
     pb = PackedBatch(
-        B=B, N=N, M=M, I=int(img_comment.numel()), L=Lq, batched_data=bd,
+        B=B, N=N, M=int(csr["graph_row"].numel()), I=int(img_comment.numel()), L=Lq, batched_data=bd,
         ids=bd["x"][mask].to(torch.int32).contiguous(), types=bd["x_token_type_ids"][mask].to(torch.int32).contiguous(),
-        text_mask=bd["x_attention_mask"][mask].to(torch.uint8).contiguous(), node_row=node_row, graph_row=graph_row,
-        degree=deg.reshape(-1).contiguous(), deg_scatter=deg_scatter.view(-1), key_pad=key_pad,
+        text_mask=bd["x_attention_mask"][mask].to(torch.uint8).contiguous(), **csr,
+        degree=bd["in_degree"].reshape(-1).to(torch.int32).contiguous(),
         attn_bias=bd["attn_bias"].float().contiguous(), spatial_pos=bd["spatial_pos"].to(torch.int32).contiguous(),
         img_comment=img_comment, images=None if images is None else images.float().contiguous(),
         label_rows=label_rows, targets=(y.flatten().to(torch.int32) if y is not None else label_rows),

@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from .. import engine as E
 from .. import ops
+from ..data import geometry as G
 
 
 def init_params(module, n_layers):
@@ -48,16 +49,9 @@ class GraphNodeFeature(nn.Module):
         ind = in_degree.to(torch.int32).contiguous().view(-1)
         outd = ind if out_degree is in_degree else out_degree.to(torch.int32).contiguous().view(-1)
         rows = torch.arange(n_graph * n_node, dtype=torch.int32, device=dev)
-
-        def scatter_idx(d):
-            idx = torch.full((n_graph, T), -1, dtype=torch.int32, device=dev)
-            d2 = d.view(n_graph, n_node)
-            idx[:, 1:] = torch.where(d2 > 0, d2, torch.full_like(d2, -1))
-            return idx.view(-1)
-
-        graph_rows = (torch.arange(n_graph, device=dev)[:, None] * T + 1 + torch.arange(n_node, device=dev)[None]).to(torch.int32).view(-1)
-        in_idx = scatter_idx(ind)
-        out_idx = in_idx if outd is ind else scatter_idx(outd)
+        graph_rows = G.graph_rows(n_graph, n_node, dev)
+        in_idx = G.degree_scatter(ind.view(n_graph, n_node)).view(-1)
+        out_idx = in_idx if outd is ind else G.degree_scatter(outd.view(n_graph, n_node)).view(-1)
 
         def run(tape, xv):
             return (E.graph_node_features(tape, xv, rows, ind, outd, self.in_degree_encoder.weight,

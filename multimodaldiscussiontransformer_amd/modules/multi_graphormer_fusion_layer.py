@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from .. import engine as E
+from ..data import geometry as G
 from ._fused import BertLayer, ViTLayer
 
 
@@ -93,9 +94,8 @@ class GraphFusionLayer(nn.Module):
             # positions of the image comments WITHOUT torch.nonzero (its output size is data-dependent: a D2H sync): I is known
             # from the ViT tensor, and a stable sort of the negated mask lists the True positions first, in order
             img = torch.sort((~x_image_indexes.bool()).to(torch.uint8), stable=True).indices[:I]
-            j = torch.arange(nb, device=dev)
-            img_text_rows = (img[:, None] * St + j[None]).to(torch.int32).reshape(-1).contiguous()
-            vit_rows = (torch.arange(I, device=dev)[:, None] * Sv + j[None]).to(torch.int32).reshape(-1).contiguous()
+            img_text_rows = G.bottleneck_rows((img * St).to(torch.int32), nb)
+            vit_rows = G.bottleneck_rows(torch.arange(I, dtype=torch.int32, device=dev) * Sv, nb)
         else:
             img_text_rows = vit_rows = None
         inputs = [bert_hidden_states.contiguous().view(M * Lq, D), bottle_neck.contiguous().view(M * nb, D)]

@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import engine as E
+from ..data import geometry as G
 from ..data.packer import get_ragged, PackedBatch, packed_from_batched_data
 from ._fused import BertModel, ViTModel
 from .graphormer_graph_encoder_layer import GraphEncoderStack, GraphormerGraphEncoderLayer  # noqa: F401
@@ -184,7 +185,7 @@ class MultiGraphormerGraphEncoder(nn.Module):
 
     # ------------------------------------------------------------------ index helpers
     def _indices(self, pb: PackedBatch):
-        """Row geometry of the text side, as index vectors, for the two layouts the tape can run in:
+        """Row geometry of the text side, as index vectors (data/geometry.py text_rows), for the two layouts the tape can run in:
         padded (every comment owns nb + L rows, attention masks the padding — bit-for-bit the reference, including
         the hidden states of padded positions) and ragged (``ragged_tokens``, default: only valid tokens own rows;
         logits and gradients are unchanged, see data/packer.py RaggedText)."""
@@ -193,99 +194,32 @@ class MultiGraphormerGraphEncoder(nn.Module):
         key = ("enc_idx", nb, ragged)
         if key in pb.extras:
             return pb.extras[key]
-        dev = pb.ids.device
-        M, Lq = pb.M, pb.L
-        np_ = (self.vit_config["image_size"] // self.vit_config["patch"]) ** 2
-        Sv = nb + np_ + 1
-        if pb.host is not None:
-            idx = self._indices_host(pb, nb, ragged, np_, Sv)
-            pb.extras[key] = idx
-            return idx
-        i32 = dict(device=dev, dtype=torch.int32)
-        j = torch.arange(nb, **i32)
-        m_ar = torch.arange(M, **i32)
+        rt = get_ragged(pb) if ragged else None
+        feed, place = self._row_feed(pb, rt)
+        Sv = nb + (self.vit_config["image_size"] // self.vit_config["patch"]) ** 2 + 1
+        ix = G.text_rows(nb, pb.M, pb.L, pb.I, Sv, ragged=ragged, max_len=rt.max_len if ragged else 0, **feed)
+        # what the batch already holds on the device is handed on as it is, not uploaded a second time
+        ix["spec_pre"].update(dict(seq_offsets=rt.offsets) if ragged else dict(key_mask=pb.text_mask))
+        ix = place(ix)
         if ragged:
-            rt = get_ragged(pb)
-            off_pre = rt.offsets                                   # [M+1]
-            off_fus = (off_pre + torch.arange(M + 1, **i32) * nb).contiguous()
-            bn0 = off_fus[:M].contiguous()
-            pre2fus = (torch.arange(rt.rows, **i32) + (rt.comment + 1) * nb).contiguous()
-            rows_pre, rows_fus = rt.rows, rt.rows + M * nb
-            S_pre, S_fus = rt.max_len, rt.max_len + nb
             # comments of at most 64 rows (four key tiles) run the small attention kernels in a launch of their own
-            spec_pre = dict(S=S_pre, seq_offsets=off_pre, bins=rt.length_bins(0) if self.length_bins else None)
-            spec_fus = dict(S=S_fus, seq_offsets=off_fus, bins=rt.length_bins(nb) if self.length_bins else None)
-        else:
-            St = nb + Lq
-            bn0 = (m_ar * St).contiguous()
-            r = torch.arange(M * Lq, **i32)
-            pre2fus = (torch.div(r, Lq, rounding_mode="floor") * St + nb + r % Lq).contiguous()
-            rows_pre, rows_fus = M * Lq, M * St
-            ones = torch.ones(M, nb, dtype=torch.uint8, device=dev)
-            spec_pre = dict(S=Lq, key_mask=pb.text_mask)
-            spec_fus = dict(S=St, key_mask=torch.cat([ones, pb.text_mask], dim=1).contiguous())
-        idx = dict(
-            ragged=ragged, Sv=Sv, P=np_ + 1, rows_pre=rows_pre, rows_fus=rows_fus, spec_pre=spec_pre, spec_fus=spec_fus,
-            pre2fus=pre2fus, bn0_rows=bn0, cls_rows=(bn0 + nb).contiguous(),
-            bn_rows_all=(bn0[:, None] + j[None]).reshape(-1).contiguous(),
-            text_row_of_node=torch.where(pb.node_row >= 0, bn0[pb.node_row.clamp(min=0).long()], pb.node_row).contiguous(),
-            img_text_bn_rows=(bn0[pb.img_comment.long()][:, None] + j[None]).reshape(-1).contiguous(),
-            vit_bn_rows=(torch.arange(pb.I, **i32)[:, None] * Sv + j[None]).reshape(-1).contiguous(),
-        )
-        pb.extras[key] = idx
-        return idx
+            ix["spec_pre"]["bins"] = rt.length_bins(0) if self.length_bins else None
+            ix["spec_fus"]["bins"] = rt.length_bins(nb) if self.length_bins else None
+        pb.extras[key] = ix
+        return ix
 
-    def _indices_host(self, pb: PackedBatch, nb: int, ragged: bool, np_: int, Sv: int):
-        """The same vectors as the device arithmetic of ``_indices``, computed with numpy from the packer's host copies and
-        uploaded (pinned, non-blocking, on whatever stream is current — the prefetch thread's copy stream): a batch from
-        ``pack_batch`` costs the step no eager index kernels at all."""
-        import numpy as np
-        h = pb.host
-        dev = pb.ids.device
-        M, Lq, I = pb.M, pb.L, pb.I
-        pin = bool(h["pin"]) and dev.type == "cuda"
-
-        def up(a):
-            t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
-            if pin:
-                t = t.pin_memory()
-            return t.to(dev, non_blocking=bool(h["non_blocking"]))
-
-        j = np.arange(nb, dtype=np.int64)
-        m_ar = np.arange(M, dtype=np.int64)
-        if ragged:
-            rt = get_ragged(pb)
-            off_pre = h["offsets"]
-            off_fus = off_pre + np.arange(M + 1, dtype=np.int64) * nb
-            bn0 = off_fus[:M]
-            pre2fus = np.arange(rt.rows, dtype=np.int64) + (h["comment"] + 1) * nb
-            rows_pre, rows_fus = rt.rows, rt.rows + M * nb
-            S_pre, S_fus = rt.max_len, rt.max_len + nb
-            spec_pre = dict(S=S_pre, seq_offsets=rt.offsets, bins=rt.length_bins(0) if self.length_bins else None)
-            spec_fus = dict(S=S_fus, seq_offsets=up(off_fus), bins=rt.length_bins(nb) if self.length_bins else None)
-        else:
-            St = nb + Lq
-            bn0 = m_ar * St
-            r = np.arange(M * Lq, dtype=np.int64)
-            pre2fus = (r // Lq) * St + nb + r % Lq
-            rows_pre, rows_fus = M * Lq, M * St
-            km = np.concatenate([np.ones((M, nb), dtype=np.uint8), h["text_mask"].reshape(M, Lq).astype(np.uint8)], axis=1)
-            kmt = torch.from_numpy(np.ascontiguousarray(km))
-            if pin:
-                kmt = kmt.pin_memory()
-            spec_pre = dict(S=Lq, key_mask=pb.text_mask)
-            spec_fus = dict(S=St, key_mask=kmt.to(dev, non_blocking=bool(h["non_blocking"])))
-        node_row = h["node_row"]
-        bn0_dev = up(bn0)
-        return dict(
-            ragged=ragged, Sv=Sv, P=np_ + 1, rows_pre=rows_pre, rows_fus=rows_fus, spec_pre=spec_pre, spec_fus=spec_fus,
-            pre2fus=up(pre2fus), bn0_rows=bn0_dev, cls_rows=up(bn0 + nb),
-            bn_rows_all=up((bn0[:, None] + j[None]).reshape(-1)),
-            text_row_of_node=up(np.where(node_row >= 0, bn0[np.clip(node_row, 0, None)] if M else node_row, node_row)),
-            img_text_bn_rows=up((bn0[h["img_comment"]][:, None] + j[None]).reshape(-1)),
-            vit_bn_rows=up((np.arange(I, dtype=np.int64)[:, None] * Sv + j[None]).reshape(-1)),
-            _host=dict(bn0=bn0, up=up),
-        )
+    @staticmethod
+    def _row_feed(pb: PackedBatch, rt):
+        """→ (the tensors data/geometry.py derives the index vectors from, place).  A batch from ``pack_batch`` feeds the
+        packer's host arrays and ``place`` uploads the results: it costs the step no eager index kernel at all.  Any other
+        batch feeds its device tensors (``rt``: its valid-token packing, None in the padded layout)."""
+        dev, h = pb.ids.device, pb.host
+        if h is not None:
+            feed = {k: torch.from_numpy(h[k]) for k in ("offsets", "comment", "node_row", "img_comment", "text_mask")}
+            return feed, lambda x: G.place(x, dev, bool(h["pin"]) and dev.type == "cuda", bool(h["non_blocking"]))
+        feed = dict(offsets=rt and rt.offsets, comment=rt and rt.comment, node_row=pb.node_row, img_comment=pb.img_comment,
+                    text_mask=pb.text_mask)
+        return feed, lambda x: G.place(x, dev)
 
     # ------------------------------------------------------------------ tape-level forward
     def _fwd(self, tape, pb: PackedBatch, prune_last: bool = False):
@@ -420,25 +354,13 @@ class MultiGraphormerGraphEncoder(nn.Module):
             raise ValueError(f"{pb.L} text tokens per comment exceed the BERT position table ({max_pos})")
 
     def _prune_indices(self, pb: PackedBatch, ix):
-        key = ("prune_idx", self.num_bottle_neck, bool(self.ragged_tokens))
-        if key not in pb.extras and "_host" in ix:
-            import numpy as np
-            hb, up = ix["_host"]["bn0"], ix["_host"]["up"]
-            m2 = np.arange(pb.M, dtype=np.int64) * 2
-            prune = dict(text_keep=up(np.stack([hb, hb + self.num_bottle_neck], axis=1).reshape(-1)),
-                         vit_keep=up(np.arange(pb.I, dtype=np.int64) * ix["Sv"]),
-                         img_bn0_compact=up(pb.host["img_comment"] * 2))
-            pb.extras[key] = (prune, dict(bn0_rows=up(m2), cls_rows=up(m2 + 1)))
+        """→ (``prune`` of GraphFusionLayer._fwd, bn0_rows / cls_rows in its compact output), from the feed of ``_indices``."""
+        nb, ragged = self.num_bottle_neck, ix["ragged"]
+        key = ("prune_idx", nb, ragged)
         if key not in pb.extras:
-            dev = pb.ids.device
-            i32 = dict(device=dev, dtype=torch.int32)
-            m_ar = torch.arange(pb.M, **i32)
-            text_keep = torch.stack([ix["bn0_rows"], ix["cls_rows"]], dim=1).reshape(-1).contiguous()     # 2m, 2m+1
-            prune = dict(text_keep=text_keep,
-                         vit_keep=(torch.arange(pb.I, **i32) * ix["Sv"]).contiguous(),
-                         img_bn0_compact=(pb.img_comment * 2).contiguous())
-            rows = dict(bn0_rows=(m_ar * 2).contiguous(), cls_rows=(m_ar * 2 + 1).contiguous())
-            pb.extras[key] = (prune, rows)
+            feed, place = self._row_feed(pb, get_ragged(pb) if ragged else None)
+            bn0 = G.first_rows(nb, pb.M, pb.L, feed["offsets"] if ragged else None, feed["node_row"].device)[:pb.M]
+            pb.extras[key] = place(G.prune_rows(nb, pb.M, pb.I, ix["Sv"], bn0, feed["img_comment"]))
         return pb.extras[key]
 
     def live_parameters(self):

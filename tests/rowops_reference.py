@@ -50,6 +50,9 @@ engine._type_emb_grad, two any-order column sums (all rows; the rows weighted by
 row 1 = one + old and row 0 = (tot - one) + old.  reference_patch_embed: mdt_vit_patch_embed, the fp64 value of the projection,
 bias and position add on the stored operands before its ONE rounding; δ = γ_K |A| |B| for the accumulation in any order plus one
 rounding of a partial sum for each of the two adds, in either order.
+
+Row geometry (tests/test_rowops_reference_cpu.py).  reference_text_rows / reference_prune_rows: the encoder's index vectors as
+plain loops over the comments, tokens and images of the host trees, with no formula taken from data/geometry.py.
 """
 from __future__ import annotations
 
@@ -525,3 +528,94 @@ def scatter_operands(n, D, dtype, seed, granule, device="cpu", s_stride=2, s_off
     idx = torch.randint(0, table_rows, (n,), generator=g, dtype=torch.int32)
     idx[torch.arange(n) % 7 == 3] = -1                            # skipped rows
     return table0, idx.to(device), src
+
+
+# ------------------------------------------------------------------------------------------------ row geometry of a batch
+def _i32(v):
+    return torch.tensor(v, dtype=torch.int32).reshape(-1)
+
+
+def batch_layout(trees):
+    """What the loop references below read, taken from the host trees themselves with plain loops: ``mask`` (per comment, its
+    attention mask as a list of 0 / 1), ``node_comment`` (per padded node (b, n), its comment number or -1) and
+    ``img_comment`` (the comments that carry an image, in order)."""
+    N = max(len(t["parent"]) for t in trees)
+    mask, node_comment, img_comment = [], [], []
+    for t in trees:
+        n = len(t["parent"])
+        for k in range(N):
+            if k < n:
+                node_comment.append(len(mask))
+                if bool(t["image_index"][k]):
+                    img_comment.append(len(mask))
+                mask.append([int(v != 0) for v in t["attention_mask"][k]])
+            else:
+                node_comment.append(-1)
+    return mask, node_comment, img_comment
+
+
+def _first_rows(nb, mask, ragged):
+    """(first fused row of every comment, token count of every comment in this layout, rows of the fused buffer): comment m
+    starts where the running sum of nb + tokens stands."""
+    first, ntok, row = [], [], 0
+    for mk in mask:
+        first.append(row)
+        ntok.append(sum(mk) if ragged else len(mk))
+        row += nb + ntok[-1]
+    return first, ntok, row
+
+
+def _reference_bins(ntok, extra, cap=64):
+    """RaggedText.length_bins with its default cap: the comments of at most ``cap - extra`` tokens, shortest first, and the
+    rest, each with the key length it runs at; None unless both bins exist."""
+    top = max(ntok) + extra
+    order = sorted(range(len(ntok)), key=lambda m: ntok[m])           # stable: ties keep the comment order
+    short = [m for m in order if ntok[m] + extra <= cap]
+    rest = [m for m in order if ntok[m] + extra > cap]
+    if cap >= top or not short or not rest:
+        return None
+    return [(_i32(short), cap), (_i32(rest), top)]
+
+
+def reference_text_rows(nb, Sv, mask, node_comment, img_comment, ragged, length_bins=True):
+    """The index vectors of MultiGraphormerGraphEncoder._indices, row by row: comment m starts at the running sum of
+    nb + tokens; bottleneck token k sits at first + k, [CLS] at first + nb, token t at first + nb + t (ragged: t counts the
+    valid tokens; padded: every position owns a row); image i owns Sv rows from i Sv, bottleneck tokens first."""
+    M, L = len(mask), len(mask[0])
+    first, ntok, rows_fus = _first_rows(nb, mask, ragged)
+    pre2fus, bn_all, off_pre = [], [], [0]
+    for m in range(M):
+        for k in range(nb):
+            bn_all.append(first[m] + k)
+        for t in range(ntok[m]):
+            pre2fus.append(first[m] + nb + t)
+        off_pre.append(off_pre[-1] + ntok[m])
+    img_text, vit = [], []
+    for i, c in enumerate(img_comment):
+        for k in range(nb):
+            img_text.append(first[c] + k)
+            vit.append(i * Sv + k)
+    if ragged:
+        spec_pre = dict(S=max(ntok), seq_offsets=_i32(off_pre), bins=_reference_bins(ntok, 0) if length_bins else None)
+        spec_fus = dict(S=max(ntok) + nb, seq_offsets=_i32(first + [rows_fus]), bins=_reference_bins(ntok, nb) if length_bins else None)
+    else:
+        spec_pre = dict(S=L, key_mask=torch.tensor(mask, dtype=torch.uint8))
+        spec_fus = dict(S=nb + L, key_mask=torch.tensor([[1] * nb + mk for mk in mask], dtype=torch.uint8))
+    return dict(ragged=ragged, Sv=Sv, P=Sv - nb, rows_pre=len(pre2fus), rows_fus=rows_fus, spec_pre=spec_pre, spec_fus=spec_fus,
+                pre2fus=_i32(pre2fus), bn0_rows=_i32(first), cls_rows=_i32([f + nb for f in first]), bn_rows_all=_i32(bn_all),
+                text_row_of_node=_i32([first[c] if c >= 0 else -1 for c in node_comment]), img_text_bn_rows=_i32(img_text),
+                vit_bn_rows=_i32(vit))
+
+
+def reference_prune_rows(nb, Sv, mask, img_comment, ragged):
+    """(prune, rows) of MultiGraphormerGraphEncoder._prune_indices: the last fusion layer keeps bottleneck token 0 and [CLS]
+    of every comment and bottleneck token 0 (row i Sv) of every image; comment m lands on rows 2m and 2m + 1 of its output."""
+    first, _, _ = _first_rows(nb, mask, ragged)
+    keep, bn0, cls = [], [], []
+    for m, f in enumerate(first):
+        keep += [f, f + nb]
+        bn0.append(2 * m)
+        cls.append(2 * m + 1)
+    prune = dict(text_keep=_i32(keep), vit_keep=_i32([i * Sv for i in range(len(img_comment))]),
+                 img_bn0_compact=_i32([2 * c for c in img_comment]))
+    return prune, dict(bn0_rows=_i32(bn0), cls_rows=_i32(cls))

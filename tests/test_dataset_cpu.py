@@ -74,8 +74,9 @@ def test_user_data_dir_dataset_to_batches(tmp_path):
     # the compatibility path (a dict straight from ``collator``, no CSR view) derives the same indices
     bare = {k: v for k, v in moved.items() if k != "_csr"}
     pb2 = packed_from_batched_data(bare)
-    for f in ("ids", "node_row", "graph_row", "deg_scatter", "key_pad", "img_comment", "label_rows"):
-        assert torch.equal(getattr(pb2, f), getattr(pb0, f)), f
+    for f in ("ids", "types", "text_mask", "node_row", "graph_row", "degree", "deg_scatter", "key_pad", "img_comment", "label_rows", "targets"):
+        assert torch.equal(getattr(pb2, f), getattr(pb0, f)) and getattr(pb2, f).dtype == getattr(pb0, f).dtype, f
+    assert (pb2.B, pb2.N, pb2.M, pb2.I, pb2.L, pb2.n_labels) == (pb0.B, pb0.N, pb0.M, pb0.I, pb0.L, pb0.n_labels)
     sys.path.remove(str(tmp_path)) if str(tmp_path) in sys.path else None
 
 

@@ -4,8 +4,10 @@ contracts every add that follows a product into one FMA) is accepted at every (d
 (tests/test_rowops_gpu.py), and each listed mutant of it, a subtly wrong kernel, is rejected at the same shapes.  The
 emulation decodes rows with // and % on its own; the reference is the only judge.
 
-The last test is about the engine, not the kernels: mdt_row_axpby(accumulate) is a plain read-modify-write, correct only
-while no destination row appears twice, and the index vectors the encoder builds are checked for exactly that."""
+The last two tests are about the engine, not the kernels: mdt_row_axpby(accumulate) is a plain read-modify-write, correct
+only while no destination row appears twice, and the index vectors the encoder builds are checked for exactly that; then
+the vectors themselves (data/geometry.py, fed from the host and from the batch's tensors) against the plain loops of
+rowops_reference.reference_text_rows / reference_prune_rows."""
 import numpy as np
 import pytest
 import torch
@@ -447,3 +449,123 @@ def test_destination_index_vectors_never_repeat_a_row(kind, ragged, host):
     _no_repeat("dense_rows", dense_rows, M * pb.L, "scatter_rows forward: row_axpby(out, n, di=d_idx)")
     if ragged:
         assert dense_rows.numel() == ix["pre2fus"].numel() == rt.rows
+
+
+# ------------------------------------------------------------------------------------------------ row geometry against loops
+GEOMETRY_KINDS = ("A", "B", "M", "no_image", "all_images", "single", "one_token")
+
+
+def _geometry_case(kind):
+    """(hyper-parameters, host trees): the batches of oracle/cases.py and one batch each without any image, with an image on
+    every comment, of a single one-comment tree, and of one-token texts (two of them with an image)."""
+    from multimodaldiscussiontransformer_amd import synthetic
+    from oracle import cases
+    if kind in ("A", "B"):
+        hp = cases.tiny_hparams(kind)
+        return hp, cases.tiny_trees(kind, hp)
+    if kind == "M":
+        hp = cases.real_hparams(kind)
+        return hp, cases.real_trees(kind, hp)
+    hp = cases.tiny_hparams("A")
+    spec = dict(no_image=((5, 0.0, "bushy"), (3, 0.0, "deep"), (6, 0.0, "bushy")), all_images=((4, 1.0, "bushy"), (3, 1.0, "deep")),
+                single=((1, 0.0, "bushy"),), one_token=((4, 0.5, "bushy"), (2, 0.0, "deep")))[kind]
+    rng = np.random.Generator(np.random.PCG64(4242))
+    trees = [synthetic.make_tree(n, rng, seq_len=16, vocab_size=hp.vocab_size, image_frac=f, image_size=hp.image_size, shape=s,
+                                 min_len=3) for n, f, s in spec]
+    if kind == "one_token":
+        for t in trees:
+            t["attention_mask"][:, 1:] = 0
+            t["input_ids"] *= t["attention_mask"]
+    return hp, trees
+
+
+def _same(got, want, path):
+    """Equal key by key: tensors by value, dtype, shape and both contiguous; scalars by value and type."""
+    if torch.is_tensor(got) or torch.is_tensor(want):
+        assert torch.is_tensor(got) and torch.is_tensor(want), path
+        assert got.dtype == want.dtype and got.shape == want.shape and torch.equal(got, want), f"{path}: {got} != {want}"
+        assert got.is_contiguous() and want.is_contiguous(), f"{path} is not contiguous"
+    elif isinstance(want, dict):
+        assert isinstance(got, dict) and list(sorted(got)) == list(sorted(want)), f"{path}: keys {sorted(got)} != {sorted(want)}"
+        for k in want:
+            _same(got[k], want[k], f"{path}.{k}")
+    elif isinstance(want, (list, tuple)):
+        assert isinstance(got, (list, tuple)) and len(got) == len(want), path
+        for i, (g, w) in enumerate(zip(got, want)):
+            _same(g, w, f"{path}[{i}]")
+    else:
+        assert type(got) is type(want) and got == want, f"{path}: {got!r} != {want!r}"
+
+
+def _geometry_mutant(name, ix, prune, nb):
+    """A subtly wrong builder: the faithful result with one vector derived by a wrong rule."""
+    ix, prune = dict(ix), dict(prune)
+    I = prune["vit_keep"].numel()
+    if name == "cls_off_by_one":
+        ix["cls_rows"] = ix["cls_rows"] + 1
+    elif name == "pre2fus_without_nb":
+        ix["pre2fus"] = ix["pre2fus"] - nb
+    elif name == "img_rows_in_node_order":                        # the first I comments instead of the image comments
+        ix["img_text_bn_rows"] = ix["bn_rows_all"][:I * nb].clone()
+    elif name == "vit_keep_stride_P":
+        prune["vit_keep"] = torch.arange(I, dtype=torch.int32) * ix["P"]
+    else:
+        raise KeyError(name)
+    return ix, prune
+
+
+GEOMETRY_MUTANTS = ("cls_off_by_one", "pre2fus_without_nb", "img_rows_in_node_order", "vit_keep_stride_P")
+
+
+@pytest.fixture(scope="module")
+def geometry_encoder():
+    from multimodaldiscussiontransformer_amd.models import GraphormerModel
+    from tests.util_model import model_args
+    made = {}
+
+    def get(hp):
+        key = repr(sorted(vars(hp).items()))
+        if key not in made:
+            made[key] = GraphormerModel.build_model(model_args(hp), task=None).encoder.graph_encoder
+        return made[key]
+    return get
+
+
+@pytest.mark.parametrize("ragged", (False, True), ids=["padded", "ragged"])
+@pytest.mark.parametrize("kind", GEOMETRY_KINDS)
+def test_index_vectors_equal_the_loop_reference_from_both_feeds(kind, ragged, geometry_encoder):
+    """_indices and _prune_indices fed with the packer's host arrays, fed with the batch's tensors (``pb.host = None``) and
+    the plain loops of rowops_reference over the host trees give the same vectors: equal values, dtypes and scalars, all
+    contiguous.  On batch A and M (three and four images on scattered comments) four wrong rules are rejected by the same
+    comparison."""
+    from multimodaldiscussiontransformer_amd.data.packer import pack_batch
+    hp, trees = _geometry_case(kind)
+    ge = geometry_encoder(hp)
+    ge.ragged_tokens = ragged
+    nb = ge.num_bottle_neck
+    mask, node_comment, img_comment = RR.batch_layout(trees)
+    Sv = nb + (hp.image_size // hp.patch) ** 2 + 1
+    want = RR.reference_text_rows(nb, Sv, mask, node_comment, img_comment, ragged, length_bins=ge.length_bins)
+    want_prune = RR.reference_prune_rows(nb, Sv, mask, img_comment, ragged)
+    got = {}
+    for feed in ("host", "device"):
+        pb = pack_batch(trees, 5, device="cpu")
+        assert pb.host is not None
+        if feed == "device":
+            pb.host = None
+        ix = ge._indices(pb)
+        assert ix["ragged"] == ragged and ge._indices(pb) is ix
+        pr = ge._prune_indices(pb, ix)
+        assert isinstance(pr, tuple) and len(pr) == 2 and ge._prune_indices(pb, ix) is pr
+        _same(ix, want, f"{feed}-fed _indices")
+        _same(pr, want_prune, f"{feed}-fed _prune_indices")
+        got[feed] = (ix, pr)
+    _same(got["host"], got["device"], "host-fed against device-fed")
+    assert (pb.M, pb.I) == (len(mask), len(img_comment))
+    if kind in ("A", "M"):
+        assert img_comment != list(range(len(img_comment))) and len(img_comment) > 1
+        for name in GEOMETRY_MUTANTS:
+            bad_ix, bad_prune = _geometry_mutant(name, got["host"][0], got["host"][1][0], nb)
+            with pytest.raises(AssertionError):
+                _same(bad_ix, want, name)
+                _same((bad_prune, got["host"][1][1]), want_prune, name)
