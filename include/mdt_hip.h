@@ -435,6 +435,40 @@ int mdt_adam_step_multi_guarded(void* stream, int dtype, int n_tensors, const md
                                 const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2,
                                 float eps, float weight_decay, int step, const mdt_adam_guard* guard);
 
+/* The weight average (FairSeq --store-ema) riding on the Adam step: the four entry points above with an fp32 average per tensor.
+ * After the element's new value p is final — the value stored to `master`, or to `param` where master is NULL — the kernel does
+ *        e = ema[i];  e = d * e + (1.0f - d) * p;  ema[i] = e;          d = ema_decay, `1.0f - d` ONE fp32 subtraction in the kernel
+ * two fp32 products and one fp32 sum (the build does not contract them; a bound should allow either FMA as well).  ema_decay
+ * must lie in [0, 1].  ema_decay == 0 stores p itself: ema == p bit for bit, for every p (FairSeq's "copy until
+ * --ema-start-update").  param, master, m and v come out with exactly the bits of the entry point without `_ema` on the same
+ * inputs.  A skipped update (guard->skip) stores nothing: the average keeps its bits too.  The averages need 4-byte alignment only.
+ * Single tensor: `ema` is float[n], not NULL.  Table form: `ema_dev` is a DEVICE array of n_tensors pointers parallel to the
+ * table (mdt_adam_tensor keeps its layout); a NULL entry: that tensor has no average and gets the plain arithmetic. */
+int mdt_adam_step_ema(void* stream, int dtype, int64_t n, void* param, float* master, const float* grad, float* m,
+                      float* v, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                      const float* grad_scale, float* ema, float ema_decay);
+int mdt_adam_step_multi_ema(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
+                            const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2,
+                            float eps, float weight_decay, int step, const float* grad_scale, float* const* ema_dev,
+                            float ema_decay);
+int mdt_adam_step_ema_guarded(void* stream, int dtype, int64_t n, void* param, float* master, const float* grad, float* m,
+                              float* v, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                              const mdt_adam_guard* guard, float* ema, float ema_decay);
+int mdt_adam_step_multi_ema_guarded(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
+                                    const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2,
+                                    float eps, float weight_decay, int step, const mdt_adam_guard* guard, float* const* ema_dev,
+                                    float ema_decay);
+/* Evaluate with the averaged weights: ONE launch over the same table and the same ema_dev swaps the average into the working
+ * parameters (restore = 0) and the raw weights back (restore = 1).
+ *   tensor with a master:   restore = 0: param = T(ema)         restore = 1: param = T(master) — the bits it had, as the Adam
+ *                           step keeps param == T(master)
+ *   fp32 tensor without:    param[i] and ema[i] trade contents; restore = 1 trades them back (the exchange is its own inverse)
+ * master, grad, m and v are never touched (grad, m, v of the table are not even read); a NULL entry of ema_dev leaves the tensor
+ * alone, and so does a bf16 tensor without a master (there is nowhere to keep its raw bits).  4-byte alignment suffices;
+ * 16-byte aligned tensors move 16 bytes at a time.  No atomics. */
+int mdt_ema_swap_multi(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev, float* const* ema_dev,
+                       const int64_t* chunk_first_dev, int64_t total_chunks, int restore);
+
 /* ------------------------------------------------------------------ ordered (bit-reproducible) gradient reductions
  * The backward pass accumulates gradients with fp32 atomics (MDT_EPI_ATOMIC / _ASUM / _COLSUM, mdt_colsum, mdt_layernorm_bwd,
  * mdt_row_scatter_add_f32, the structural-bias gradient of mdt_attention_bwd): two runs of one step agree to ~1e-7, not bit for

@@ -108,6 +108,11 @@ _SIGS = {
     "mdt_grad_norm_finalize": ([_vp, _vp, _i64, _f, _vp, _f, _f, _f, _i, _i, _vp], _i),
     "mdt_adam_step_guarded": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp], _i),
     "mdt_adam_step_multi_guarded": ([_vp, _i, _i, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp], _i),
+    "mdt_adam_step_ema": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp, _vp, _f], _i),
+    "mdt_adam_step_multi_ema": ([_vp, _i, _i, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp, _vp, _f], _i),
+    "mdt_adam_step_ema_guarded": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp, _vp, _f], _i),
+    "mdt_adam_step_multi_ema_guarded": ([_vp, _i, _i, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp, _vp, _f], _i),
+    "mdt_ema_swap_multi": ([_vp, _i, _i, _vp, _vp, _vp, _i64, _i], _i),
     "mdt_resize_plan_ksize": ([_i, _i], _i),
     "mdt_resize_plan": ([_i, _i, _vp, _vp, _i], _i),
     "mdt_image_norm_lut": ([C.c_double, _vp, _vp, _vp], _i),

@@ -14,7 +14,8 @@ dict —
     criterion            None (the criteria have no parameters)
     optimizer_history    [{"criterion_name", "optimizer_name", "lr_scheduler_state", "num_updates"}]
     task_state           {}
-    extra_state          {"metrics", "previous_training_time", "train_iterator": {"epoch", ...}}
+    extra_state          {"metrics", "previous_training_time", "train_iterator": {"epoch", ...}}; with --store-ema also "ema": the
+                         averaged weights as an fp32 state dict under the model's keys (FusedAdam.ema_state_dict)
     last_optimizer_state torch-optimizer state dict of Adam: {"state": {i: {"step", "exp_avg", "exp_avg_sq"}},
                          "param_groups": [{"lr", "betas", "eps", "weight_decay", "params": [0 .. T-1]}]}  — numbered over
                          the TRAINABLE parameters in ``model.parameters()`` order, as torch numbers them (frozen ones are
@@ -224,6 +225,7 @@ def load_checkpoint(path: str, model, *, optimizer=None, reset_optimizer: bool =
         if not reset_lr_scheduler:
             out["lr_scheduler_state"] = dict(hist[-1].get("lr_scheduler_state") or {})
     extra = state.get("extra_state") or {}
+    out["ema"] = extra.get("ema")     # FairSeq --store-ema: the averaged weights (model state: kept whatever is reset); None: not stored
     if not reset_meters:
         out["extra_state"] = extra
     if not reset_dataloader:      # FairSeq ties the iterator state (epoch AND position inside it) to --reset-dataloader alone

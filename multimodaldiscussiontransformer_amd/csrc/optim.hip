@@ -26,12 +26,26 @@ __device__ __forceinline__ bool adam_scale_and_step(const float* __restrict__ gr
   return true;
 }
 
-template <typename T, bool GUARD>
+// The weight average of the `_ema` entry points (FairSeq --store-ema).  EMA = false: an empty argument, the plain kernels —
+// the same instantiations as before the average existed.  EMA = true: after p is final, e = d * e + (1.0f - d) * p on the fp32
+// average, p being the value stored to the master (to the parameter where there is none); d == 0 stores p itself, so the
+// copy is exact for every p.  A skipped update returns before anything is read: the average keeps its bits too.
+template <bool EMA> struct EmaOne {};
+template <> struct EmaOne<true> { float* ema; float decay; };
+template <bool EMA> struct EmaTable {};
+template <> struct EmaTable<true> { float* const* ema; float decay; };     // one pointer per table entry, NULL: no average
+
+__device__ __forceinline__ void ema_update(float* __restrict__ ema, int64_t i, float d, float p) {
+  const float e = d * ema[i] + (1.0f - d) * p;
+  ema[i] = d == 0.0f ? p : e;
+}
+
+template <typename T, bool GUARD, bool EMA>
 __global__ __launch_bounds__(256) void adam_kernel(int64_t n, T* __restrict__ param, float* __restrict__ master,
                                                    const float* __restrict__ grad, float* __restrict__ m,
                                                    float* __restrict__ v, float lr, float beta1, float beta2, float eps,
                                                    float wd, float step_size, const float* __restrict__ grad_scale,
-                                                   const mdt_adam_guard* __restrict__ guard) {
+                                                   const mdt_adam_guard* __restrict__ guard, EmaOne<EMA> ea) {
   float gs;
   if (!adam_scale_and_step<GUARD>(grad_scale, guard, gs, step_size)) return;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -44,7 +58,9 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, T* __restrict__ pa
     m[i] = mi;
     v[i] = vi;
     if (master) master[i] = p;
-    param[i] = from_f32<T>(p);
+    const T stored = from_f32<T>(p);
+    param[i] = stored;
+    if constexpr (EMA) ema_update(ea.ema, i, ea.decay, master ? p : to_f32(stored));
   }
 }
 
@@ -61,12 +77,12 @@ __device__ __forceinline__ int tensor_of_chunk(const int64_t* __restrict__ chunk
 // Multi-tensor form: one launch walks a device table of tensors (the ~400 parameter tensors of mDT would otherwise
 // cost ~400 launches of 10-20 us each).  Block b works on chunk b of 4096 elements; `chunk_first[t]` is the first
 // chunk of tensor t (monotone, chunk_first[n] = total), found by binary search.
-template <typename T, bool GUARD>
+template <typename T, bool GUARD, bool EMA>
 __global__ __launch_bounds__(256) void adam_multi_kernel(int n_tensors, const mdt_adam_tensor* __restrict__ tab,
                                                          const int64_t* __restrict__ chunk_first, float lr, float beta1,
                                                          float beta2, float eps, float wd, float step_size,
                                                          const float* __restrict__ grad_scale,
-                                                         const mdt_adam_guard* __restrict__ guard) {
+                                                         const mdt_adam_guard* __restrict__ guard, EmaTable<EMA> ea) {
   float gs;
   if (!adam_scale_and_step<GUARD>(grad_scale, guard, gs, step_size)) return;
   const int64_t total = chunk_first[n_tensors];
@@ -75,6 +91,8 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(int n_tensors, const md
     const mdt_adam_tensor t = tab[lo];
     const int64_t base = (chunk - chunk_first[lo]) * 4096;
     T* param = (T*)t.param;
+    float* ema = nullptr;
+    if constexpr (EMA) ema = ea.ema[lo];
 #pragma unroll 4
     for (int k = 0; k < 16; ++k) {
       const int64_t i = base + k * 256 + threadIdx.x;
@@ -88,7 +106,68 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(int n_tensors, const md
       t.m[i] = mi;
       t.v[i] = vi;
       if (t.master) t.master[i] = p;
-      param[i] = from_f32<T>(p);
+      const T stored = from_f32<T>(p);
+      param[i] = stored;
+      if constexpr (EMA) {
+        if (ema) ema_update(ema, i, ea.decay, t.master ? p : to_f32(stored));
+      }
+    }
+  }
+}
+
+// The swap of mdt_ema_swap_multi: one block per 4096-element chunk of the same table.  A tensor with a master: param = T(ema)
+// (restore: T(master)) — the master is the keeper of the raw weights, nothing else is written.  An fp32 tensor without one:
+// param and ema trade contents (restore trades them back).  Thread t owns the 16-byte group (k * 256 + t) of the chunk's
+// parameter elements: one vector load / store each where param and the fp32 source start on 16-byte boundaries and the group
+// lies inside the tensor, element by element, same ownership and order, elsewhere.
+template <typename T>
+__global__ __launch_bounds__(256) void ema_swap_multi_kernel(int n_tensors, const mdt_adam_tensor* __restrict__ tab,
+                                                             float* const* __restrict__ ema_tab,
+                                                             const int64_t* __restrict__ chunk_first, int restore) {
+  constexpr int N = Vec<T>::N;
+  const int64_t total = chunk_first[n_tensors];
+  for (int64_t chunk = blockIdx.x; chunk < total; chunk += gridDim.x) {
+    const int lo = tensor_of_chunk(chunk_first, n_tensors, chunk);
+    float* ema = ema_tab[lo];
+    if (!ema) continue;
+    const mdt_adam_tensor t = tab[lo];
+    const int64_t base = (chunk - chunk_first[lo]) * 4096;
+    T* param = (T*)t.param + base;
+    const int64_t left = t.numel - base;
+    if (t.master) {
+      const float* src = (restore ? t.master : ema) + base;
+      const bool vec = (((uintptr_t)param | (uintptr_t)src) & 15) == 0;
+      for (int j = threadIdx.x * N; j < 4096; j += 256 * N) {
+        if (j >= left) break;
+        if (vec && j + N <= left) {
+          Vec<T> o;
+#pragma unroll
+          for (int q = 0; q < N; q += 4) {
+            const f32x4 x = *(const f32x4*)(src + j + q);
+            o.set(q, x[0]); o.set(q + 1, x[1]); o.set(q + 2, x[2]); o.set(q + 3, x[3]);
+          }
+          *(Vec<T>*)(param + j) = o;
+        } else {
+          for (int q = 0; q < N && j + q < left; ++q) param[j + q] = from_f32<T>(src[j + q]);
+        }
+      }
+    } else if constexpr (std::is_same<T, float>::value) {
+      float* e = ema + base;
+      const bool vec = (((uintptr_t)param | (uintptr_t)e) & 15) == 0;
+      for (int j = threadIdx.x * 4; j < 4096; j += 1024) {
+        if (j >= left) break;
+        if (vec && j + 4 <= left) {
+          const f32x4 a = *(const f32x4*)(param + j), b = *(const f32x4*)(e + j);
+          *(f32x4*)(param + j) = b;
+          *(f32x4*)(e + j) = a;
+        } else {
+          for (int q = 0; q < 4 && j + q < left; ++q) {
+            const float a = param[j + q], b = e[j + q];
+            param[j + q] = b;
+            e[j + q] = a;
+          }
+        }
+      }
     }
   }
 }
@@ -202,35 +281,38 @@ static float adam_step_size(float lr, float beta1, float beta2, int step) {
   return (float)(lr * sqrt(bc2) / bc1);
 }
 
-template <bool GUARD>
+template <bool GUARD, bool EMA = false>
 static int adam_step_multi(const char* what, void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
                            const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2, float eps,
-                           float weight_decay, int step, const float* grad_scale, const mdt_adam_guard* guard) {
+                           float weight_decay, int step, const float* grad_scale, const mdt_adam_guard* guard,
+                           EmaTable<EMA> ea = {}) {
   if (n_tensors == 0 || total_chunks == 0) return MDT_OK;
   MDT_CHECK_ARG(table_dev && chunk_first_dev && step >= 1 && (!GUARD || guard), "%s: bad arguments", what);
+  if constexpr (EMA) MDT_CHECK_ARG(ea.ema && ea.decay >= 0.0f && ea.decay <= 1.0f, "%s: ema_dev is NULL or ema_decay is outside [0, 1]", what);
   const float step_size = adam_step_size(lr, beta1, beta2, step);
   const unsigned grid = (unsigned)(total_chunks > 65536 ? 65536 : total_chunks);
   hipStream_t st = (hipStream_t)stream;
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return launch_plain<adam_multi_kernel<T, GUARD>>(what, grid, 256, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay, step_size,
-                                                     grad_scale, guard);
+    return launch_plain<adam_multi_kernel<T, GUARD, EMA>>(what, grid, 256, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay,
+                                                          step_size, grad_scale, guard, ea);
   });
 }
 
-template <bool GUARD>
+template <bool GUARD, bool EMA = false>
 static int adam_step_one(const char* what, void* stream, int dtype, int64_t n, void* param, float* master, const float* grad,
                          float* m, float* v, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                         const float* grad_scale, const mdt_adam_guard* guard) {
+                         const float* grad_scale, const mdt_adam_guard* guard, EmaOne<EMA> ea = {}) {
   if (n == 0) return MDT_OK;
   MDT_CHECK_ARG(param && grad && m && v && step >= 1 && (!GUARD || guard), "%s: bad arguments", what);
+  if constexpr (EMA) MDT_CHECK_ARG(ea.ema && ea.decay >= 0.0f && ea.decay <= 1.0f, "%s: ema is NULL or ema_decay is outside [0, 1]", what);
   const float step_size = adam_step_size(lr, beta1, beta2, step);
   const unsigned grid = (unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return launch_plain<adam_kernel<T, GUARD>>(what, grid, 256, st, n, (T*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step_size, grad_scale,
-                                               guard);
+    return launch_plain<adam_kernel<T, GUARD, EMA>>(what, grid, 256, st, n, (T*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step_size,
+                                                    grad_scale, guard, ea);
   });
 }
 
@@ -260,6 +342,48 @@ extern "C" int mdt_adam_step_guarded(void* stream, int dtype, int64_t n, void* p
                                      const mdt_adam_guard* guard) {
   return adam_step_one<true>("adam_step_guarded", stream, dtype, n, param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay,
                              step, nullptr, guard);
+}
+
+// The `_ema` forms: the same launches with the weight average riding on them (include/mdt_hip.h).
+extern "C" int mdt_adam_step_multi_ema(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
+                                       const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2,
+                                       float eps, float weight_decay, int step, const float* grad_scale, float* const* ema_dev,
+                                       float ema_decay) {
+  return adam_step_multi<false, true>("adam_step_multi_ema", stream, dtype, n_tensors, table_dev, chunk_first_dev, total_chunks, lr,
+                                      beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, {ema_dev, ema_decay});
+}
+
+extern "C" int mdt_adam_step_ema(void* stream, int dtype, int64_t n, void* param, float* master, const float* grad, float* m,
+                                 float* v, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                 const float* grad_scale, float* ema, float ema_decay) {
+  return adam_step_one<false, true>("adam_step_ema", stream, dtype, n, param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay,
+                                    step, grad_scale, nullptr, {ema, ema_decay});
+}
+
+extern "C" int mdt_adam_step_multi_ema_guarded(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
+                                               const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1,
+                                               float beta2, float eps, float weight_decay, int step, const mdt_adam_guard* guard,
+                                               float* const* ema_dev, float ema_decay) {
+  return adam_step_multi<true, true>("adam_step_multi_ema_guarded", stream, dtype, n_tensors, table_dev, chunk_first_dev, total_chunks,
+                                     lr, beta1, beta2, eps, weight_decay, step, nullptr, guard, {ema_dev, ema_decay});
+}
+
+extern "C" int mdt_adam_step_ema_guarded(void* stream, int dtype, int64_t n, void* param, float* master, const float* grad,
+                                         float* m, float* v, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                         int step, const mdt_adam_guard* guard, float* ema, float ema_decay) {
+  return adam_step_one<true, true>("adam_step_ema_guarded", stream, dtype, n, param, master, grad, m, v, lr, beta1, beta2, eps,
+                                   weight_decay, step, nullptr, guard, {ema, ema_decay});
+}
+
+extern "C" int mdt_ema_swap_multi(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev, float* const* ema_dev,
+                                  const int64_t* chunk_first_dev, int64_t total_chunks, int restore) {
+  if (n_tensors == 0 || total_chunks == 0) return MDT_OK;
+  MDT_CHECK_ARG(table_dev && ema_dev && chunk_first_dev && (restore == 0 || restore == 1), "ema_swap_multi: bad arguments");
+  const unsigned grid = (unsigned)(total_chunks > 65536 ? 65536 : total_chunks);
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_plain<ema_swap_multi_kernel<T>>("ema_swap_multi", grid, 256, (hipStream_t)stream, n_tensors, table_dev, ema_dev, chunk_first_dev, restore);
+  });
 }
 
 extern "C" int mdt_grad_sumsq_multi(void* stream, int n_tensors, const mdt_adam_tensor* table_dev, const int64_t* chunk_first_dev,

@@ -6,8 +6,14 @@ working-precision parameter in a single pass.
 ``clip_norm`` (FairSeq ``--clip-norm``) adds the global gradient norm on the device: one deterministic read of the
 gradients (no atomics), a one-block finaliser that writes the guard state — gnorm, the effective gradient scale, the
 skip flag of a non-finite update, running counters — and Adam kernels that read their scale from it.  Nothing of it
-synchronises with the host."""
+synchronises with the host.
+
+``ema_decay`` (FairSeq ``--store-ema``) keeps an fp32 exponential moving average of the weights in one flat arena.  The
+average is updated by the Adam launch itself (the ``_ema`` entry points: the fresh fp32 value is in a register, a skipped
+update leaves the average alone); ``ema_weights()`` swaps it into the working parameters for an evaluation and back."""
 from __future__ import annotations
+
+import contextlib
 
 import torch
 
@@ -15,9 +21,15 @@ from ._lib import check, dt, lib, ptr, stream
 
 
 class FusedAdam:
-    def __init__(self, params, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, multi_tensor=True, clip_norm=None):
+    def __init__(self, params, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, multi_tensor=True, clip_norm=None,
+                 ema_decay=None, ema_start_update=0, ema_update_freq=1):
         """``clip_norm=None``: no norm pass, the unguarded kernels.  A number (0 included): the guarded path — gnorm is
-        measured, a non-finite update is skipped, and gradients are clipped to that norm when it is > 0."""
+        measured, a non-finite update is skipped, and gradients are clipped to that norm when it is > 0.
+
+        ``ema_decay=None``: no average, nothing allocated, the launches of a plain optimiser.  A number in [0, 1]: update
+        ``k`` (``num_updates`` of ``step``, by default the count of ``step`` calls) with ``k % ema_update_freq == 0`` also
+        does ``ema = d ema + (1 - d) p`` in the Adam kernel, d = 0 while ``k < ema_start_update`` (FairSeq: the average is
+        a copy of the weights until then) and ``ema_decay`` afterwards; every other update is the plain launch."""
         self.params = [p for p in params if p.requires_grad]
         self.clip_norm = None if clip_norm is None else float(clip_norm)
         self.norm_launches = 0                    # sum-of-squares and finaliser launches issued so far (tests)
@@ -32,6 +44,28 @@ class FusedAdam:
             if p.dtype != torch.float32:
                 st["master"] = p.detach().float().clone()
             self.state[id(p)] = st
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_start_update, self.ema_update_freq = int(ema_start_update), int(ema_update_freq)
+        self.ema_arena = None
+        self._ema_ptrs, self._swap_tab, self._in_ema = {}, None, False
+        if self.ema_decay is not None:
+            if not 0.0 <= self.ema_decay <= 1.0 or self.ema_update_freq < 1:
+                raise ValueError(f"FusedAdam: ema_decay {ema_decay!r} must lie in [0, 1] and ema_update_freq {ema_update_freq!r} be >= 1")
+            # one flat fp32 arena, a slot per parameter on a 16-byte boundary, seeded from the master (or the fp32 parameter)
+            offs, n = [], 0
+            for p in self.params:
+                offs.append(n)
+                n += (p.numel() + 3) // 4 * 4
+            self.ema_arena = torch.zeros(max(n, 1), dtype=torch.float32, device=self.params[0].device if self.params else "cpu")
+            for p, off in zip(self.params, offs):
+                st = self.state[id(p)]
+                st["ema"] = self.ema_arena[off:off + p.numel()].view(p.shape)
+                st["ema"].copy_(st["master"] if "master" in st else p.detach().float())
+
+    def _ema_pointers(self, ps):
+        import numpy as np
+        a = np.asarray([self.state[id(p)]["ema"].data_ptr() for p in ps], dtype=np.int64)
+        return torch.from_numpy(a).to(ps[0].device)
 
     def _tables(self):
         """Device tables for the one-launch update, built once: parameters of one dtype whose gradients live in the
@@ -59,6 +93,8 @@ class FusedAdam:
             dev = ps[0].device
             tab[dtype] = (torch.from_numpy(rec).to(dev), torch.from_numpy(first).to(dev), len(ps), int(first[-1]),
                           {id(p) for p in ps}, ps, [p.main_grad.data_ptr() for p in ps])
+            if self.ema_decay is not None:
+                self._ema_ptrs[dtype] = self._ema_pointers(ps)      # parallel to the table: mdt_adam_step_multi_ema's ema_dev
         self._tab = tab
         return tab
 
@@ -127,11 +163,19 @@ class FusedAdam:
         self._guard_fresh = False
         return guard
 
-    def step(self, lr=None, grad_scale: torch.Tensor = None):
+    def step(self, lr=None, grad_scale: torch.Tensor = None, num_updates: int = None):
         """Gradients are read from ``p.main_grad`` (fp32 arena) or ``p.grad``; ``grad_scale`` is an optional
-        fp32 device scalar multiplied into every gradient.  Never synchronises with the host."""
+        fp32 device scalar multiplied into every gradient.  Never synchronises with the host.  ``num_updates``: the
+        trainer's count including this update, which the EMA schedule follows (default: the count of ``step`` calls)."""
+        if self._in_ema:
+            raise RuntimeError("FusedAdam.step() inside ema_weights(): the parameters hold the averaged weights")
         self.step_count += 1
         lr = self.lr if lr is None else lr
+        ema = None                                # None: the plain launches; a number: the decay of this update's _ema launches
+        if self.ema_decay is not None:
+            k = self.step_count if num_updates is None else int(num_updates)
+            if k % self.ema_update_freq == 0:
+                ema = 0.0 if k < self.ema_start_update else self.ema_decay
         done = set()
         # main_grad views move when the DDP arena is re-laid-out after the first step: rebuild the tables then
         if getattr(self, "_tab", None) is not None and any(
@@ -145,11 +189,21 @@ class FusedAdam:
         for dtype, (rec, first, n, total, ids, _, _) in tables.items():
             head = (stream(), 0 if dtype == torch.float32 else 1, n, ptr(rec), ptr(first), total, float(lr), float(self.betas[0]),
                     float(self.betas[1]), float(self.eps), float(self.weight_decay), self.step_count)
-            if guard is None:
+            if ema is not None:
+                tail = (ptr(self._ema_ptrs[dtype]), ema)
+                if guard is None:
+                    check(lib.mdt_adam_step_multi_ema(*head, ptr(grad_scale), *tail), "mdt_adam_step_multi_ema")
+                else:
+                    check(lib.mdt_adam_step_multi_ema_guarded(*head, ptr(guard), *tail), "mdt_adam_step_multi_ema_guarded")
+            elif guard is None:
                 check(lib.mdt_adam_step_multi(*head, ptr(grad_scale)), "mdt_adam_step_multi")
             else:
                 check(lib.mdt_adam_step_multi_guarded(*head, ptr(guard)), "mdt_adam_step_multi_guarded")
-        self._step_rest(lr, grad_scale, rest, guard)
+        self._step_rest(lr, grad_scale, rest, guard, ema)
+        self._weights_moved()
+
+    @staticmethod
+    def _weights_moved():
         from . import fp8
         if fp8.ACTIVE is not None:
             fp8.ACTIVE.optimizer_stepped()      # the cached 8-bit weight copies are stale now
@@ -170,15 +224,115 @@ class FusedAdam:
                     g = g.float()
             yield p, g.contiguous()
 
-    def _step_rest(self, lr, grad_scale, rest, guard=None):
+    def _step_rest(self, lr, grad_scale, rest, guard=None, ema=None):
         for p, g in rest:
             st = self.state[id(p)]
             head = (stream(), dt(p), p.numel(), ptr(p.data), ptr(st.get("master")), ptr(g), ptr(st["m"]), ptr(st["v"]), float(lr),
                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.step_count)
-            if guard is None:
+            if ema is not None:
+                if guard is None:
+                    check(lib.mdt_adam_step_ema(*head, ptr(grad_scale), ptr(st["ema"]), ema), "mdt_adam_step_ema")
+                else:
+                    check(lib.mdt_adam_step_ema_guarded(*head, ptr(guard), ptr(st["ema"]), ema), "mdt_adam_step_ema_guarded")
+            elif guard is None:
                 check(lib.mdt_adam_step(*head, ptr(grad_scale)), "mdt_adam_step")
             else:
                 check(lib.mdt_adam_step_guarded(*head, ptr(guard)), "mdt_adam_step_guarded")
+
+    # -- the weight average (FairSeq --store-ema)
+    def _need_ema(self):
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdam(ema_decay=None) keeps no weight average: construct it with ema_decay=<decay>")
+
+    def _ema_entries(self, model):
+        """(state-dict key, fp32 view into the EMA arena) of every state-dict entry of ``model`` that is a trainable
+        parameter of this optimiser or a row slice of one (the fused q/k/v parameter is saved as its three parts, as
+        checkpoint.py saves the weights)."""
+        spans = []
+        for p in self.params:
+            beg = p.data.data_ptr()
+            spans.append((beg, beg + p.numel() * p.element_size(), p))
+        for k, v in model.state_dict().items():
+            for beg, end, p in spans:
+                if beg <= v.data_ptr() < end and v.dtype == p.dtype:
+                    off = (v.data_ptr() - beg) // p.element_size()
+                    yield k, self.state[id(p)]["ema"].view(-1)[off:off + v.numel()].view(v.shape)
+                    break
+
+    def ema_state_dict(self, model):
+        """The averaged weights as fp32 CPU tensors under ``model``'s state-dict keys (trainable entries only)."""
+        self._need_ema()
+        from collections import OrderedDict
+        return OrderedDict((k, e.detach().cpu().clone()) for k, e in self._ema_entries(model))
+
+    def load_ema_state_dict(self, model, sd):
+        """Inverse of ``ema_state_dict``: every trainable entry must be there with its shape (a missing key raises, as a
+        strict model load does); entries of ``sd`` that are no trainable entry of the model raise as unexpected."""
+        self._need_ema()
+        if self._in_ema:
+            raise RuntimeError("FusedAdam.load_ema_state_dict() inside ema_weights()")
+        want = dict(self._ema_entries(model))
+        missing = [k for k in want if k not in sd]
+        unexpected = [k for k in sd if k not in want]
+        if missing or unexpected:
+            raise RuntimeError(f"EMA state dict: missing keys {missing[:8]}{'...' if len(missing) > 8 else ''}, "
+                               f"unexpected keys {unexpected[:8]}")
+        for k, e in want.items():
+            if tuple(sd[k].shape) != tuple(e.shape):
+                raise ValueError(f"EMA state dict: shape of {k} is {tuple(sd[k].shape)}, the model expects {tuple(e.shape)}")
+            e.copy_(sd[k])
+
+    def seed_ema_from_weights(self):
+        """The average restarts as a copy of the current weights (the masters where there are any)."""
+        self._need_ema()
+        for p in self.params:
+            st = self.state[id(p)]
+            st["ema"].copy_(st["master"] if "master" in st else p.detach().float())
+
+    def _swap_tables(self):
+        """Tables of the swap launch: EVERY parameter of the optimiser by dtype (the step's tables leave out what has no
+        ``main_grad``), rebuilt when a parameter's storage moved."""
+        import numpy as np
+        now = [p.data.data_ptr() for p in self.params]
+        if self._swap_tab is not None and self._swap_tab[0] == now:
+            return self._swap_tab[1]
+        groups = {}
+        for p in self.params:
+            if not p.data.is_contiguous():
+                raise RuntimeError("FusedAdam.ema_weights(): a parameter is not contiguous")
+            groups.setdefault(p.dtype, []).append(p)
+        tabs = []
+        for dtype, ps in groups.items():
+            rec = np.zeros((len(ps), 6), dtype=np.int64)
+            first = np.zeros(len(ps) + 1, dtype=np.int64)
+            for i, p in enumerate(ps):
+                st = self.state[id(p)]
+                rec[i] = (p.data.data_ptr(), st["master"].data_ptr() if "master" in st else 0, 0, st["m"].data_ptr(), st["v"].data_ptr(), p.numel())
+                first[i + 1] = first[i] + (p.numel() + 4095) // 4096
+            dev = ps[0].device
+            tabs.append((dt(ps[0]), len(ps), torch.from_numpy(rec).to(dev), self._ema_pointers(ps), torch.from_numpy(first).to(dev), int(first[-1])))
+        self._swap_tab = (now, tabs)
+        return tabs
+
+    def _swap(self, restore):
+        for d, n, rec, eptr, first, total in self._swap_tables():
+            check(lib.mdt_ema_swap_multi(stream(), d, n, ptr(rec), ptr(eptr), ptr(first), total, int(restore)), "mdt_ema_swap_multi")
+        self._weights_moved()                    # both ends: the cached weight copies (fp8, padded, transposed) are stale
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """The working parameters hold the averaged weights inside the context (one swap launch per dtype at each end) and
+        their own bits after it.  No ``step()`` and no nesting inside."""
+        self._need_ema()
+        if self._in_ema:
+            raise RuntimeError("FusedAdam.ema_weights() does not nest")
+        self._swap(0)
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self._in_ema = False
+            self._swap(1)
 
 
 class PolynomialDecayLR:

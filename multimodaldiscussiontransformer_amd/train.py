@@ -64,6 +64,18 @@ def build_parser():
     p.add_argument("--deterministic", action="store_true", default=False,
                    help="not a reference flag: ordered gradient reductions instead of fp32 atomics (engine.set_deterministic) — loss, "
                         "gradients and parameters are bit-for-bit reproducible in one process on one GPU; bf16 / fp32 only, not with --fp8")
+    # FairSeq's EMA flags (fairseq/dataclass/configs.py EMAConfig); defaults are filled in main() so that a flag given without
+    # --store-ema can be told from one left alone
+    p.add_argument("--store-ema", action="store_true", default=False,
+                   help="keep an fp32 exponential moving average of the trainable weights (updated inside the fused Adam launch) and "
+                        "store it in checkpoints as extra_state['ema']")
+    p.add_argument("--ema-decay", type=float, default=None, help="FairSeq's default: 0.9999")
+    p.add_argument("--ema-start-update", type=int, default=None, help="the average is a copy of the weights before this update (default 0)")
+    p.add_argument("--ema-update-freq", type=int, default=None, help="update the average every N updates (default 1)")
+    p.add_argument("--ema-fp32", action="store_true", default=None, help="accepted: the average here is always fp32, built from the fp32 masters")
+    p.add_argument("--validate-with-ema", action="store_true", default=None,
+                   help="not a FairSeq flag: run the validation passes with the averaged weights (FusedAdam.ema_weights) — the validation "
+                        "log line then carries \"weights\": \"ema\"")
     p.add_argument("--log-interval", type=int, default=10)
     # criterion flags: every field of every registered criterion's config dataclass (FairSeq derives them the same way)
     from .registry import CRITERION_REGISTRY as _CR
@@ -150,6 +162,24 @@ def main(argv=None):
     if args.required_batch_size_multiple != 1:
         print("[mdt-train] --required-batch-size-multiple: ignored — batches hold exactly --batch-size trees (the last one of an epoch may be smaller)",
               file=sys.stderr)
+    ema_names = ["ema_decay", "ema_start_update", "ema_update_freq", "ema_fp32", "validate_with_ema"]
+    ema_flags = [f for f in ema_names if getattr(args, f) is not None]
+    if ema_flags and not args.store_ema:
+        raise SystemExit("[mdt-train] " + ", ".join("--" + f.replace("_", "-") for f in ema_flags) + " without --store-ema: there is no "
+                         "weight average to configure, evaluate or store — add --store-ema")
+    if args.store_ema:
+        if args.ema_fp32:
+            print("[mdt-train] --ema-fp32: the average is always fp32 here, built from the fp32 master weights", file=sys.stderr)
+        args.ema_decay = 0.9999 if args.ema_decay is None else args.ema_decay
+        args.ema_start_update = args.ema_start_update or 0
+        args.ema_update_freq = args.ema_update_freq or 1
+        if not 0.0 <= args.ema_decay <= 1.0 or args.ema_update_freq < 1:
+            raise SystemExit("[mdt-train] --ema-decay must lie in [0, 1] and --ema-update-freq be >= 1")
+    store_ema, validate_with_ema = args.store_ema, bool(args.validate_with_ema)
+    args.ema_fp32, args.validate_with_ema = bool(args.ema_fp32), validate_with_ema
+    if not store_ema:
+        for f in ["store_ema"] + ema_names:      # a run without the average writes the checkpoint (its cfg included) it always wrote
+            delattr(args, f)
     from . import engine
     was_deterministic = engine.deterministic()
     if args.deterministic:
@@ -196,7 +226,9 @@ def main(argv=None):
     crit = crit_cls.build_criterion(args, task)      # constructor arguments by name from the flags, as FairSeq does
     betas = ast.literal_eval(args.adam_betas) if isinstance(args.adam_betas, str) else args.adam_betas
     opt = FusedAdam([p for p in model.parameters() if hasattr(p, "main_grad")], lr=args.lr, betas=betas, eps=args.adam_eps,
-                    weight_decay=args.weight_decay, clip_norm=args.clip_norm)     # the norm pass and the guard are always on, as in FairSeq
+                    weight_decay=args.weight_decay, clip_norm=args.clip_norm,     # the norm pass and the guard are always on, as in FairSeq
+                    **(dict(ema_decay=args.ema_decay, ema_start_update=args.ema_start_update, ema_update_freq=args.ema_update_freq)
+                       if store_ema else {}))
     sched = PolynomialDecayLR(args.lr, args.end_learning_rate, args.warmup_updates, args.total_num_update, args.power)
     from . import checkpoint as ckpt
     start_update, epoch0 = 0, 1
@@ -210,6 +242,14 @@ def main(argv=None):
         if rank == 0:
             print(json.dumps(dict(restored=args.restore_file, num_updates=start_update, optimizer=info["loaded_optimizer"],
                                   missing=len(info["missing"]), unexpected=len(info["unexpected"]))), flush=True)
+        if store_ema:
+            # the average is model state, not optimiser state: --reset-optimizer does not drop it
+            if info.get("ema") is not None:
+                opt.load_ema_state_dict(model, info["ema"])
+            else:
+                opt.seed_ema_from_weights()
+                print(f"[mdt-train] --store-ema: {args.restore_file} holds no extra_state['ema'] — the average starts as a copy of the "
+                      "restored weights", file=sys.stderr)
         dp.broadcast_parameters()
 
     skip_batches = 0          # batches of the running epoch that the restored checkpoint had already consumed
@@ -318,7 +358,7 @@ def main(argv=None):
                              training_time=time.time() - t0,
                              extra_state={"train_iterator": {"version": 2, "epoch": epoch0 + done // max(1, n_batches),
                                                              "iterations_in_epoch": done % max(1, n_batches), "shuffle": True},
-                                          "val_loss": best["value"]})
+                                          "val_loss": best["value"], **({"ema": opt.ema_state_dict(model)} if store_ema else {})})
 
     valid_history = []
     main.valid_history = valid_history
@@ -334,7 +374,8 @@ def main(argv=None):
         model.eval()
         tot = torch.zeros(6, dtype=torch.float32, device="cuda")
         keys = None
-        with torch.no_grad():
+        import contextlib
+        with (opt.ema_weights() if validate_with_ema else contextlib.nullcontext()), torch.no_grad():
             for pb in valid_batches():
                 loss, sample_size, log = crit(model, {"nsamples": pb.B, "net_input": {"batched_data": pb.batched_data}})
                 keys = [k for k in log if k not in ("loss", "sample_size", "nsentences", "ntokens")]
@@ -351,6 +392,8 @@ def main(argv=None):
         crit_cls.reduce_metrics([summed])            # logs through fairseq.metrics when fairseq is there
         m = {("valid_" + k): v for k, v in crit_cls.compute_metrics([summed]).items()}
         m.update(valid_counters=summed, num_updates=upd, subset=args.valid_subset)
+        if validate_with_ema:
+            m["weights"] = "ema"
         if best["value"] is None or m["valid_loss"] < best["value"]:
             best["value"] = m["valid_loss"]
         m["valid_best_loss"] = best["value"]
@@ -374,7 +417,7 @@ def main(argv=None):
             acc[2:6] += torch.stack([log[k] for k in counter_keys]).float()
         scal.copy_(acc)
         gscale = dp.finish_backward(scal, fold_scale=True)     # all-reduce (world > 1); 1 / global sample size is applied by the optimiser
-        opt.step(lr=lr_for(upd), grad_scale=gscale)
+        opt.step(lr=lr_for(upd), grad_scale=gscale, num_updates=upd)
         if upd % args.log_interval == 0 or upd == max_update:
             s = torch.cat([scal.double(), opt.guard_log_vector()]).tolist()     # the only host sync, once per log interval
             g = check_guard(upd, dict(gnorm=s[6], applied=int(s[7]), clipped=int(s[8]), skipped=int(s[9])))
