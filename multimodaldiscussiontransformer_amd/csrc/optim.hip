@@ -40,6 +40,25 @@ __device__ __forceinline__ void ema_update(float* __restrict__ ema, int64_t i, f
   ema[i] = d == 0.0f ? p : e;
 }
 
+// The Adam update of element i, the one copy both kernels run: loads, arithmetic and stores.  → the fp32 value the weight
+// average follows: what went to the master, or where there is none the parameter as stored.
+template <typename T>
+__device__ __forceinline__ float adam_element(int64_t i, const float* grad, float* m, float* v, float* master, T* param, float lr,
+                                              float beta1, float beta2, float eps, float wd, float gs, float step_size) {
+  const float g = grad[i] * gs;
+  const float mi = beta1 * m[i] + (1.0f - beta1) * g;
+  const float vi = beta2 * v[i] + (1.0f - beta2) * g * g;
+  float p = master ? master[i] : to_f32(param[i]);
+  p -= wd * lr * p;
+  p -= step_size * mi / (sqrtf(vi) + eps);
+  m[i] = mi;
+  v[i] = vi;
+  if (master) master[i] = p;
+  const T stored = from_f32<T>(p);
+  param[i] = stored;
+  return master ? p : to_f32(stored);
+}
+
 template <typename T, bool GUARD, bool EMA>
 __global__ __launch_bounds__(256) void adam_kernel(int64_t n, T* __restrict__ param, float* __restrict__ master,
                                                    const float* __restrict__ grad, float* __restrict__ m,
@@ -49,18 +68,8 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, T* __restrict__ pa
   float gs;
   if (!adam_scale_and_step<GUARD>(grad_scale, guard, gs, step_size)) return;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float g = grad[i] * gs;
-    const float mi = beta1 * m[i] + (1.0f - beta1) * g;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * g * g;
-    float p = master ? master[i] : to_f32(param[i]);
-    p -= wd * lr * p;
-    p -= step_size * mi / (sqrtf(vi) + eps);
-    m[i] = mi;
-    v[i] = vi;
-    if (master) master[i] = p;
-    const T stored = from_f32<T>(p);
-    param[i] = stored;
-    if constexpr (EMA) ema_update(ea.ema, i, ea.decay, master ? p : to_f32(stored));
+    const float p = adam_element(i, grad, m, v, master, param, lr, beta1, beta2, eps, wd, gs, step_size);
+    if constexpr (EMA) ema_update(ea.ema, i, ea.decay, p);
   }
 }
 
@@ -72,6 +81,18 @@ __device__ __forceinline__ int tensor_of_chunk(const int64_t* __restrict__ chunk
     if (chunk_first[mid] <= chunk) lo = mid; else hi = mid - 1;
   }
   return lo;
+}
+
+// Where chunk `chunk` of such a table lies: its tensor, and the element of that tensor the chunk starts at.  base() reads
+// chunk_first where the kernel asks for it: each kernel keeps the order of its loads.
+struct ChunkAt {
+  int tensor;
+  const int64_t* first;
+  int64_t chunk;
+  __device__ __forceinline__ int64_t base() const { return (chunk - first[tensor]) * 4096; }
+};
+__device__ __forceinline__ ChunkAt chunk_at(const int64_t* __restrict__ chunk_first, int n_tensors, int64_t chunk) {
+  return {tensor_of_chunk(chunk_first, n_tensors, chunk), chunk_first, chunk};
 }
 
 // Multi-tensor form: one launch walks a device table of tensors (the ~400 parameter tensors of mDT would otherwise
@@ -87,29 +108,18 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(int n_tensors, const md
   if (!adam_scale_and_step<GUARD>(grad_scale, guard, gs, step_size)) return;
   const int64_t total = chunk_first[n_tensors];
   for (int64_t chunk = blockIdx.x; chunk < total; chunk += gridDim.x) {
-    const int lo = tensor_of_chunk(chunk_first, n_tensors, chunk);
-    const mdt_adam_tensor t = tab[lo];
-    const int64_t base = (chunk - chunk_first[lo]) * 4096;
-    T* param = (T*)t.param;
+    const ChunkAt at = chunk_at(chunk_first, n_tensors, chunk);
+    const mdt_adam_tensor t = tab[at.tensor];
+    const int64_t base = at.base();
     float* ema = nullptr;
-    if constexpr (EMA) ema = ea.ema[lo];
+    if constexpr (EMA) ema = ea.ema[at.tensor];
 #pragma unroll 4
     for (int k = 0; k < 16; ++k) {
       const int64_t i = base + k * 256 + threadIdx.x;
       if (i >= t.numel) break;
-      const float g = t.grad[i] * gs;
-      const float mi = beta1 * t.m[i] + (1.0f - beta1) * g;
-      const float vi = beta2 * t.v[i] + (1.0f - beta2) * g * g;
-      float p = t.master ? t.master[i] : to_f32(param[i]);
-      p -= wd * lr * p;
-      p -= step_size * mi / (sqrtf(vi) + eps);
-      t.m[i] = mi;
-      t.v[i] = vi;
-      if (t.master) t.master[i] = p;
-      const T stored = from_f32<T>(p);
-      param[i] = stored;
+      const float p = adam_element(i, t.grad, t.m, t.v, t.master, (T*)t.param, lr, beta1, beta2, eps, wd, gs, step_size);
       if constexpr (EMA) {
-        if (ema) ema_update(ema, i, ea.decay, t.master ? p : to_f32(stored));
+        if (ema) ema_update(ema, i, ea.decay, p);
       }
     }
   }
@@ -127,11 +137,11 @@ __global__ __launch_bounds__(256) void ema_swap_multi_kernel(int n_tensors, cons
   constexpr int N = Vec<T>::N;
   const int64_t total = chunk_first[n_tensors];
   for (int64_t chunk = blockIdx.x; chunk < total; chunk += gridDim.x) {
-    const int lo = tensor_of_chunk(chunk_first, n_tensors, chunk);
-    float* ema = ema_tab[lo];
+    const ChunkAt at = chunk_at(chunk_first, n_tensors, chunk);
+    float* ema = ema_tab[at.tensor];
     if (!ema) continue;
-    const mdt_adam_tensor t = tab[lo];
-    const int64_t base = (chunk - chunk_first[lo]) * 4096;
+    const mdt_adam_tensor t = tab[at.tensor];
+    const int64_t base = at.base();
     T* param = (T*)t.param + base;
     const int64_t left = t.numel - base;
     if (t.master) {
@@ -214,9 +224,9 @@ __global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(int n_tensors, co
   __shared__ float red[4];
   const int64_t total = chunk_first[n_tensors];
   for (int64_t chunk = blockIdx.x; chunk < total; chunk += gridDim.x) {
-    const int lo = tensor_of_chunk(chunk_first, n_tensors, chunk);
-    const int64_t base = (chunk - chunk_first[lo]) * 4096;
-    const float s = chunk_sumsq(tab[lo].grad + base, tab[lo].numel - base, red);
+    const ChunkAt at = chunk_at(chunk_first, n_tensors, chunk);
+    const int64_t base = at.base();
+    const float s = chunk_sumsq(tab[at.tensor].grad + base, tab[at.tensor].numel - base, red);
     if (threadIdx.x == 0) partials[chunk] = s;
   }
 }
@@ -276,6 +286,9 @@ __global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const float* __
 
 using namespace mdt;
 
+// Grid of the chunk kernels: a block per 4096-element chunk, at most 65536 blocks (each then strides over the chunks).
+static unsigned chunk_grid(int64_t total_chunks) { return (unsigned)(total_chunks > 65536 ? 65536 : total_chunks); }
+
 static float adam_step_size(float lr, float beta1, float beta2, int step) {
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   return (float)(lr * sqrt(bc2) / bc1);
@@ -290,11 +303,10 @@ static int adam_step_multi(const char* what, void* stream, int dtype, int n_tens
   MDT_CHECK_ARG(table_dev && chunk_first_dev && step >= 1 && (!GUARD || guard), "%s: bad arguments", what);
   if constexpr (EMA) MDT_CHECK_ARG(ea.ema && ea.decay >= 0.0f && ea.decay <= 1.0f, "%s: ema_dev is NULL or ema_decay is outside [0, 1]", what);
   const float step_size = adam_step_size(lr, beta1, beta2, step);
-  const unsigned grid = (unsigned)(total_chunks > 65536 ? 65536 : total_chunks);
   hipStream_t st = (hipStream_t)stream;
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return launch_plain<adam_multi_kernel<T, GUARD, EMA>>(what, grid, 256, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay,
+    return launch_plain<adam_multi_kernel<T, GUARD, EMA>>(what, chunk_grid(total_chunks), 256, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay,
                                                           step_size, grad_scale, guard, ea);
   });
 }
@@ -379,10 +391,10 @@ extern "C" int mdt_ema_swap_multi(void* stream, int dtype, int n_tensors, const 
                                   const int64_t* chunk_first_dev, int64_t total_chunks, int restore) {
   if (n_tensors == 0 || total_chunks == 0) return MDT_OK;
   MDT_CHECK_ARG(table_dev && ema_dev && chunk_first_dev && (restore == 0 || restore == 1), "ema_swap_multi: bad arguments");
-  const unsigned grid = (unsigned)(total_chunks > 65536 ? 65536 : total_chunks);
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return launch_plain<ema_swap_multi_kernel<T>>("ema_swap_multi", grid, 256, (hipStream_t)stream, n_tensors, table_dev, ema_dev, chunk_first_dev, restore);
+    return launch_plain<ema_swap_multi_kernel<T>>("ema_swap_multi", chunk_grid(total_chunks), 256, (hipStream_t)stream, n_tensors, table_dev, ema_dev,
+                                                  chunk_first_dev, restore);
   });
 }
 
@@ -390,18 +402,14 @@ extern "C" int mdt_grad_sumsq_multi(void* stream, int n_tensors, const mdt_adam_
                                     int64_t total_chunks, float* partials) {
   if (n_tensors == 0 || total_chunks == 0) return MDT_OK;
   MDT_CHECK_ARG(table_dev && chunk_first_dev && partials, "grad_sumsq_multi: bad arguments");
-  const unsigned grid = (unsigned)(total_chunks > 65536 ? 65536 : total_chunks);
-  hipLaunchKernelGGL(grad_sumsq_multi_kernel, grid, 256, 0, (hipStream_t)stream, n_tensors, table_dev, chunk_first_dev, partials);
-  return check_launch("grad_sumsq_multi");
+  return launch_plain<grad_sumsq_multi_kernel>("grad_sumsq_multi", chunk_grid(total_chunks), 256, (hipStream_t)stream, n_tensors, table_dev,
+                                               chunk_first_dev, partials);
 }
 
 extern "C" int mdt_grad_sumsq(void* stream, int64_t n, const float* grad, float* partials) {
   if (n == 0) return MDT_OK;
   MDT_CHECK_ARG(n > 0 && grad && partials, "grad_sumsq: bad arguments");
-  const int64_t chunks = (n + 4095) / 4096;
-  const unsigned grid = (unsigned)(chunks > 65536 ? 65536 : chunks);
-  hipLaunchKernelGGL(grad_sumsq_kernel, grid, 256, 0, (hipStream_t)stream, n, grad, partials);
-  return check_launch("grad_sumsq");
+  return launch_plain<grad_sumsq_kernel>("grad_sumsq", chunk_grid((n + 4095) / 4096), 256, (hipStream_t)stream, n, grad, partials);
 }
 
 extern "C" int mdt_grad_norm_finalize(void* stream, const float* partials, int64_t n_partials, float max_norm,

@@ -379,7 +379,7 @@ _LN_BIAS_RIDE = os.environ.get("MDT_LN_BIAS_RIDE", "1") != "0"    # 0: those sum
 EMBED_LN_FUSED = os.environ.get("MDT_EMBED_LN_FUSED", "1") != "0"         # 0: embedding sum and its LayerNorm as two launches (A/B runs, tests)
 PATCH_K_PAD = os.environ.get("MDT_PATCH_K_PAD", "1") != "0"               # 0: ViT-L/14's K = 588 patch GEMMs stay on the any-shape kernel (A/B runs)
 PATCH_EMBED_FUSED = os.environ.get("MDT_PATCH_EMBED_FUSED", "1") != "0"   # 0: patch gather, GEMM and assembly as three launches (A/B runs, tests)
-WEIGHT_EPOCH = 0            # bumped by whoever rewrites weights behind torch's back (optim.FusedAdam.step)
+WEIGHT_EPOCH = 0            # bumped by whoever rewrites weights behind torch's back (FusedAdam's step and swap, a restore, a broadcast)
 
 
 def weights_changed():
@@ -387,14 +387,20 @@ def weights_changed():
     WEIGHT_EPOCH += 1
 
 
+def weight_stamp(w: torch.nn.Parameter) -> tuple:
+    """What a copy derived from ``w`` (zero-padded here, 8-bit in fp8.Fp8State) is stamped with; the copy is stale once the
+    stamp differs: torch-side in-place writes bump ``_version``, writes behind torch's back bump WEIGHT_EPOCH, a new storage moves
+    ``data_ptr``."""
+    return (w._version, WEIGHT_EPOCH, w.data_ptr())
+
+
 _KP_CACHE: dict = {}
 
 
 def _k_padded(w: torch.nn.Parameter, wmat: torch.Tensor, kp: int) -> torch.Tensor:
-    """[out, kp] copy of a weight viewed as [out, k] with zero columns behind k, cached until the weight changes (torch-side
-    writes bump ``_version``, the fused optimiser bumps WEIGHT_EPOCH)."""
+    """[out, kp] copy of a weight viewed as [out, k] with zero columns behind k, cached until the weight's stamp changes."""
     key = (id(w), kp)
-    ver = (w._version, WEIGHT_EPOCH, w.data_ptr())
+    ver = weight_stamp(w)
     hit = _KP_CACHE.get(key)
     if hit is not None and hit[0]() is w and hit[1] == ver:
         return hit[2]

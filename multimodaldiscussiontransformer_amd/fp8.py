@@ -18,10 +18,12 @@ the previous step measured at the same site (fmax / (amax * margin), margin 2 = 
 records this step's maximum, and one launch at the end of backward turns all maxima into the next scales.  Nothing ever
 leaves the device.  A site seen for the first time measures its maximum first (one extra reduction, once).  Weights:
 current scaling, re-quantised (and transposed where the input gradient needs the k-contiguous copy) whenever the
-optimiser has stepped.  Formats: OCP e4m3 for activations and weights, e5m2 for gradients; fp32 accumulation.
+weight's stamp has changed (engine.weight_stamp).  Formats: OCP e4m3 for activations and weights, e5m2 for gradients; fp32
+accumulation.
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -67,8 +69,7 @@ class Fp8State:
         self.amax = torch.zeros(capacity, dtype=torch.float32, device=self.device)
         self.fmax = torch.full((capacity,), 448.0, dtype=torch.float32, device=self.device)
         self.sites: Dict[tuple, int] = {}
-        self.weights: Dict[tuple, Tuple[torch.Tensor, int, int]] = {}
-        self.weights_version = 0
+        self.weights: Dict[tuple, tuple] = {}     # (id(w), transposed) -> (weakref to w, engine.weight_stamp(w), u8 copy, site)
         self.gemms = 0                      # launches that took the 8-bit kernel (diagnostics / tests)
         self.fused_outputs = 0              # ... of which also wrote the next GEMM's operand
         self.no_q8: set = set()             # consumer sites whose producer has no kernel that writes the copy (asked once)
@@ -118,12 +119,21 @@ class Fp8State:
         self.fused_outputs += 1
         return torch.empty(rows, k, dtype=torch.uint8, device=self.device), fmt, self.scale[i:i + 1], self.amax[i:i + 1], self.inv[i:i + 1]
 
+    @property
+    def weights_version(self) -> int:
+        """The epoch of weights rewritten behind torch's back (engine.WEIGHT_EPOCH): there is one counter, and it is not kept here."""
+        from . import engine
+        return engine.WEIGHT_EPOCH
+
     def weight(self, w: torch.nn.Parameter, transposed: bool = False):
-        """e4m3 copy of a weight ([N, K], or its transpose for dX = dY W), cached until the optimiser steps."""
+        """e4m3 copy of a weight ([N, K], or its transpose for dX = dY W), cached until the weight's stamp changes
+        (engine.weight_stamp: the optimiser stepped, a restore or broadcast wrote it, torch wrote it in place)."""
+        from .engine import weight_stamp
         key = (id(w), transposed)
+        stamp = weight_stamp(w)
         hit = self.weights.get(key)
-        if hit is not None and hit[2] == self.weights_version:
-            return hit[0], self.inv[hit[1]:hit[1] + 1]
+        if hit is not None and hit[0]() is w and hit[1] == stamp:
+            return hit[2], self.inv[hit[3]:hit[3] + 1]
         i, _ = self._site(("w", id(w), transposed), ops.FP8_E4M3)
         src = w.data
         if transposed:
@@ -132,11 +142,8 @@ class Fp8State:
         self.scale[i] = 448.0 / a
         self.inv[i] = a / 448.0
         q = ops.fp8_quantize(src.contiguous(), ops.FP8_E4M3, scale=self.scale[i:i + 1])
-        self.weights[key] = (q, i, self.weights_version)
+        self.weights[key] = (weakref.ref(w), stamp, q, i)
         return q, self.inv[i:i + 1]
-
-    def optimizer_stepped(self):
-        self.weights_version += 1
 
     def end_of_step(self):
         """All activation / gradient maxima of this step → next step's scales (one launch); weights keep theirs."""

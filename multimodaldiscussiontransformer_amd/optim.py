@@ -14,10 +14,23 @@ update leaves the average alone); ``ema_weights()`` swaps it into the working pa
 from __future__ import annotations
 
 import contextlib
+from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from ._lib import check, dt, lib, ptr, stream
+
+
+class Table(NamedTuple):
+    """The parameters of one dtype as the one-launch kernels read them (include/mdt_hip.h: mdt_adam_tensor)."""
+    rec: torch.Tensor                      # int64 [n, 6] on the device: param, master or 0, grad or 0, m, v, numel
+    first: torch.Tensor                    # int64 [n + 1] on the device: first 4096-element chunk of each tensor, first[n] = total
+    n: int
+    total: int
+    params: list
+    grad_ptrs: list                        # the gradient address each record was built from (0: a table without gradients)
+    ema_ptrs: Optional[torch.Tensor]       # int64 [n] on the device: the averages in table order (None: no average is kept)
 
 
 class FusedAdam:
@@ -47,7 +60,8 @@ class FusedAdam:
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_start_update, self.ema_update_freq = int(ema_start_update), int(ema_update_freq)
         self.ema_arena = None
-        self._ema_ptrs, self._swap_tab, self._in_ema = {}, None, False
+        self._tab, self._outside = None, self.params        # the step's tables by dtype, and the parameters they leave out
+        self._swap_tab, self._in_ema = None, False
         if self.ema_decay is not None:
             if not 0.0 <= self.ema_decay <= 1.0 or self.ema_update_freq < 1:
                 raise ValueError(f"FusedAdam: ema_decay {ema_decay!r} must lie in [0, 1] and ema_update_freq {ema_update_freq!r} be >= 1")
@@ -58,45 +72,49 @@ class FusedAdam:
                 n += (p.numel() + 3) // 4 * 4
             self.ema_arena = torch.zeros(max(n, 1), dtype=torch.float32, device=self.params[0].device if self.params else "cpu")
             for p, off in zip(self.params, offs):
-                st = self.state[id(p)]
-                st["ema"] = self.ema_arena[off:off + p.numel()].view(p.shape)
-                st["ema"].copy_(st["master"] if "master" in st else p.detach().float())
+                self.state[id(p)]["ema"] = self.ema_arena[off:off + p.numel()].view(p.shape)
+            self.seed_ema_from_weights()
 
-    def _ema_pointers(self, ps):
-        import numpy as np
-        a = np.asarray([self.state[id(p)]["ema"].data_ptr() for p in ps], dtype=np.int64)
-        return torch.from_numpy(a).to(ps[0].device)
+    def _fp32_source(self, p):
+        """The fp32 weights of ``p``: its master, or the parameter itself where there is none."""
+        st = self.state[id(p)]
+        return st["master"] if "master" in st else p.detach().float()
 
-    def _tables(self):
-        """Device tables for the one-launch update, built once: parameters of one dtype whose gradients live in the
-        fp32 ``main_grad`` arena (stable addresses).  Others fall back to one launch per tensor."""
-        if not self.multi_tensor:
-            return {}
-        if getattr(self, "_tab", None) is not None:
-            return self._tab
-        import numpy as np
+    def _build_tables(self, params, with_grads):
+        """{dtype: Table} over ``params`` in their order; ``with_grads``: the records point at ``p.main_grad``."""
         groups = {}
-        for p in self.params:
-            g = getattr(p, "main_grad", None)
-            if g is None or not g.is_contiguous() or not p.data.is_contiguous():
-                continue
+        for p in params:
             groups.setdefault(p.dtype, []).append(p)
         tab = {}
         for dtype, ps in groups.items():
+            gptrs = [p.main_grad.data_ptr() if with_grads else 0 for p in ps]
             rec = np.zeros((len(ps), 6), dtype=np.int64)
             first = np.zeros(len(ps) + 1, dtype=np.int64)
             for i, p in enumerate(ps):
                 st = self.state[id(p)]
-                rec[i] = (p.data.data_ptr(), st["master"].data_ptr() if "master" in st else 0, p.main_grad.data_ptr(),
-                          st["m"].data_ptr(), st["v"].data_ptr(), p.numel())
+                rec[i] = (p.data.data_ptr(), st["master"].data_ptr() if "master" in st else 0, gptrs[i], st["m"].data_ptr(),
+                          st["v"].data_ptr(), p.numel())
                 first[i + 1] = first[i] + (p.numel() + 4095) // 4096
             dev = ps[0].device
-            tab[dtype] = (torch.from_numpy(rec).to(dev), torch.from_numpy(first).to(dev), len(ps), int(first[-1]),
-                          {id(p) for p in ps}, ps, [p.main_grad.data_ptr() for p in ps])
+            ema = None
             if self.ema_decay is not None:
-                self._ema_ptrs[dtype] = self._ema_pointers(ps)      # parallel to the table: mdt_adam_step_multi_ema's ema_dev
-        self._tab = tab
+                ema = torch.from_numpy(np.asarray([self.state[id(p)]["ema"].data_ptr() for p in ps], dtype=np.int64)).to(dev)
+            tab[dtype] = Table(torch.from_numpy(rec).to(dev), torch.from_numpy(first).to(dev), len(ps), int(first[-1]), ps, gptrs, ema)
         return tab
+
+    def _tables(self):
+        """Device tables for the one-launch update: parameters of one dtype whose gradients live in the fp32 ``main_grad``
+        arena.  Others (``_outside``) take one launch per tensor.  Built once, and again when a ``main_grad`` moved: the views
+        move when the DDP arena is re-laid-out after the first step."""
+        if not self.multi_tensor:
+            return {}
+        if self._tab is None or any([p.main_grad.data_ptr() for p in t.params] != t.grad_ptrs for t in self._tab.values()):
+            inside = [p for p in self.params if getattr(p, "main_grad", None) is not None and p.main_grad.is_contiguous()
+                      and p.data.is_contiguous()]
+            self._tab = self._build_tables(inside, True)
+            ids = {id(p) for p in inside}
+            self._outside = [p for p in self.params if id(p) not in ids]
+        return self._tab
 
     # -- guard state (include/mdt_hip.h: mdt_adam_guard — 8 words: scale, gnorm, step_size | skip, applied, clipped, skipped, -)
     def guard_buffers(self):
@@ -148,9 +166,9 @@ class FusedAdam:
         ones, in step order), then the one finaliser launch."""
         guard, partials = self.guard_buffers()
         n = 0
-        for rec, first, nt, total, _, _, _ in tables.values():
-            check(lib.mdt_grad_sumsq_multi(stream(), nt, ptr(rec), ptr(first), total, ptr(partials[n:])), "mdt_grad_sumsq_multi")
-            n += total
+        for t in tables.values():
+            check(lib.mdt_grad_sumsq_multi(stream(), t.n, ptr(t.rec), ptr(t.first), t.total, ptr(partials[n:])), "mdt_grad_sumsq_multi")
+            n += t.total
             self.norm_launches += 1
         for p, g in rest:
             check(lib.mdt_grad_sumsq(stream(), g.numel(), ptr(g), ptr(partials[n:])), "mdt_grad_sumsq")
@@ -176,45 +194,31 @@ class FusedAdam:
             k = self.step_count if num_updates is None else int(num_updates)
             if k % self.ema_update_freq == 0:
                 ema = 0.0 if k < self.ema_start_update else self.ema_decay
-        done = set()
-        # main_grad views move when the DDP arena is re-laid-out after the first step: rebuild the tables then
-        if getattr(self, "_tab", None) is not None and any(
-                [p.main_grad.data_ptr() for p in ps] != gptrs for (_, _, _, _, _, ps, gptrs) in self._tab.values()):
-            self._tab = None
         tables = self._tables()
-        for (_, _, _, _, ids, _, _) in tables.values():
-            done |= ids
-        rest = list(self._rest(done))
+        rest = list(self._rest())
         guard = self._norm_pass(lr, grad_scale, tables, rest) if self.clip_norm is not None else None
-        for dtype, (rec, first, n, total, ids, _, _) in tables.items():
-            head = (stream(), 0 if dtype == torch.float32 else 1, n, ptr(rec), ptr(first), total, float(lr), float(self.betas[0]),
-                    float(self.betas[1]), float(self.eps), float(self.weight_decay), self.step_count)
-            if ema is not None:
-                tail = (ptr(self._ema_ptrs[dtype]), ema)
-                if guard is None:
-                    check(lib.mdt_adam_step_multi_ema(*head, ptr(grad_scale), *tail), "mdt_adam_step_multi_ema")
-                else:
-                    check(lib.mdt_adam_step_multi_ema_guarded(*head, ptr(guard), *tail), "mdt_adam_step_multi_ema_guarded")
-            elif guard is None:
-                check(lib.mdt_adam_step_multi(*head, ptr(grad_scale)), "mdt_adam_step_multi")
-            else:
-                check(lib.mdt_adam_step_multi_guarded(*head, ptr(guard)), "mdt_adam_step_multi_guarded")
-        self._step_rest(lr, grad_scale, rest, guard, ema)
-        self._weights_moved()
+        hyper = (float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.step_count)
+        for t in tables.values():
+            self._adam(True, (stream(), dt(t.params[0]), t.n, ptr(t.rec), ptr(t.first), t.total, *hyper), grad_scale, guard,
+                       () if ema is None else (ptr(t.ema_ptrs), ema))
+        for p, g in rest:
+            st = self.state[id(p)]
+            self._adam(False, (stream(), dt(p), p.numel(), ptr(p.data), ptr(st.get("master")), ptr(g), ptr(st["m"]), ptr(st["v"]), *hyper),
+                       grad_scale, guard, () if ema is None else (ptr(st["ema"]), ema))
+        from . import engine
+        engine.weights_changed()                 # copies derived from the weights (engine._k_padded, fp8.Fp8State.weight) are stale now
 
     @staticmethod
-    def _weights_moved():
-        from . import fp8
-        if fp8.ACTIVE is not None:
-            fp8.ACTIVE.optimizer_stepped()      # the cached 8-bit weight copies are stale now
-        from . import engine
-        engine.weights_changed()                # ... and the zero-padded copies the patch projection reads (engine._k_padded)
+    def _adam(multi, head, grad_scale, guard, ema_tail):
+        """One Adam launch.  ``head``: the arguments up to ``step``; then the guard state where there is one, else the optional
+        gradient scale; then ``ema_tail`` (averages, decay) or nothing.  The entry point is looked up in ``lib`` by its name, at
+        the call."""
+        name = "mdt_adam_step" + ("_multi" if multi else "") + ("_ema" if ema_tail else "") + ("" if guard is None else "_guarded")
+        check(getattr(lib, name)(*head, ptr(grad_scale if guard is None else guard), *ema_tail), name)
 
-    def _rest(self, done):
+    def _rest(self):
         """(parameter, contiguous fp32 gradient) of every parameter the tables do not cover and that has a gradient."""
-        for p in self.params:
-            if id(p) in done:
-                continue
+        for p in self._outside:
             g = getattr(p, "main_grad", None)
             if g is None:
                 g = p.grad
@@ -223,21 +227,6 @@ class FusedAdam:
                 if g.dtype != torch.float32:
                     g = g.float()
             yield p, g.contiguous()
-
-    def _step_rest(self, lr, grad_scale, rest, guard=None, ema=None):
-        for p, g in rest:
-            st = self.state[id(p)]
-            head = (stream(), dt(p), p.numel(), ptr(p.data), ptr(st.get("master")), ptr(g), ptr(st["m"]), ptr(st["v"]), float(lr),
-                    float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.step_count)
-            if ema is not None:
-                if guard is None:
-                    check(lib.mdt_adam_step_ema(*head, ptr(grad_scale), ptr(st["ema"]), ema), "mdt_adam_step_ema")
-                else:
-                    check(lib.mdt_adam_step_ema_guarded(*head, ptr(guard), ptr(st["ema"]), ema), "mdt_adam_step_ema_guarded")
-            elif guard is None:
-                check(lib.mdt_adam_step(*head, ptr(grad_scale)), "mdt_adam_step")
-            else:
-                check(lib.mdt_adam_step_guarded(*head, ptr(guard)), "mdt_adam_step_guarded")
 
     # -- the weight average (FairSeq --store-ema)
     def _need_ema(self):
@@ -286,38 +275,24 @@ class FusedAdam:
         """The average restarts as a copy of the current weights (the masters where there are any)."""
         self._need_ema()
         for p in self.params:
-            st = self.state[id(p)]
-            st["ema"].copy_(st["master"] if "master" in st else p.detach().float())
+            self.state[id(p)]["ema"].copy_(self._fp32_source(p))
 
-    def _swap_tables(self):
-        """Tables of the swap launch: EVERY parameter of the optimiser by dtype (the step's tables leave out what has no
-        ``main_grad``), rebuilt when a parameter's storage moved."""
-        import numpy as np
+    def _all_tables(self):
+        """Tables of the swap launch: EVERY parameter of the optimiser by dtype, no gradients (the step's tables leave out what
+        has no ``main_grad``), rebuilt when a parameter's storage moved."""
         now = [p.data.data_ptr() for p in self.params]
-        if self._swap_tab is not None and self._swap_tab[0] == now:
-            return self._swap_tab[1]
-        groups = {}
-        for p in self.params:
-            if not p.data.is_contiguous():
+        if self._swap_tab is None or self._swap_tab[0] != now:
+            if not all(p.data.is_contiguous() for p in self.params):
                 raise RuntimeError("FusedAdam.ema_weights(): a parameter is not contiguous")
-            groups.setdefault(p.dtype, []).append(p)
-        tabs = []
-        for dtype, ps in groups.items():
-            rec = np.zeros((len(ps), 6), dtype=np.int64)
-            first = np.zeros(len(ps) + 1, dtype=np.int64)
-            for i, p in enumerate(ps):
-                st = self.state[id(p)]
-                rec[i] = (p.data.data_ptr(), st["master"].data_ptr() if "master" in st else 0, 0, st["m"].data_ptr(), st["v"].data_ptr(), p.numel())
-                first[i + 1] = first[i] + (p.numel() + 4095) // 4096
-            dev = ps[0].device
-            tabs.append((dt(ps[0]), len(ps), torch.from_numpy(rec).to(dev), self._ema_pointers(ps), torch.from_numpy(first).to(dev), int(first[-1])))
-        self._swap_tab = (now, tabs)
-        return tabs
+            self._swap_tab = (now, self._build_tables(self.params, False))
+        return self._swap_tab[1]
 
     def _swap(self, restore):
-        for d, n, rec, eptr, first, total in self._swap_tables():
-            check(lib.mdt_ema_swap_multi(stream(), d, n, ptr(rec), ptr(eptr), ptr(first), total, int(restore)), "mdt_ema_swap_multi")
-        self._weights_moved()                    # both ends: the cached weight copies (fp8, padded, transposed) are stale
+        for t in self._all_tables().values():
+            check(lib.mdt_ema_swap_multi(stream(), dt(t.params[0]), t.n, ptr(t.rec), ptr(t.ema_ptrs), ptr(t.first), t.total, int(restore)),
+                  "mdt_ema_swap_multi")
+        from . import engine
+        engine.weights_changed()                 # both ends: the cached weight copies (fp8, zero-padded) are stale
 
     @contextlib.contextmanager
     def ema_weights(self):

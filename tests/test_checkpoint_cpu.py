@@ -263,6 +263,65 @@ def test_torch_adam_state_of_a_frozen_encoder_model_loads_positionally(tmp_path)
         ck.load_optimizer_state_dict(opt, model, shifted)
 
 
+def test_fused_adam_tables_come_from_one_builder():
+    """FusedAdam's device tables (optim.Table) over hand-made CPU parameters; building them launches nothing.  Two bf16 parameters
+    (4097 and 4096 elements) and a one-element fp32 one have a ``main_grad``, a fourth has only ``.grad``: the step's tables hold
+    the first three with the pointers and chunk counts computed here, the fourth comes out of ``_rest()``, the swap's tables hold
+    all four without gradients, both carry the averages' pointers in table order, and the step's tables are reused until a
+    ``main_grad`` lies at another address."""
+    from multimodaldiscussiontransformer_amd.optim import FusedAdam
+    gen = torch.Generator().manual_seed(11)
+    a = torch.nn.Parameter(torch.randn(4097, generator=gen).bfloat16())
+    b = torch.nn.Parameter(torch.randn(64, 64, generator=gen).bfloat16())
+    c = torch.nn.Parameter(torch.randn(1, generator=gen))
+    d = torch.nn.Parameter(torch.randn(5, generator=gen))
+    for p in (a, b, c):
+        p.main_grad = torch.zeros(p.shape)
+    d.grad = torch.ones(5)
+    opt = FusedAdam([a, b, c, d], ema_decay=0.9)
+
+    def rows(ps, grads):
+        out = []
+        for p in ps:
+            st = opt.state[id(p)]
+            out.append([p.data.data_ptr(), st["master"].data_ptr() if p.dtype == torch.bfloat16 else 0,
+                        p.main_grad.data_ptr() if grads else 0, st["m"].data_ptr(), st["v"].data_ptr(), p.numel()])
+        return out
+
+    def firsts(ps):
+        out = [0]
+        for p in ps:
+            out.append(out[-1] + -(-p.numel() // 4096))
+        return out
+
+    def check(tabs, want, grads):
+        assert list(tabs) == [ps[0].dtype for ps in want]
+        for t, ps in zip(tabs.values(), want):
+            assert len(t.params) == len(ps) and all(x is y for x, y in zip(t.params, ps))
+            assert t.rec.dtype == torch.int64 and t.rec.tolist() == rows(ps, grads)
+            assert t.first.dtype == torch.int64 and t.first.tolist() == firsts(ps)
+            assert (t.n, t.total) == (len(ps), firsts(ps)[-1])
+            assert t.grad_ptrs == [r[2] for r in rows(ps, grads)]
+            assert t.ema_ptrs.dtype == torch.int64 and t.ema_ptrs.tolist() == [opt.state[id(p)]["ema"].data_ptr() for p in ps]
+
+    tabs = opt._tables()
+    check(tabs, [[a, b], [c]], True)
+    assert tabs[torch.bfloat16].first.tolist() == [0, 2, 3] and tabs[torch.float32].total == 1
+    rest = list(opt._rest())
+    assert len(rest) == 1 and rest[0][0] is d and rest[0][1].data_ptr() == d.grad.data_ptr()
+    check(opt._all_tables(), [[a, b], [c, d]], False)
+    again = opt._tables()
+    assert again is tabs and all(again[k] is tabs[k] for k in tabs), "the step's tables were rebuilt without a reason"
+    old = a.main_grad                                       # stays alive: the new one cannot take its address
+    a.main_grad = torch.zeros(a.shape)
+    assert a.main_grad.data_ptr() != old.data_ptr()
+    moved = opt._tables()
+    assert moved[torch.bfloat16] is not tabs[torch.bfloat16]
+    check(moved, [[a, b], [c]], True)
+    assert [id(p) for p, _ in opt._rest()] == [id(d)]
+    assert FusedAdam([c])._tables()[torch.float32].ema_ptrs is None          # no average: nothing to point at
+
+
 def test_reset_meters_does_not_rewind_the_data_iterator(tmp_path):
     """FairSeq ties the iterator state (epoch and position inside it) to --reset-dataloader only; --reset-meters empties
     the meters, not the resume position."""

@@ -232,7 +232,7 @@ def test_state_dict_round_trip(engine):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_parameters_outside_the_table_take_the_single_tensor_form(dtype, clip_norm):
     """tests/test_grad_clip_gpu.py's stand-alone parameters: all in the table ("multi"), one launch per tensor ("single"), every
-    other one with only p.grad ("mix": those go through _step_rest and the single-tensor `_ema` entry points).  The three optimisers
+    other one with only p.grad ("mix": those take the per-tensor launches of step(), the single-tensor `_ema` entry points).  The three optimisers
     end with the same bits in parameters and averages, and ema_weights() covers the parameters outside the table too."""
     from multimodaldiscussiontransformer_amd.optim import FusedAdam
     from tests.test_grad_clip_gpu import CLIP_SHAPES, _params, _set_grads

@@ -394,3 +394,49 @@ def test_fp8_training_learns_what_bf16_learns(capsys):
     assert abs(f["last"] - b["last"]) <= 0.05 * b["last"] + 0.01, (b["last"], f["last"])
     assert abs(f["vloss"] - b["vloss"]) <= 0.05 * b["vloss"] + 0.01, (b["vloss"], f["vloss"])
     assert abs(f["f1"] - b["f1"]) <= 0.03 and abs(f["acc"] - b["acc"]) <= 0.02, (b, f)
+
+
+@pytest.mark.parametrize("transposed", [False, True], ids=["n_k", "transposed"])
+def test_fp8_weight_cache_follows_the_one_weight_epoch(ops, transposed):
+    """Fp8State.weight() keeps its 8-bit copy while engine.weight_stamp(w) stands and makes a new one when it moves: a .data write
+    announced by engine.weights_changed() (what a restore and a parameter broadcast do), an in-place write under no_grad that only
+    bumps w._version, and a FusedAdam step.  [256, 64] is the smallest 2-D weight fp8_quantize takes on its vector path.  Doubling
+    a weight doubles its maximum too, so the fresh bytes equal the old ones: what tells a fresh copy from a stale one is the tensor
+    object and the inverse scale that comes with it."""
+    from multimodaldiscussiontransformer_amd import engine
+    from multimodaldiscussiontransformer_amd.fp8 import Fp8State
+    from multimodaldiscussiontransformer_amd.optim import FusedAdam
+    g = torch.Generator(device="cuda").manual_seed(17)
+    w = torch.nn.Parameter((torch.randn(256, 64, device="cuda", generator=g) * 0.05).bfloat16())
+    state = Fp8State("cuda")
+
+    def fresh(q, inv, old, what):
+        src = w.data.t().contiguous() if transposed else w.data
+        amax = src.abs().max().float()
+        assert q is not old, f"{what}: the stale copy was returned"
+        assert torch.equal(q, ops.fp8_quantize(src, ops.FP8_E4M3, scale=(448.0 / amax).reshape(1))), f"{what}: not the bytes of the weight as it is now"
+        assert torch.equal(inv, (amax / 448.0).reshape(1)), f"{what}: not the scale of the weight as it is now"
+
+    q0, inv0 = state.weight(w, transposed)
+    fresh(q0, inv0, None, "first call")
+    first_inv = float(inv0)                                 # inv is a view of the state's slot: it follows the refreshes
+    assert tuple(q0.shape) == ((64, 256) if transposed else (256, 64)) and q0.dtype == torch.uint8
+    assert state.weight(w, transposed)[0] is q0, "a second call with nothing in between made a new copy"
+    w.data.mul_(2)
+    engine.weights_changed()
+    q1, inv1 = state.weight(w, transposed)
+    fresh(q1, inv1, q0, ".data write + weights_changed()")
+    assert state.weight(w, transposed)[0] is q1
+    with torch.no_grad():
+        w.mul_(2)
+    q2, inv2 = state.weight(w, transposed)
+    fresh(q2, inv2, q1, "in-place write under no_grad")
+    assert float(inv2) == 4.0 * first_inv
+    tiny = torch.nn.Parameter(torch.ones(8, device="cuda"))
+    tiny.grad = torch.ones(8, device="cuda")
+    epoch = engine.WEIGHT_EPOCH
+    FusedAdam([tiny], lr=1e-3).step()
+    assert engine.WEIGHT_EPOCH > epoch and state.weights_version == engine.WEIGHT_EPOCH
+    q3, inv3 = state.weight(w, transposed)
+    fresh(q3, inv3, q2, "FusedAdam.step()")
+    assert state.weight(w, transposed)[0] is q3

@@ -57,7 +57,7 @@ def main():
     opt = FusedAdam([p for p in model.parameters() if hasattr(p, "main_grad")], lr=3e-5, weight_decay=0.01, ema_decay=a.decay)
     model.main_grad_flat.normal_(0.0, 1e-3)
     tables = opt._tables()
-    covered = sum(len(t[5]) for t in tables.values())
+    covered = sum(len(t.params) for t in tables.values())
     assert covered == len(opt.params), f"{len(opt.params) - covered} parameters are outside the multi-tensor table"
     elements = sum(p.numel() for p in opt.params)
     masters = [opt.state[id(p)]["master"] for p in opt.params]
@@ -66,8 +66,7 @@ def main():
     step = [0]
 
     def head(dtype, t):
-        rec, first, n, total = t[:4]
-        return (stream(), 0 if dtype == torch.float32 else 1, n, ptr(rec), ptr(first), total, *hyper, step[0])
+        return (stream(), 0 if dtype == torch.float32 else 1, t.n, ptr(t.rec), ptr(t.first), t.total, *hyper, step[0])
 
     def plain(which=lib):
         for dtype, t in tables.items():
@@ -75,7 +74,7 @@ def main():
 
     def ema():
         for dtype, t in tables.items():
-            check(lib.mdt_adam_step_multi_ema(*head(dtype, t), None, ptr(opt._ema_ptrs[dtype]), a.decay), "mdt_adam_step_multi_ema")
+            check(lib.mdt_adam_step_multi_ema(*head(dtype, t), None, ptr(t.ema_ptrs), a.decay), "mdt_adam_step_multi_ema")
 
     def plain_lerp():
         plain()
