@@ -469,6 +469,40 @@ int mdt_adam_step_multi_ema_guarded(void* stream, int dtype, int n_tensors, cons
 int mdt_ema_swap_multi(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev, float* const* ema_dev,
                        const int64_t* chunk_first_dev, int64_t total_chunks, int restore);
 
+/* Parameter groups: a learning-rate scale and a weight decay PER TENSOR on the same one launch (lower rates for pretrained
+ * blocks, layer-wise rate decay, no decay on biases and LayerNorm weights).  One record per table entry, in a DEVICE array
+ * parallel to the table and indexed by tensor, as ema_dev is (mdt_adam_tensor keeps its layout).  For the tensor's record g the
+ * kernel computes, once per tensor (per 4096-element chunk in the table form), after the guard state has been read:
+ *        lr_t        = lr * g.lr_scale                  ONE fp32 product
+ *        step_size_t = step_size * g.lr_scale           ONE fp32 product; step_size is the host's
+ *                                                       (float)(lr * sqrt(1 - beta2^step) / (1 - beta1^step)), or the guard state's
+ *                                                       once an update has been skipped: that one is scaled too
+ *        wd_t        = g.weight_decay
+ * and every element then takes the update of mdt_adam_step with (lr_t, wd_t, step_size_t) in place of (lr, weight_decay,
+ * step_size): p -= (wd_t * lr_t) * p;  p -= step_size_t * m' / (sqrtf(v') + eps).  Consequences:
+ *   - lr_scale == 1.0f and weight_decay equal to a global value: the bits of the entry point without groups called with that
+ *     weight_decay (x * 1.0f == x), in every output;
+ *   - lr_scale == 0: m and v advance, param and master keep their bits for finite values (torch's lr = 0 group): both
+ *     subtrahends are +-0;
+ *   - the gradient norm, the guard and the average do not know about groups: one norm over all gradients, a skipped update
+ *     stores nothing, e = d e + (1 - d) p follows the p this tensor's group produced.
+ * The optional parts are nullable: at most one of grad_scale / guard (both: MDT_ERR_ARG), ema_dev / ema NULL: no average
+ * (ema_decay is then ignored).  groups_dev NULL is MDT_ERR_ARG: the entry points above are the forms without groups.  The single
+ * form takes the record by value, does the same two products in the kernel and so equals the table form bit for bit; it refuses
+ * a non-finite or negative lr_scale or weight_decay (the table's records live on the device and are the caller's to validate).
+ * Nothing but the tensors' own param, master, m, v and ema is written; no atomics. */
+typedef struct {
+  float lr_scale;
+  float weight_decay;
+} mdt_adam_group;
+int mdt_adam_step_multi_groups(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
+                               const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2,
+                               float eps, int step, const mdt_adam_group* groups_dev, const float* grad_scale,
+                               const mdt_adam_guard* guard, float* const* ema_dev, float ema_decay);
+int mdt_adam_step_group(void* stream, int dtype, int64_t n, void* param, float* master, const float* grad, float* m, float* v,
+                        float lr, float beta1, float beta2, float eps, int step, float lr_scale, float weight_decay,
+                        const float* grad_scale, const mdt_adam_guard* guard, float* ema, float ema_decay);
+
 /* ------------------------------------------------------------------ ordered (bit-reproducible) gradient reductions
  * The backward pass accumulates gradients with fp32 atomics (MDT_EPI_ATOMIC / _ASUM / _COLSUM, mdt_colsum, mdt_layernorm_bwd,
  * mdt_row_scatter_add_f32, the structural-bias gradient of mdt_attention_bwd): two runs of one step agree to ~1e-7, not bit for

@@ -112,6 +112,8 @@ _SIGS = {
     "mdt_adam_step_multi_ema": ([_vp, _i, _i, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp, _vp, _f], _i),
     "mdt_adam_step_ema_guarded": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp, _vp, _f], _i),
     "mdt_adam_step_multi_ema_guarded": ([_vp, _i, _i, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp, _vp, _f], _i),
+    "mdt_adam_step_multi_groups": ([_vp, _i, _i, _vp, _vp, _i64, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _f], _i),
+    "mdt_adam_step_group": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _f, _vp, _vp, _vp, _f], _i),
     "mdt_ema_swap_multi": ([_vp, _i, _i, _vp, _vp, _vp, _i64, _i], _i),
     "mdt_resize_plan_ksize": ([_i, _i], _i),
     "mdt_resize_plan": ([_i, _i, _vp, _vp, _i], _i),

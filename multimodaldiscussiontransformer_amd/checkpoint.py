@@ -22,7 +22,12 @@ dict —
                          not counted; a parameter that never got a gradient has no ``state`` entry), FairSeq's layout for
                          fp32 training and for
                          ``--fp16-no-flatten-grads``; its flattened-fp32-copy layout holds a single entry instead and is
-                         accepted on load when the element counts add up)
+                         accepted on load when the element counts add up).  An optimiser with parameter groups
+                         (FusedAdam(..., [{"params", "lr_scale", "weight_decay"}])) writes one ``param_groups`` entry per
+                         distinct (lr_scale, weight_decay) in order of first appearance — "lr" = base x scale, "lr_scale",
+                         the same positional ids — and on load keeps the hyper-parameters of the RUNNING optimiser
+                         (FairSeq: current arguments override stored ones); the state stays positional, so a one-group
+                         file restores into a grouped optimiser and the reverse
 
 ``load_checkpoint`` follows ``Trainer.load_checkpoint``: the model is loaded strictly (missing / unexpected keys raise),
 optimizer state, update count and LR schedule come back unless ``reset_optimizer`` — the combination the launch script
@@ -84,9 +89,30 @@ def optimizer_state_dict(optimizer, model, criterion=None) -> dict:
         i = index[id(p)]
         st = optimizer.state[id(p)]
         state[i] = {"step": step, "exp_avg": st["m"].detach().cpu(), "exp_avg_sq": st["v"].detach().cpu()}
+    if getattr(optimizer, "has_groups", False):
+        return {"state": state, "param_groups": _group_entries(optimizer, params, index)}
     group = {"lr": optimizer.lr, "betas": tuple(optimizer.betas), "eps": optimizer.eps, "weight_decay": optimizer.weight_decay,
              "amsgrad": False, "params": list(range(len(params)))}
     return {"state": state, "param_groups": [group]}
+
+
+def _group_entries(optimizer, params, index):
+    """``param_groups`` of an optimiser with parameter groups: one entry per distinct (lr_scale, weight_decay) in order of first
+    appearance in the positional numbering; a trainable parameter the optimiser does not hold counts as (1, global)."""
+    held = {id(p) for p in optimizer.params}
+    out = {}
+    for p in params:
+        scale, wd = optimizer.hyper_of(p) if id(p) in held else (1.0, float(optimizer.weight_decay))
+        if (scale, wd) not in out:
+            out[(scale, wd)] = {"lr": optimizer.lr * scale, "lr_scale": scale, "betas": tuple(optimizer.betas), "eps": optimizer.eps,
+                                "weight_decay": wd, "amsgrad": False, "params": []}
+        out[(scale, wd)]["params"].append(index[id(p)])
+    return list(out.values())
+
+
+def _partition(groups):
+    """The partition a ``param_groups`` list describes, as a comparable value: sorted (lr_scale, weight_decay, ids)."""
+    return sorted((float(g.get("lr_scale", 1.0)), float(g["weight_decay"]), tuple(g["params"])) for g in groups)
 
 
 def load_optimizer_state_dict(optimizer, model, osd: dict, criterion=None):
@@ -97,6 +123,8 @@ def load_optimizer_state_dict(optimizer, model, osd: dict, criterion=None):
     params = _trainable(model, criterion)
     st_in = osd["state"]
     ids = [i for g in osd["param_groups"] for i in g["params"]]
+    if len(osd["param_groups"]) > 1:
+        ids = sorted(ids)          # several groups: each lists ids of the ONE positional numbering, whatever the order of the groups
     if len(st_in) == 1 and len(ids) <= 1 and len(optimizer.params) > 1:
         # FairSeq FP16Optimizer with flattened fp32 copies: one flat tensor over the trainable parameters in order
         (flat,) = st_in.values()
@@ -138,8 +166,18 @@ def load_optimizer_state_dict(optimizer, model, osd: dict, criterion=None):
         optimizer.step_count = steps.pop() if steps else 0
     if hasattr(optimizer, "reset_guard"):
         optimizer.reset_guard()                 # the restored count is of applied updates: nothing skipped since
-    g = osd["param_groups"][0]
-    optimizer.lr, optimizer.betas, optimizer.eps, optimizer.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
+    stored = osd["param_groups"]
+    if not getattr(optimizer, "has_groups", False) and len(stored) == 1 and "lr_scale" not in stored[0]:
+        g = stored[0]
+        optimizer.lr, optimizer.betas, optimizer.eps, optimizer.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
+        return
+    # parameter groups on either side: the hyper-parameters of the running optimiser stand (FairSeq: current arguments override
+    # stored ones); only the state above, which is positional, came from the file
+    index = {id(p): i for i, p in enumerate(params)}
+    if hasattr(optimizer, "hyper_of") and len(ids) == len(params) and _partition(stored) != _partition(_group_entries(optimizer, params, index)):
+        import sys
+        print(f"[checkpoint] the stored parameter groups ({len(stored)}) differ from the running optimiser's "
+              f"({len(_group_entries(optimizer, params, index))}): keeping the running lr scales and weight decays", file=sys.stderr)
 
 
 def save_checkpoint(path: str, model, args, *, optimizer=None, lr_scheduler_state: Optional[dict] = None, num_updates: int = 0,

@@ -40,6 +40,21 @@ __device__ __forceinline__ void ema_update(float* __restrict__ ema, int64_t i, f
   ema[i] = d == 0.0f ? p : e;
 }
 
+// Parameter groups of the `_group(s)` entry points (include/mdt_hip.h: mdt_adam_group).  GROUPS = false: an empty argument, the
+// kernels without groups.  GROUPS = true: the tensor's record replaces the launch's hyper-parameters, once per tensor (per chunk
+// in the table form): lr_t = lr * lr_scale and step_size_t = step_size * lr_scale, one fp32 product each, the second AFTER
+// adam_scale_and_step so that the guard's own step size is scaled as well; wd_t = weight_decay of the record.
+template <bool GROUPS> struct GroupOne {};
+template <> struct GroupOne<true> { mdt_adam_group g; };
+template <bool GROUPS> struct GroupTable {};
+template <> struct GroupTable<true> { const mdt_adam_group* groups; };      // one record per table entry, by TENSOR
+
+__device__ __forceinline__ void group_hyper(const mdt_adam_group g, float& lr, float& wd, float& step_size) {
+  lr = lr * g.lr_scale;
+  step_size = step_size * g.lr_scale;
+  wd = g.weight_decay;
+}
+
 // The Adam update of element i, the one copy both kernels run: loads, arithmetic and stores.  → the fp32 value the weight
 // average follows: what went to the master, or where there is none the parameter as stored.
 template <typename T>
@@ -59,14 +74,15 @@ __device__ __forceinline__ float adam_element(int64_t i, const float* grad, floa
   return master ? p : to_f32(stored);
 }
 
-template <typename T, bool GUARD, bool EMA>
+template <typename T, bool GUARD, bool EMA, bool GROUPS>
 __global__ __launch_bounds__(256) void adam_kernel(int64_t n, T* __restrict__ param, float* __restrict__ master,
                                                    const float* __restrict__ grad, float* __restrict__ m,
                                                    float* __restrict__ v, float lr, float beta1, float beta2, float eps,
                                                    float wd, float step_size, const float* __restrict__ grad_scale,
-                                                   const mdt_adam_guard* __restrict__ guard, EmaOne<EMA> ea) {
+                                                   const mdt_adam_guard* __restrict__ guard, EmaOne<EMA> ea, GroupOne<GROUPS> ga) {
   float gs;
   if (!adam_scale_and_step<GUARD>(grad_scale, guard, gs, step_size)) return;
+  if constexpr (GROUPS) group_hyper(ga.g, lr, wd, step_size);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float p = adam_element(i, grad, m, v, master, param, lr, beta1, beta2, eps, wd, gs, step_size);
     if constexpr (EMA) ema_update(ea.ema, i, ea.decay, p);
@@ -98,12 +114,13 @@ __device__ __forceinline__ ChunkAt chunk_at(const int64_t* __restrict__ chunk_fi
 // Multi-tensor form: one launch walks a device table of tensors (the ~400 parameter tensors of mDT would otherwise
 // cost ~400 launches of 10-20 us each).  Block b works on chunk b of 4096 elements; `chunk_first[t]` is the first
 // chunk of tensor t (monotone, chunk_first[n] = total), found by binary search.
-template <typename T, bool GUARD, bool EMA>
+template <typename T, bool GUARD, bool EMA, bool GROUPS>
 __global__ __launch_bounds__(256) void adam_multi_kernel(int n_tensors, const mdt_adam_tensor* __restrict__ tab,
                                                          const int64_t* __restrict__ chunk_first, float lr, float beta1,
                                                          float beta2, float eps, float wd, float step_size,
                                                          const float* __restrict__ grad_scale,
-                                                         const mdt_adam_guard* __restrict__ guard, EmaTable<EMA> ea) {
+                                                         const mdt_adam_guard* __restrict__ guard, EmaTable<EMA> ea,
+                                                         GroupTable<GROUPS> ga) {
   float gs;
   if (!adam_scale_and_step<GUARD>(grad_scale, guard, gs, step_size)) return;
   const int64_t total = chunk_first[n_tensors];
@@ -113,11 +130,13 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(int n_tensors, const md
     const int64_t base = at.base();
     float* ema = nullptr;
     if constexpr (EMA) ema = ea.ema[at.tensor];
+    float lr_t = lr, wd_t = wd, step_size_t = step_size;
+    if constexpr (GROUPS) group_hyper(ga.groups[at.tensor], lr_t, wd_t, step_size_t);
 #pragma unroll 4
     for (int k = 0; k < 16; ++k) {
       const int64_t i = base + k * 256 + threadIdx.x;
       if (i >= t.numel) break;
-      const float p = adam_element(i, t.grad, t.m, t.v, t.master, (T*)t.param, lr, beta1, beta2, eps, wd, gs, step_size);
+      const float p = adam_element(i, t.grad, t.m, t.v, t.master, (T*)t.param, lr_t, beta1, beta2, eps, wd_t, gs, step_size_t);
       if constexpr (EMA) {
         if (ema) ema_update(ema, i, ea.decay, p);
       }
@@ -294,11 +313,11 @@ static float adam_step_size(float lr, float beta1, float beta2, int step) {
   return (float)(lr * sqrt(bc2) / bc1);
 }
 
-template <bool GUARD, bool EMA = false>
+template <bool GUARD, bool EMA = false, bool GROUPS = false>
 static int adam_step_multi(const char* what, void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
                            const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2, float eps,
                            float weight_decay, int step, const float* grad_scale, const mdt_adam_guard* guard,
-                           EmaTable<EMA> ea = {}) {
+                           EmaTable<EMA> ea = {}, GroupTable<GROUPS> ga = {}) {
   if (n_tensors == 0 || total_chunks == 0) return MDT_OK;
   MDT_CHECK_ARG(table_dev && chunk_first_dev && step >= 1 && (!GUARD || guard), "%s: bad arguments", what);
   if constexpr (EMA) MDT_CHECK_ARG(ea.ema && ea.decay >= 0.0f && ea.decay <= 1.0f, "%s: ema_dev is NULL or ema_decay is outside [0, 1]", what);
@@ -306,15 +325,15 @@ static int adam_step_multi(const char* what, void* stream, int dtype, int n_tens
   hipStream_t st = (hipStream_t)stream;
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return launch_plain<adam_multi_kernel<T, GUARD, EMA>>(what, chunk_grid(total_chunks), 256, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps, weight_decay,
-                                                          step_size, grad_scale, guard, ea);
+    return launch_plain<adam_multi_kernel<T, GUARD, EMA, GROUPS>>(what, chunk_grid(total_chunks), 256, st, n_tensors, table_dev, chunk_first_dev, lr, beta1, beta2, eps,
+                                                                  weight_decay, step_size, grad_scale, guard, ea, ga);
   });
 }
 
-template <bool GUARD, bool EMA = false>
+template <bool GUARD, bool EMA = false, bool GROUPS = false>
 static int adam_step_one(const char* what, void* stream, int dtype, int64_t n, void* param, float* master, const float* grad,
                          float* m, float* v, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                         const float* grad_scale, const mdt_adam_guard* guard, EmaOne<EMA> ea = {}) {
+                         const float* grad_scale, const mdt_adam_guard* guard, EmaOne<EMA> ea = {}, GroupOne<GROUPS> ga = {}) {
   if (n == 0) return MDT_OK;
   MDT_CHECK_ARG(param && grad && m && v && step >= 1 && (!GUARD || guard), "%s: bad arguments", what);
   if constexpr (EMA) MDT_CHECK_ARG(ea.ema && ea.decay >= 0.0f && ea.decay <= 1.0f, "%s: ema is NULL or ema_decay is outside [0, 1]", what);
@@ -323,8 +342,8 @@ static int adam_step_one(const char* what, void* stream, int dtype, int64_t n, v
   hipStream_t st = (hipStream_t)stream;
   return with_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    return launch_plain<adam_kernel<T, GUARD, EMA>>(what, grid, 256, st, n, (T*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay, step_size,
-                                                    grad_scale, guard, ea);
+    return launch_plain<adam_kernel<T, GUARD, EMA, GROUPS>>(what, grid, 256, st, n, (T*)param, master, grad, m, v, lr, beta1, beta2, eps, weight_decay,
+                                                            step_size, grad_scale, guard, ea, ga);
   });
 }
 
@@ -385,6 +404,42 @@ extern "C" int mdt_adam_step_ema_guarded(void* stream, int dtype, int64_t n, voi
                                          int step, const mdt_adam_guard* guard, float* ema, float ema_decay) {
   return adam_step_one<true, true>("adam_step_ema_guarded", stream, dtype, n, param, master, grad, m, v, lr, beta1, beta2, eps,
                                    weight_decay, step, nullptr, guard, {ema, ema_decay});
+}
+
+// The group forms (include/mdt_hip.h): per-tensor lr scale and weight decay; the guard and the average are nullable arguments.
+extern "C" int mdt_adam_step_multi_groups(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev,
+                                          const int64_t* chunk_first_dev, int64_t total_chunks, float lr, float beta1, float beta2,
+                                          float eps, int step, const mdt_adam_group* groups_dev, const float* grad_scale,
+                                          const mdt_adam_guard* guard, float* const* ema_dev, float ema_decay) {
+  const char* what = "adam_step_multi_groups";
+  MDT_CHECK_ARG(!(grad_scale && guard), "%s: grad_scale and guard are both given (the guard state carries the scale)", what);
+  MDT_CHECK_ARG(groups_dev, "%s: groups_dev is NULL (mdt_adam_step_multi* are the forms without groups)", what);
+  const GroupTable<true> ga{groups_dev};
+  const EmaTable<true> ea{ema_dev, ema_decay};
+#define MDT_ADAM_GROUPS(G, E, ...) \
+  adam_step_multi<G, E, true>(what, stream, dtype, n_tensors, table_dev, chunk_first_dev, total_chunks, lr, beta1, beta2, eps, 0.0f, step, \
+                              grad_scale, guard, __VA_ARGS__, ga)
+  if (guard) return ema_dev ? MDT_ADAM_GROUPS(true, true, ea) : MDT_ADAM_GROUPS(true, false, EmaTable<false>{});
+  return ema_dev ? MDT_ADAM_GROUPS(false, true, ea) : MDT_ADAM_GROUPS(false, false, EmaTable<false>{});
+#undef MDT_ADAM_GROUPS
+}
+
+extern "C" int mdt_adam_step_group(void* stream, int dtype, int64_t n, void* param, float* master, const float* grad, float* m,
+                                   float* v, float lr, float beta1, float beta2, float eps, int step, float lr_scale,
+                                   float weight_decay, const float* grad_scale, const mdt_adam_guard* guard, float* ema,
+                                   float ema_decay) {
+  const char* what = "adam_step_group";
+  MDT_CHECK_ARG(!(grad_scale && guard), "%s: grad_scale and guard are both given (the guard state carries the scale)", what);
+  MDT_CHECK_ARG(std::isfinite(lr_scale) && lr_scale >= 0.0f && std::isfinite(weight_decay) && weight_decay >= 0.0f,
+                "%s: lr_scale %g and weight_decay %g must be finite and >= 0", what, (double)lr_scale, (double)weight_decay);
+  const GroupOne<true> ga{{lr_scale, weight_decay}};
+  const EmaOne<true> ea{ema, ema_decay};
+#define MDT_ADAM_GROUP(G, E, ...) \
+  adam_step_one<G, E, true>(what, stream, dtype, n, param, master, grad, m, v, lr, beta1, beta2, eps, 0.0f, step, grad_scale, guard, \
+                            __VA_ARGS__, ga)
+  if (guard) return ema ? MDT_ADAM_GROUP(true, true, ea) : MDT_ADAM_GROUP(true, false, EmaOne<false>{});
+  return ema ? MDT_ADAM_GROUP(false, true, ea) : MDT_ADAM_GROUP(false, false, EmaOne<false>{});
+#undef MDT_ADAM_GROUP
 }
 
 extern "C" int mdt_ema_swap_multi(void* stream, int dtype, int n_tensors, const mdt_adam_tensor* table_dev, float* const* ema_dev,

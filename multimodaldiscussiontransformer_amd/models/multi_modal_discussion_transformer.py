@@ -107,6 +107,46 @@ class GraphormerModel(FairseqEncoderModel):
     def forward(self, batched_data, **kwargs):
         return self.encoder(batched_data, **kwargs)
 
+    # ---- optimiser parameter groups -----------------------------------------------------------
+    def encoder_layer_ids(self):
+        """{id(parameter): (layer id, L)} for the parameters of the two PRETRAINED encoders.  Per encoder of full depth L
+        (``bert_config["layers"]`` / ``vit_config["layers"]``): its embeddings (ViT: patch projection, [CLS], position table)
+        have id 0 and the block with original index i has id i + 1, whether it stayed in the truncated ``text_model`` /
+        ``vit_model`` prefix or was sliced out into a GraphFusionStack.  Poolers and ViT's final LayerNorm are not listed."""
+        ge = self.encoder.graph_encoder
+        out = {}
+        for enc, cfg, side in ((ge.text_model, ge.bert_config, "bert_encoder"), (ge.vit_model, ge.vit_config, "vit_encoder")):
+            depth = int(cfg["layers"])
+            blocks = list(enc.encoder.layer) + [getattr(fl, side) for st in ge.fusion_layers for fl in st.fusion_layers]
+            assert len(blocks) == depth, f"{side}: {len(blocks)} blocks found, the encoder has {depth}"
+            for p in enc.embeddings.parameters():
+                out[id(p)] = (0, depth)
+            for i, blk in enumerate(blocks):
+                for p in blk.parameters():
+                    out[id(p)] = (i + 1, depth)
+        return out
+
+    def optimizer_groups(self, encoder_lr_scale=1.0, encoder_layer_decay=1.0, no_decay_bias_norm=False, weight_decay=0.01):
+        """The parameter groups for FusedAdam: ``[{"params", "lr_scale", "weight_decay"}]``, one per distinct pair in
+        ``parameters()`` order of first appearance, every trainable parameter exactly once (frozen ones in none).
+        A pretrained-encoder parameter of layer id ``k`` (encoder_layer_ids) gets lr_scale =
+        ``encoder_lr_scale * encoder_layer_decay ** (L + 1 - k)``: the last block runs at scale x decay, the embeddings at
+        scale x decay^(L + 1).  Everything else — poolers, ViT's final LayerNorm, graph stacks, structural-bias tables, bottleneck
+        tokens, fusion projections, classifier, the dead head parameters — has scale 1.  ``no_decay_bias_norm``: weight decay 0 for
+        parameters with ``ndim <= 1``.  Reads module structure only: runs on the CPU."""
+        ids = self.encoder_layer_ids()
+        groups = {}
+        for p in self.parameters():
+            if not p.requires_grad:
+                continue
+            scale = 1.0
+            if id(p) in ids:
+                k, depth = ids[id(p)]
+                scale = float(encoder_lr_scale) * float(encoder_layer_decay) ** (depth + 1 - k)
+            wd = 0.0 if (no_decay_bias_norm and p.ndim <= 1) else float(weight_decay)
+            groups.setdefault((scale, wd), {"params": [], "lr_scale": scale, "weight_decay": wd})["params"].append(p)
+        return list(groups.values())
+
     # ---- fp32 gradient arena ----------------------------------------------------------------
     def prepare_main_grads(self):
         """Give every trainable parameter an fp32 ``main_grad`` view into one flat buffer (reverse

@@ -10,7 +10,13 @@ synchronises with the host.
 
 ``ema_decay`` (FairSeq ``--store-ema``) keeps an fp32 exponential moving average of the weights in one flat arena.  The
 average is updated by the Adam launch itself (the ``_ema`` entry points: the fresh fp32 value is in a register, a skipped
-update leaves the average alone); ``ema_weights()`` swaps it into the working parameters for an evaluation and back."""
+update leaves the average alone); ``ema_weights()`` swaps it into the working parameters for an evaluation and back.
+
+Parameter groups (torch-style ``[{"params": [...], "lr_scale": 0.5, "weight_decay": 0.0}, ...]``) give a tensor its own rate
+scale and weight decay inside the SAME launches: a float32 ``[n, 2]`` device array parallel to the table (include/mdt_hip.h:
+mdt_adam_group) and the ``_groups`` / ``_group`` entry points.  The norm pass, the guard and the EMA arena are shared by all
+groups; an optimiser whose parameters all have (1, the constructor's weight decay) issues exactly the entry points of one
+without groups."""
 from __future__ import annotations
 
 import contextlib
@@ -31,6 +37,7 @@ class Table(NamedTuple):
     params: list
     grad_ptrs: list                        # the gradient address each record was built from (0: a table without gradients)
     ema_ptrs: Optional[torch.Tensor]       # int64 [n] on the device: the averages in table order (None: no average is kept)
+    groups: Optional[torch.Tensor] = None  # float32 [n, 2] on the device: (lr_scale, weight_decay) per tensor (None: all trivial)
 
 
 class FusedAdam:
@@ -43,11 +50,29 @@ class FusedAdam:
         ``k`` (``num_updates`` of ``step``, by default the count of ``step`` calls) with ``k % ema_update_freq == 0`` also
         does ``ema = d ema + (1 - d) p`` in the Adam kernel, d = 0 while ``k < ema_start_update`` (FairSeq: the average is
         a copy of the weights until then) and ``ema_decay`` afterwards; every other update is the plain launch."""
+        params = list(params)
+        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self._hyper = {}                          # id(parameter) -> (lr_scale, weight_decay) where a group was given
+        self._has_groups = (None, False)          # (the weight decay it was worked out for, has_groups)
+        if params and isinstance(params[0], dict):
+            flat = []
+            for k, g in enumerate(params):
+                unknown = set(g) - {"params", "lr_scale", "weight_decay"}
+                if unknown or "params" not in g:
+                    raise ValueError(f"FusedAdam: group {k} has unknown keys {sorted(unknown)} or no 'params' (params, lr_scale, weight_decay)")
+                scale, wd = float(g.get("lr_scale", 1.0)), float(g.get("weight_decay", weight_decay))
+                if not (np.isfinite(scale) and scale >= 0.0 and np.isfinite(wd) and wd >= 0.0):
+                    raise ValueError(f"FusedAdam: group {k}: lr_scale {scale!r} and weight_decay {wd!r} must be finite and >= 0")
+                for p in g["params"]:
+                    if id(p) in self._hyper:
+                        raise ValueError(f"FusedAdam: a parameter of shape {tuple(p.shape)} appears in more than one group (group {k})")
+                    self._hyper[id(p)] = (scale, wd)
+                    flat.append(p)
+            params = flat
         self.params = [p for p in params if p.requires_grad]
         self.clip_norm = None if clip_norm is None else float(clip_norm)
         self.norm_launches = 0                    # sum-of-squares and finaliser launches issued so far (tests)
         self._guard = self._partials = None
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.step_count = 0
         self.multi_tensor = multi_tensor          # False: one launch per tensor (tests compare the two)
         self.state = {}
@@ -80,6 +105,35 @@ class FusedAdam:
         st = self.state[id(p)]
         return st["master"] if "master" in st else p.detach().float()
 
+    def hyper_of(self, p):
+        """(lr_scale, weight_decay) of parameter ``p``: its group's, or (1, the optimiser's weight decay)."""
+        return self._hyper.get(id(p), (1.0, float(self.weight_decay)))
+
+    def _grouped(self, p):
+        """True where ``p`` needs the group entry points: the fp32 numbers the kernel would get differ from (1, global)."""
+        scale, wd = self.hyper_of(p)
+        return np.float32(scale) != np.float32(1.0) or np.float32(wd) != np.float32(self.weight_decay)
+
+    @property
+    def has_groups(self):
+        """True where any parameter differs from (1, the optimiser's weight decay): the step then issues the group entry points."""
+        key = float(self.weight_decay)
+        if self._has_groups[0] != key:
+            self._has_groups = (key, any(self._grouped(p) for p in self.params))
+        return self._has_groups[1]
+
+    @property
+    def param_groups(self):
+        """torch-style view: one dict per distinct (lr_scale, weight_decay) in order of first appearance, ``lr`` = base x scale."""
+        out = {}
+        for p in self.params:
+            key = self.hyper_of(p)
+            if key not in out:
+                out[key] = {"params": [], "lr": self.lr * key[0], "lr_scale": key[0], "weight_decay": key[1],
+                            "betas": tuple(self.betas), "eps": self.eps}
+            out[key]["params"].append(p)
+        return list(out.values())
+
     def _build_tables(self, params, with_grads):
         """{dtype: Table} over ``params`` in their order; ``with_grads``: the records point at ``p.main_grad``."""
         groups = {}
@@ -99,7 +153,10 @@ class FusedAdam:
             ema = None
             if self.ema_decay is not None:
                 ema = torch.from_numpy(np.asarray([self.state[id(p)]["ema"].data_ptr() for p in ps], dtype=np.int64)).to(dev)
-            tab[dtype] = Table(torch.from_numpy(rec).to(dev), torch.from_numpy(first).to(dev), len(ps), int(first[-1]), ps, gptrs, ema)
+            grp = None
+            if with_grads and any(self._grouped(p) for p in ps):
+                grp = torch.from_numpy(np.asarray([self.hyper_of(p) for p in ps], dtype=np.float32).reshape(len(ps), 2)).to(dev)
+            tab[dtype] = Table(torch.from_numpy(rec).to(dev), torch.from_numpy(first).to(dev), len(ps), int(first[-1]), ps, gptrs, ema, grp)
         return tab
 
     def _tables(self):
@@ -200,19 +257,27 @@ class FusedAdam:
         hyper = (float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.step_count)
         for t in tables.values():
             self._adam(True, (stream(), dt(t.params[0]), t.n, ptr(t.rec), ptr(t.first), t.total, *hyper), grad_scale, guard,
-                       () if ema is None else (ptr(t.ema_ptrs), ema))
+                       () if ema is None else (ptr(t.ema_ptrs), ema), None if t.groups is None else (ptr(t.groups),))
+        grouped = self.has_groups               # then every per-tensor launch is the group form, trivial records included
         for p, g in rest:
             st = self.state[id(p)]
             self._adam(False, (stream(), dt(p), p.numel(), ptr(p.data), ptr(st.get("master")), ptr(g), ptr(st["m"]), ptr(st["v"]), *hyper),
-                       grad_scale, guard, () if ema is None else (ptr(st["ema"]), ema))
+                       grad_scale, guard, () if ema is None else (ptr(st["ema"]), ema), self.hyper_of(p) if grouped else None)
         from . import engine
         engine.weights_changed()                 # copies derived from the weights (engine._k_padded, fp8.Fp8State.weight) are stale now
 
     @staticmethod
-    def _adam(multi, head, grad_scale, guard, ema_tail):
+    def _adam(multi, head, grad_scale, guard, ema_tail, group=None):
         """One Adam launch.  ``head``: the arguments up to ``step``; then the guard state where there is one, else the optional
-        gradient scale; then ``ema_tail`` (averages, decay) or nothing.  The entry point is looked up in ``lib`` by its name, at
-        the call."""
+        gradient scale; then ``ema_tail`` (averages, decay) or nothing.  ``group``: None, or what the group form takes after
+        ``step`` — (records,) of a table, (lr_scale, weight_decay) of one tensor; that form has the global weight decay taken
+        out of ``head`` and both of gradient scale and guard, averages and decay as nullable arguments.  The entry point is
+        looked up in ``lib`` by its name, at the call."""
+        if group is not None:
+            name = "mdt_adam_step_multi_groups" if multi else "mdt_adam_step_group"
+            check(getattr(lib, name)(*head[:-2], head[-1], *group, ptr(grad_scale) if guard is None else None, ptr(guard),
+                                     *(ema_tail or (None, 0.0))), name)
+            return
         name = "mdt_adam_step" + ("_multi" if multi else "") + ("_ema" if ema_tail else "") + ("" if guard is None else "_guarded")
         check(getattr(lib, name)(*head, ptr(grad_scale if guard is None else guard), *ema_tail), name)
 

@@ -21,6 +21,7 @@ from __future__ import annotations
 import argparse
 import ast
 import json
+import math
 import os
 import sys
 import time
@@ -76,6 +77,15 @@ def build_parser():
     p.add_argument("--validate-with-ema", action="store_true", default=None,
                    help="not a FairSeq flag: run the validation passes with the averaged weights (FusedAdam.ema_weights) — the validation "
                         "log line then carries \"weights\": \"ema\"")
+    # parameter groups of the fused Adam step (not reference flags): GraphormerModel.optimizer_groups
+    p.add_argument("--encoder-lr-scale", type=float, default=1.0,
+                   help="not a reference flag: learning-rate scale of the pretrained BERT / ViT embeddings and blocks (finite, >= 0; 0 freezes "
+                        "them while their Adam moments advance)")
+    p.add_argument("--encoder-layer-decay", type=float, default=1.0,
+                   help="not a reference flag: layer-wise rate decay G in (0, 1] down the pretrained stacks — the block with original index i "
+                        "of a depth-L encoder runs at --encoder-lr-scale * G^(L - i), its embeddings at G^(L + 1)")
+    p.add_argument("--no-decay-bias-norm", action="store_true", default=False,
+                   help="not a reference flag: weight decay 0 for biases and LayerNorm weights (every parameter with ndim <= 1)")
     p.add_argument("--log-interval", type=int, default=10)
     # criterion flags: every field of every registered criterion's config dataclass (FairSeq derives them the same way)
     from .registry import CRITERION_REGISTRY as _CR
@@ -180,6 +190,16 @@ def main(argv=None):
     if not store_ema:
         for f in ["store_ema"] + ema_names:      # a run without the average writes the checkpoint (its cfg included) it always wrote
             delattr(args, f)
+    if not (math.isfinite(args.encoder_lr_scale) and args.encoder_lr_scale >= 0.0):
+        raise SystemExit("[mdt-train] --encoder-lr-scale must be finite and >= 0")
+    if not (math.isfinite(args.encoder_layer_decay) and 0.0 < args.encoder_layer_decay <= 1.0):
+        raise SystemExit("[mdt-train] --encoder-layer-decay must be finite and lie in (0, 1]")
+    group_flags = dict(encoder_lr_scale=args.encoder_lr_scale, encoder_layer_decay=args.encoder_layer_decay,
+                       no_decay_bias_norm=bool(args.no_decay_bias_norm))
+    use_groups = group_flags != dict(encoder_lr_scale=1.0, encoder_layer_decay=1.0, no_decay_bias_norm=False)
+    if not use_groups:
+        for f in group_flags:                    # flags left at their defaults: the optimiser, the log lines and the checkpoint cfg of a run without them
+            delattr(args, f)
     from . import engine
     was_deterministic = engine.deterministic()
     if args.deterministic:
@@ -225,10 +245,22 @@ def main(argv=None):
     crit_cls, _ = CRITERION_REGISTRY[args.criterion]
     crit = crit_cls.build_criterion(args, task)      # constructor arguments by name from the flags, as FairSeq does
     betas = ast.literal_eval(args.adam_betas) if isinstance(args.adam_betas, str) else args.adam_betas
-    opt = FusedAdam([p for p in model.parameters() if hasattr(p, "main_grad")], lr=args.lr, betas=betas, eps=args.adam_eps,
+    opt_params = [p for p in model.parameters() if hasattr(p, "main_grad")]
+    if use_groups:
+        opt_params = [dict(g, params=[p for p in g["params"] if hasattr(p, "main_grad")])
+                      for g in model.optimizer_groups(weight_decay=args.weight_decay, **group_flags)]
+        opt_params = [g for g in opt_params if g["params"]]
+    opt = FusedAdam(opt_params, lr=args.lr, betas=betas, eps=args.adam_eps,
                     weight_decay=args.weight_decay, clip_norm=args.clip_norm,     # the norm pass and the guard are always on, as in FairSeq
                     **(dict(ema_decay=args.ema_decay, ema_start_update=args.ema_start_update, ema_update_freq=args.ema_update_freq)
                        if store_ema else {}))
+    min_scale = None
+    if use_groups:
+        min_scale = min(g["lr_scale"] for g in opt.param_groups)
+        if rank == 0:
+            print(json.dumps(dict(optimizer_groups=[dict(tensors=len(g["params"]), elements=sum(p.numel() for p in g["params"]),
+                                                         lr_scale=g["lr_scale"], weight_decay=g["weight_decay"])
+                                                    for g in opt.param_groups])), flush=True)
     sched = PolynomialDecayLR(args.lr, args.end_learning_rate, args.warmup_updates, args.total_num_update, args.power)
     from . import checkpoint as ckpt
     start_update, epoch0 = 0, 1
@@ -425,6 +457,8 @@ def main(argv=None):
             # FairSeq's meters: gnorm of this update, clip = per cent of the updates since the previous line that were clipped
             m.update(num_updates=upd, lr=lr_for(upd), gnorm=g["gnorm"], clip=100.0 * (g["clipped"] - meter["clipped"]) / (upd - meter["upd"]),
                      skipped_updates=g["skipped"], wall=round(time.time() - t0, 2))
+            if min_scale is not None:
+                m["lr_min"] = lr_for(upd) * min_scale              # the smallest group rate of this update
             meter.update(upd=upd, clipped=g["clipped"])
             history.append(m)
             if rank == 0:
