@@ -165,6 +165,16 @@ int mdt_layernorm_bwd(void* stream, int dtype, int64_t rows, int D, const void* 
  * out[row, h*hd:(h+1)*hd] = P @ v.  lse[s,h,p] (fp32) is saved for backward.
  * Head widths: hd = 16, 64, 96 or 128, in fp32 and in bf16 (any S; seq_ids / s_cap launches: bf16, hd = 64 only).
  *
+ * Row tensors.  qkv / ld_qkv, out / ld_out, dout / ld_dout and dqkv / ld_dqkv are four independent (base, row stride in
+ * elements) pairs; a stride is at least the row's width (3 D for qkv and dqkv, D for out and dout), and the columns past the
+ * width are neither read nor written.  bf16: the kernels move all four in 16-byte vectors, so every base is 16-byte aligned and
+ * every row stride a multiple of 8 elements.  fp32: every kernel family (v1, the key-chunked path, the weight outputs) moves
+ * one element at a time — any row stride, the base on a 4-byte boundary.  Anything else is MDT_ERR_ARG with the
+ * tensor's name in the message, from the launch and from mdt_attention_route alike.  Writes: rows of the launch's sequences
+ * below their length, columns below the width; lse[s, h, 0 .. S) of those sequences; nothing else — not the rows between two
+ * sequences (seq_stride > S), not a sequence that seq_ids does not name, not a byte outside d_dense_bias [nseq,H,S,S],
+ * d_sp_table [num_spatial,H] or d_virt [H].
+ *
  * Bias / mask sources, all optional (NULL):
  *   key_mask   u8[nseq,S]   1 = key may be attended (HF additive mask, quirk 9 of
  *                           −65504 / finfo.min ≡ excluded)

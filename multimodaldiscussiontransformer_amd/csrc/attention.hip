@@ -695,14 +695,28 @@ int attention_v1_launch(hipStream_t st, const AttnParams& p, const AttnPlan& pl)
   }); }); });
 }
 
+// The widest global access any kernel family makes to a row tensor decides what its base and row stride must be (the rule of
+// include/mdt_hip.h).  bf16: 16-byte vectors — qkv and dout in the image loaders and fragment loads of v1 .. v5, out in the v2
+// forward's row stores and the one-pass backwards' loads, dqkv in rows4_store (row_piece: 8 bytes) — so base and row pitch
+// are multiples of 16 bytes.  fp32 (v1, the key-chunked path, head weights): one element at a time, any row stride; the base
+// on an element boundary.  The head offset h * hd and the D | 2 D thirds keep either alignment (hd is a multiple of 16).
+static bool attn_rows_aligned(int dtype, const void* base, int64_t ld) {
+  return dtype == MDT_BF16 ? (ld % 8 == 0 && ((uintptr_t)base & 15) == 0) : ((uintptr_t)base & 3) == 0;
+}
+
 static int check_args(const mdt_attn_fwd_args& a) {
   MDT_CHECK_ARG(a.dtype == MDT_F32 || a.dtype == MDT_BF16, "attention: bad dtype %d", a.dtype);
   MDT_CHECK_ARG(a.nseq >= 0 && a.S > 0 && a.H > 0 && a.hd > 0, "attention: bad shape nseq=%d S=%d H=%d hd=%d", a.nseq,
                 a.S, a.H, a.hd);
   MDT_CHECK_ARG(a.qkv && a.out && a.lse, "attention: null qkv / out / lse");
   MDT_CHECK_ARG(a.ld_qkv >= 3 * a.H * a.hd && a.ld_out >= a.H * a.hd, "attention: row strides too small");
-  if (a.dtype == MDT_BF16)
-    MDT_CHECK_ARG(a.ld_qkv % 8 == 0 && ((uintptr_t)a.qkv & 15) == 0, "attention(bf16): qkv must be 16-byte aligned rows");
+  if (a.dtype == MDT_BF16) {
+    MDT_CHECK_ARG(attn_rows_aligned(a.dtype, a.qkv, a.ld_qkv), "attention(bf16): qkv must be 16-byte aligned rows");
+    MDT_CHECK_ARG(attn_rows_aligned(a.dtype, a.out, a.ld_out), "attention(bf16): out must be 16-byte aligned rows");
+  } else {
+    MDT_CHECK_ARG(attn_rows_aligned(a.dtype, a.qkv, a.ld_qkv), "attention(fp32): qkv must be 4-byte aligned");
+    MDT_CHECK_ARG(attn_rows_aligned(a.dtype, a.out, a.ld_out), "attention(fp32): out must be 4-byte aligned");
+  }
   if (a.attn_bias) MDT_CHECK_ARG(a.spatial_pos && a.sp_table && a.virt && a.num_spatial > 0, "attention: incomplete structural bias");
   MDT_CHECK_ARG(a.drop_p >= 0.f && a.drop_p < 1.f, "attention: dropout p=%f out of [0,1)", a.drop_p);
   if (a.seq_offsets)
@@ -725,8 +739,14 @@ static int checked_params(const mdt_attn_fwd_args& f, const mdt_attn_bwd_args* b
   if (!b) return MDT_OK;
   MDT_CHECK_ARG(b->dout && b->dqkv, "attention_bwd: null dout / dqkv");
   MDT_CHECK_ARG(b->ld_dqkv >= 3 * f.H * f.hd, "attention_bwd: ld_dqkv too small");
-  if (f.dtype == MDT_BF16)
-    MDT_CHECK_ARG(b->ld_dout % 8 == 0 && ((uintptr_t)b->dout & 15) == 0, "attention_bwd(bf16): dout must be 16-byte aligned rows");
+  MDT_CHECK_ARG(b->ld_dout >= f.H * f.hd, "attention_bwd: ld_dout too small");
+  if (f.dtype == MDT_BF16) {
+    MDT_CHECK_ARG(attn_rows_aligned(f.dtype, b->dout, b->ld_dout), "attention_bwd(bf16): dout must be 16-byte aligned rows");
+    MDT_CHECK_ARG(attn_rows_aligned(f.dtype, b->dqkv, b->ld_dqkv), "attention_bwd(bf16): dqkv must be 16-byte aligned rows");
+  } else {
+    MDT_CHECK_ARG(attn_rows_aligned(f.dtype, b->dout, b->ld_dout), "attention_bwd(fp32): dout must be 4-byte aligned");
+    MDT_CHECK_ARG(attn_rows_aligned(f.dtype, b->dqkv, b->ld_dqkv), "attention_bwd(fp32): dqkv must be 4-byte aligned");
+  }
   p.dout = b->dout; p.ld_dout = b->ld_dout; p.dqkv = b->dqkv; p.ld_dqkv = b->ld_dqkv;
   p.d_dense_bias = b->d_dense_bias; p.d_sp_table = b->d_sp_table; p.d_virt = b->d_virt;
   return MDT_OK;

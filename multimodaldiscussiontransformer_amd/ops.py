@@ -163,6 +163,14 @@ def _attn_bins(bins, qkv, H, S):
     return [(ids, cap) for ids, cap in bins if ids.numel() > 0]
 
 
+def _f32_out(out, shape, device):
+    """The caller's contiguous fp32 output of ``shape``, or a fresh one."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    assert out.shape == tuple(shape) and out.dtype == torch.float32 and out.is_contiguous(), f"expected contiguous f32{list(shape)}"
+    return out
+
+
 def attention_route(args, bwd):
     """(route, (g0, g1)) of the launch mdt_attention_fwd / mdt_attention_bwd would make of the argument block ``args``
     (L.AttnBwdArgs; the forward reads args.f only), by mdt_attention_route: nothing is launched and no pointer of the block
@@ -174,8 +182,9 @@ def attention_route(args, bwd):
 
 def attention_fwd(qkv, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None, key_mask=None, dense_bias=None,
                   attn_bias=None, spatial_pos=None, sp_table=None, virt=None, key_pad=None, drop_p=0.0, drop_seed=0,
-                  seq_offsets=None, q_limit=0, bins=None):
+                  seq_offsets=None, q_limit=0, bins=None, out=None, lse=None):
     """qkv [rows, 3*D] → (out [rows, D], lse f32[nseq, H, S]); head widths D // H of 16, 64, 96 and 128, fp32 and bf16.
+    ``out`` / ``lse``: the caller's tensors, used as they are (out with its own row stride) instead of fresh ones.
     ``q_limit`` > 0: only the first q_limit rows of every
     sequence are needed as queries (other rows of out / lse unspecified).  ``seq_offsets`` i32[nseq+1]: ragged sequences
     (sequence s = rows off[s]..off[s+1], at most S of them), see include/mdt_hip.h.  ``bins``: [(seq_ids i32[n], cap), ...]
@@ -186,8 +195,12 @@ def attention_fwd(qkv, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None,
     # kernels dispatched for such a launch read exactly those rows of out / lse and nothing past them
     # (tests/test_kernels_gpu.py::test_attention_backward_never_reads_what_forward_did_not_write); every other kernel family ignores
     # q_limit and writes all rows.  Positions of lse past a ragged sequence's length are never read either.
-    out = torch.empty(qkv.shape[0], D, dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty(nseq, H, S, dtype=torch.float32, device=qkv.device)
+    if out is None:
+        out = torch.empty(qkv.shape[0], D, dtype=qkv.dtype, device=qkv.device)
+    if lse is None:
+        lse = torch.empty(nseq, H, S, dtype=torch.float32, device=qkv.device)
+    assert out.shape == (qkv.shape[0], D) and out.dtype == qkv.dtype, "attention_fwd: out must be [rows, D] of qkv's type"
+    assert lse.shape == (nseq, H, S) and lse.dtype == torch.float32 and lse.is_contiguous(), "attention_fwd: lse must be contiguous f32[nseq, H, S]"
     for ids, cap in _attn_bins(bins, qkv, H, S):
         a = _attn_args(qkv, out, lse, nseq, S, H, None, seq_stride, pos_stride, scale, key_mask, dense_bias, attn_bias, spatial_pos,
                        sp_table, virt, key_pad, drop_p, drop_seed, seq_offsets, q_limit, ids, cap)
@@ -196,9 +209,9 @@ def attention_fwd(qkv, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None,
 
 
 def attention_mean_probs(qkv, lse, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None, key_mask=None, dense_bias=None,
-                         attn_bias=None, spatial_pos=None, sp_table=None, virt=None, key_pad=None):
-    """Head-averaged attention probabilities f32[nseq, S, S] from the qkv buffer and the forward's lse."""
-    out = torch.empty(nseq, S, S, dtype=torch.float32, device=qkv.device)
+                         attn_bias=None, spatial_pos=None, sp_table=None, virt=None, key_pad=None, out=None):
+    """Head-averaged attention probabilities f32[nseq, S, S] from the qkv buffer and the forward's lse (``out``: the caller's)."""
+    out = _f32_out(out, (nseq, S, S), qkv.device)
     a = _attn_args(qkv, qkv, lse, nseq, S, H, None, seq_stride, pos_stride, scale, key_mask, dense_bias, attn_bias, spatial_pos, sp_table,
                    virt, key_pad)
     check(lib.mdt_attention_mean_probs(stream(), C.byref(a), ptr(out)), "mdt_attention_mean_probs")
@@ -206,10 +219,10 @@ def attention_mean_probs(qkv, lse, nseq, S, H, *, seq_stride=None, pos_stride=1,
 
 
 def attention_head_weights(qkv, lse, nseq, S, H, *, raw_scores=False, seq_stride=None, pos_stride=1, scale=None, key_mask=None,
-                           dense_bias=None, attn_bias=None, spatial_pos=None, sp_table=None, virt=None, key_pad=None):
+                           dense_bias=None, attn_bias=None, spatial_pos=None, sp_table=None, virt=None, key_pad=None, out=None):
     """Per-head attention weights f32[nseq, H, S, S]: the softmax probabilities before dropout (needs the forward's ``lse``), or
-    with ``raw_scores`` the scores q k^T * scale + bias with masked keys at -inf (``lse`` may be None)."""
-    out = torch.empty(nseq, H, S, S, dtype=torch.float32, device=qkv.device)
+    with ``raw_scores`` the scores q k^T * scale + bias with masked keys at -inf (``lse`` may be None).  ``out``: the caller's."""
+    out = _f32_out(out, (nseq, H, S, S), qkv.device)
     if lse is None:            # raw scores do not read it; the argument check wants a buffer
         assert raw_scores
         lse = torch.empty(nseq * H * S, dtype=torch.float32, device=qkv.device)
@@ -222,14 +235,19 @@ def attention_head_weights(qkv, lse, nseq, S, H, *, raw_scores=False, seq_stride
 def attention_bwd(dout, qkv, out, lse, nseq, S, H, *, seq_stride=None, pos_stride=1, scale=None, key_mask=None,
                   dense_bias=None, attn_bias=None, spatial_pos=None, sp_table=None, virt=None, key_pad=None,
                   want_dense_dbias=False, d_sp_table=None, d_virt=None, drop_p=0.0, drop_seed=0, seq_offsets=None, q_limit=0,
-                  bins=None):
+                  bins=None, dqkv=None, dbias=None):
+    """→ (dqkv [rows, 3*D], dbias f32[nseq, H, S, S] or None).  ``dqkv`` / ``dbias``: the caller's tensors, used as they are
+    (dqkv with its own row stride; a given dbias asks for the dense bias gradient); what the wrapper zeroes it zeroes in them."""
     D = qkv.shape[1] // 3
     # with q_limit the kernels skip the query rows beyond it: their dQ must read as zero (dK / dV are written for every row)
-    dqkv = torch.empty_like(qkv)
+    if dqkv is None:
+        dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
+    assert dqkv.shape == qkv.shape and dqkv.dtype == qkv.dtype, "attention_bwd: dqkv must have qkv's shape and type"
     if q_limit:
         dqkv[:, :D].zero_()
-    dbias = None
-    if want_dense_dbias:
+    if dbias is not None:
+        dbias = _f32_out(dbias, (nseq, H, S, S), qkv.device).zero_()
+    elif want_dense_dbias:
         dbias = torch.zeros(nseq, H, S, S, dtype=torch.float32, device=qkv.device)
     for ids, cap in _attn_bins(bins, qkv, H, S):
         b = L.AttnBwdArgs()
@@ -244,10 +262,10 @@ def attention_bwd(dout, qkv, out, lse, nseq, S, H, *, seq_stride=None, pos_strid
     return dqkv, dbias
 
 
-def graph_attn_bias(attn_bias, spatial_pos, sp_table, virt):
+def graph_attn_bias(attn_bias, spatial_pos, sp_table, virt, out=None):
     nseq, S, _ = attn_bias.shape
     H = sp_table.shape[1]
-    out = torch.empty(nseq, H, S, S, dtype=torch.float32, device=attn_bias.device)
+    out = _f32_out(out, (nseq, H, S, S), attn_bias.device)
     check(lib.mdt_graph_attn_bias(stream(), dt(sp_table), nseq, S, H, ptr(attn_bias), ptr(spatial_pos), ptr(sp_table),
                                   ptr(virt), ptr(out)), "mdt_graph_attn_bias")
     return out

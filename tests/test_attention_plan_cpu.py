@@ -175,6 +175,55 @@ def test_refusal_messages(ops, force):
         assert e.value.status == -1, e.value
 
 
+def test_row_alignment_of_every_row_tensor(ops, force):
+    """qkv, out, dout and dqkv each get the rule the widest access to them needs (include/mdt_hip.h): in bf16 a base on a
+    16-byte boundary and a row stride of a multiple of 8 elements — out and dqkv are stored in 16-byte vectors as qkv and dout
+    are loaded in them; in fp32, where every kernel moves one element at a time, only the base on an element boundary.
+    Refused blocks name the tensor; they are only ever routed, never launched."""
+    force(None)
+    hd, S = 64, 40
+    D = H * hd
+
+    def shifted(dtype, **fields):
+        b = block(ops, dtype, hd, S, "none", 0.25)
+        for k, v in fields.items():
+            setattr(b.f if k in ("qkv", "ld_qkv", "out", "ld_out") else b, k, v)
+        return b
+
+    whole = {bwd: ops.attention_route(block(ops, BF, hd, S, "none", 0.25), bwd) for bwd in (False, True)}
+    refused = {"ld_out": (dict(ld_out=D + 4), r"attention\(bf16\): out must be 16-byte aligned rows", (False, True)),
+               "out": (dict(out=PTR + 8), r"attention\(bf16\): out must be 16-byte aligned rows", (False, True)),
+               "ld_dqkv": (dict(ld_dqkv=3 * D + 4), r"attention_bwd\(bf16\): dqkv must be 16-byte aligned rows", (True,)),
+               "dqkv": (dict(dqkv=PTR + 8), r"attention_bwd\(bf16\): dqkv must be 16-byte aligned rows", (True,)),
+               "ld_qkv": (dict(ld_qkv=3 * D + 4), r"attention\(bf16\): qkv must be 16-byte aligned rows", (False, True)),
+               "ld_dout": (dict(ld_dout=D + 4), r"attention_bwd\(bf16\): dout must be 16-byte aligned rows", (True,))}
+    for kind, (fields, text, launches) in refused.items():
+        for bwd in launches:
+            with pytest.raises(ops.L.MdtError, match=text) as e:
+                ops.attention_route(shifted(BF, **fields), bwd)
+            assert e.value.status == -1, (kind, e.value)
+    # the backward block's own tensors do not concern the forward
+    assert ops.attention_route(shifted(BF, ld_dqkv=3 * D + 4, dqkv=PTR + 8), False) == whole[False]
+    # + 8 elements and + 16 bytes: accepted, and routed as the contiguous block is
+    for fields in (dict(ld_out=D + 8), dict(ld_dqkv=3 * D + 8), dict(out=PTR + 16, dqkv=PTR + 16),
+                   dict(ld_qkv=3 * D + 8, ld_out=D + 16, ld_dout=D + 24, ld_dqkv=3 * D + 32)):
+        for bwd in (False, True):
+            assert ops.attention_route(shifted(BF, **fields), bwd) == whole[bwd], fields
+    # fp32: any row stride and any element-aligned base; half an element off is refused
+    whole32 = {bwd: ops.attention_route(block(ops, F32, hd, S, "none", 0.25), bwd) for bwd in (False, True)}
+    for fields in (dict(ld_out=D + 4), dict(ld_dqkv=3 * D + 4), dict(out=PTR + 8, dqkv=PTR + 8), dict(ld_out=D + 1, ld_dqkv=3 * D + 3, ld_qkv=3 * D + 1, ld_dout=D + 5),
+                   dict(qkv=PTR + 4, dout=PTR + 12)):
+        for bwd in (False, True):
+            assert ops.attention_route(shifted(F32, **fields), bwd) == whole32[bwd], fields
+    for name, launches in (("qkv", (False, True)), ("out", (False, True)), ("dout", (True,)), ("dqkv", (True,))):
+        for bwd in launches:
+            with pytest.raises(ops.L.MdtError, match=rf"\(fp32\): {name} must be 4-byte aligned"):
+                ops.attention_route(shifted(F32, **{name: PTR + 2}), bwd)
+    # a row stride below the width is refused for dout as for the others
+    with pytest.raises(ops.L.MdtError, match="ld_dout too small"):
+        ops.attention_route(shifted(BF, ld_dout=D - 8), True)
+
+
 def test_fp32_wide_heads_fall_back_to_the_key_chunked_backward(ops, force):
     """The one line of the table the launchers used to hide: fp32, head width 96 | 128, the 17-tile rung (S 209 .. 272),
     structural bias and dropout — the backward takes "long", the forward and every neighbour of that point v1."""
