@@ -580,6 +580,40 @@ int mdt_attn_bias_grad_ordered(void* stream, int nseq, int S, int H, int num_spa
  * unchanged. */
 int64_t mdt_float_atomic_launches(int reset);
 
+/* ------------------------------------------------------------------ low-rank adapters (LoRA) on the fused QKV projection
+ * The three skinny products of an adapter pair A_j [r, D], B_j^T [r, D] beside a frozen weight: one dimension n (the rank, or
+ * |targets| * rank) of 8 ... 192 against ~10^5 token rows.  They replace the PEFT-style eager sequence around an adapted nn.Linear,
+ *     t = x @ A.T;  y = base(x) + scale * (t @ B.T);   autograd: dB = t.T @ dy, dt = dy @ B, dA = dt.T @ x, dx += dt @ A
+ * (the reference fine-tunes every weight and has no counterpart).  Both parameters are stored [n, D], so W below is always a
+ * row-major [n, wide] matrix.  All three are memory-bound: the [R, wide] operand is read once (up_add: read and written once),
+ * the small operand stays in registers / LDS / L2, nothing is staged through global memory or transposed in it.
+ *   dtype MDT_BF16 (v_mfma_f32_16x16x32_bf16, fp32 accumulators) or MDT_F32 (plain fp32 loops: the parity path);
+ *   n a multiple of 8 with 8 <= n <= 192; K / N a positive multiple of 16; bf16 bases and rows on 16-byte boundaries (row strides
+ *   multiples of 8 elements), fp32 ones on 4-byte boundaries; a row stride may exceed the width (column slices of the [R, 3D]
+ *   qkv / dqkv buffers: ld = 3D) and only columns below the width are read or written; R = 0 is a no-op.  Anything else is
+ *   MDT_ERR_ARG with the numbers in the message, before any launch.  One rounding to the stored type per element;
+ *   mdt_last_route(): "lora_down", "lora_up", "lora_wgrad" (bf16), "lora_down_f32", "lora_up_f32", "lora_wgrad_f32".
+ *
+ * mdt_lora_down    T[R, n] = alpha * X[R, K] W[n, K]^T        (t = src A^T;  dt_j = s dqkv[:, c_j : c_j + D] Bt_j^T)
+ * mdt_lora_up_add  Y[R, N] += alpha * T[R, n] W[n, N]         (qkv[:, c_j : c_j + D] += s t_j Bt_j;  dx += dt A): Y is read in its type,
+ *                  the fp32 product joins by one FMA, the sum is rounded once
+ * mdt_lora_wgrad   dW[n, N] (fp32) += alpha * T[R, n]^T X[R, N]   (dBt_j, dA) in a FIXED order and without float atomics: token rows
+ *                  are cut into slabs of mdt_lora_wgrad_slab_rows() rows; the workgroup of (slab, column tile) stores alpha * its fp32
+ *                  partial [n, tile] to slice `slab` of the workspace ([slabs][n][N]) and mdt_sum_slices_f32 adds the slices in
+ *                  ascending order, the old dW last.  Inside a slab the rows are accumulated in ascending 32-row MFMA steps
+ *                  (fp32: one row at a time).  The result is a function of the operands and R alone — the same call in the
+ *                  default and in the deterministic mode.  Workspace: caller-owned, 16-byte aligned, uninitialised;
+ *                  a smaller one is MDT_ERR_INVALID before anything is launched. */
+int mdt_lora_down(void* stream, int dtype, int64_t R, int n, int K, const void* X, int64_t ldx,
+                  const void* W, int64_t ldw, void* T, int64_t ldt, float alpha);
+int mdt_lora_up_add(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt,
+                    const void* W, int64_t ldw, void* Y, int64_t ldy, float alpha);
+int mdt_lora_wgrad_slab_rows(void);
+size_t mdt_lora_wgrad_workspace_bytes(int64_t R, int n, int N);
+int mdt_lora_wgrad(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt,
+                   const void* X, int64_t ldx, float* dW, int64_t lddw, float alpha,
+                   void* workspace, size_t workspace_bytes);
+
 /* ------------------------------------------------------------------ packer (host, C++)
  * Native replacement of preprocess_item + collator (data/pyg_datasets/pre_processing.py:18-69,
  * data/collator.py:69-179): integer tensors are bit-exact with the reference.

@@ -56,11 +56,12 @@ def _model_state_fp32(model, optimizer) -> "OrderedDict[str, torch.Tensor]":
     for k, v in sd.items():
         hit = None
         for ptr0, (p, m) in master.items():
-            # a state-dict entry is the parameter itself or a row slice of a fused q/k/v parameter
+            # a state-dict entry is the parameter itself, a row slice of a fused q/k/v parameter or the transposed row slice of
+            # an adapter's B^T (a strided view): the same view of the master
             beg, end = p.data.data_ptr(), p.data.data_ptr() + p.numel() * p.element_size()
             if beg <= v.data_ptr() < end and v.dtype == p.dtype:
                 off = (v.data_ptr() - beg) // p.element_size()
-                hit = m.view(-1)[off:off + v.numel()].view(v.shape)
+                hit = m.as_strided(tuple(v.shape), tuple(v.stride()), m.storage_offset() + off)
                 break
         out[k] = (hit if hit is not None else v).detach().float().cpu() if v.is_floating_point() else v.detach().cpu()
     return out
@@ -180,9 +181,25 @@ def load_optimizer_state_dict(optimizer, model, osd: dict, criterion=None):
               f"({len(_group_entries(optimizer, params, index))}): keeping the running lr scales and weight decays", file=sys.stderr)
 
 
+def merged_model_state(model, optimizer=None) -> "OrderedDict[str, torch.Tensor]":
+    """The fp32 model state of an adapted model (GraphormerModel.add_lora) with every adapter folded into its projection,
+    W_j + (alpha / r) B_j A_j from the fp32 masters, and the adapter keys removed: the state of a model built without adapters
+    (what ``merge_lora()`` leaves, without touching the live model)."""
+    sd = _model_state_fp32(model, optimizer)
+    for name, m in model.named_modules():
+        if getattr(m, "lora_A", None) is None:
+            continue
+        s = m.lora_alpha / m.lora_rank
+        for t in m.lora_targets:
+            a, b = sd.pop(m._lora_key(name + ".", t, "A")).float(), sd.pop(m._lora_key(name + ".", t, "B")).float()
+            wkey = m._lora_key(name + ".", t, "A")[:-len("lora_A.weight")] + "weight"
+            sd[wkey] = sd[wkey].float() + s * (b @ a)
+    return sd
+
+
 def save_checkpoint(path: str, model, args, *, optimizer=None, lr_scheduler_state: Optional[dict] = None, num_updates: int = 0,
                     criterion_name: str = "GraphPredictionNodeCrossEntropy", epoch: int = 1, extra_state: Optional[dict] = None,
-                    training_time: float = 0.0) -> dict:
+                    training_time: float = 0.0, model_state: Optional[dict] = None) -> dict:
     cfg_model = {k: v for k, v in vars(args).items() if isinstance(v, (int, float, str, bool, type(None), list, tuple, dict))}
     state = {
         "args": None,
@@ -192,7 +209,7 @@ def save_checkpoint(path: str, model, args, *, optimizer=None, lr_scheduler_stat
                 "criterion": {"_name": cfg_model.get("criterion")},
                 "optimizer": {"_name": cfg_model.get("optimizer", "adam")},
                 "lr_scheduler": {"_name": cfg_model.get("lr_scheduler", "polynomial_decay")}},
-        "model": _model_state_fp32(model, optimizer),
+        "model": _model_state_fp32(model, optimizer) if model_state is None else model_state,      # model_state: merged_model_state()
         "criterion": None,
         "optimizer_history": [{"criterion_name": criterion_name, "optimizer_name": "FairseqAdam",
                                "lr_scheduler_state": dict(lr_scheduler_state or {}), "num_updates": int(num_updates)}],
@@ -249,7 +266,10 @@ def load_checkpoint(path: str, model, *, optimizer=None, reset_optimizer: bool =
         for p_, low in swapped:
             low.copy_(p_.data)
             p_.data = low
-    missing = [k for k in res.missing_keys if not k.startswith(tuple(allow_missing_prefixes))]
+    # an adapted model (GraphormerModel.add_lora) may start from a checkpoint of the full model: its adapter keys are reported
+    # in out["missing"], not refused (adapter keys the MODEL lacks are unexpected keys, refused as any other)
+    missing = [k for k in res.missing_keys if not k.startswith(tuple(allow_missing_prefixes))
+               and not k.endswith((".lora_A.weight", ".lora_B.weight"))]
     if strict and (missing or res.unexpected_keys):
         raise RuntimeError(f"{path}: missing keys {missing[:8]}{'...' if len(missing) > 8 else ''}, "
                            f"unexpected keys {list(res.unexpected_keys)[:8]}")

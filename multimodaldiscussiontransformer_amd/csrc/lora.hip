@@ -1,0 +1,428 @@
+// Low-rank adapter (LoRA) products on the fused QKV projection: three skinny GEMMs with one dimension n = |targets| * rank of
+// 8 ... 192 over ~10^5 token rows.  They replace the PEFT-style eager sequence around an adapted nn.Linear
+//     t = x @ A.T;  y = base(x) + scale * (t @ B.T)          and autograd's  dB = t.T @ dy,  dt = dy @ B,  dA = dt.T @ x,  dx += dt @ A
+// (the reference project has no adapters and hence no counterpart).  All three are memory-bound: the big operand ([R, D]) is
+// read once from global memory straight into MFMA fragments (down, up_add) or through one LDS image (wgrad); nothing is staged
+// through HBM and nothing is transposed in memory.
+//   lora_down_bf16_kernel     T^T = W X^T: both operands k-contiguous, 16-byte loads are the fragments; a lane ends up with four
+//                             consecutive T columns of one token (one 8-byte store)
+//   lora_up_add_bf16_kernel   Y^T += W^T T^T: a wave keeps the W fragments of its 64 columns in registers for all its rows; the
+//                             tile rows are interleaved so that a lane owns 16 consecutive Y columns (two 16-byte read-modify-writes)
+//   lora_wgrad_bf16_kernel    dW = T^T X: both operands run along the token axis — 32-token stages of T and X in row-major LDS
+//                             images, fragments by ds_read_b64_tr_b16 (the situation of gemm_wgrad.hip).  A workgroup owns
+//                             (slab of LORA_SLAB token rows, column tile) and stores its fp32 partial [n, tile] with plain stores;
+//                             sum_slices_f32 adds the slabs in ascending order, dW's old value last: no float atomics, the
+//                             result is a function of the operands and R alone.
+// bf16 arithmetic: v_mfma_f32_16x16x32_bf16, fp32 accumulators; n = 8 (or the last 8 of n = 24, ...) is half a 16-row tile fed
+// with zeros.  The fp32 forms are plain loops, one thread per output element: the parity path, not a hot path.
+#include "common.hpp"
+
+namespace mdt {
+
+constexpr int LORA_SLAB = 1024;        // token rows per wgrad slab (mdt_lora_wgrad_slab_rows)
+constexpr int LORA_LDT = 208;          // T stage image: 416-byte rows, 8 consecutive rows start on 8 different 32-byte bank groups
+
+// ------------------------------------------------------------------------------------------------ down
+// A operand = W (rows: the n index), B operand = X (columns: tokens): lane l loads W[t*16 + (l&15)][k0 + 8(l>>4) ..+8] and
+// X[row + (l&15)][the same k].  Accumulator: column l&15 = token, rows 4(l>>4) + reg = four consecutive n indices.
+template <int NT, int MT>
+__global__ __launch_bounds__(256) void lora_down_bf16_kernel(int64_t R, int n, int K, const bf16_t* __restrict__ X, int64_t ldx,
+                                                             const bf16_t* __restrict__ W, int64_t ldw, bf16_t* __restrict__ T,
+                                                             int64_t ldt, float alpha) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, i = lane & 15;
+  const int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * (16 * MT);
+  if (row0 >= R) return;
+  const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  const bf16_t* xp[MT];
+  bool xok[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int64_t r = row0 + m * 16 + i;
+    xok[m] = r < R;
+    xp[m] = X + (xok[m] ? r : 0) * ldx + g * 8;
+  }
+  const bf16_t* wp[NT];
+  bool wok[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int wr = t * 16 + i;
+    wok[t] = wr < n;
+    wp[t] = W + (int64_t)(wok[t] ? wr : 0) * ldw + g * 8;
+  }
+  f32x4 acc[MT][NT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < K; k0 += 32) {
+    const bool kok = k0 + g * 8 < K;           // K is a multiple of 8: a lane's chunk is inside or outside as a whole
+    bf16x8 xf[MT], wf[NT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) xf[m] = (xok[m] && kok) ? *(const bf16x8*)(xp[m] + k0) : zero;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) wf[t] = (wok[t] && kok) ? *(const bf16x8*)(wp[t] + k0) : zero;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[m][t] = mfma_bf16(wf[t], xf[m], acc[m][t]);
+  }
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int64_t r = row0 + m * 16 + i;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int c = t * 16 + 4 * g;            // n is a multiple of 8: c < n implies c + 4 <= n
+      if (r < R && c < n) {
+        const bf16x4 o = {(bf16_t)(alpha * acc[m][t][0]), (bf16_t)(alpha * acc[m][t][1]), (bf16_t)(alpha * acc[m][t][2]),
+                          (bf16_t)(alpha * acc[m][t][3])};
+        *(bf16x4*)(T + r * ldt + c) = o;
+      }
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void lora_down_plain_kernel(int64_t R, int n, int K, const T* __restrict__ X, int64_t ldx,
+                                                              const T* __restrict__ W, int64_t ldw, T* __restrict__ Tm, int64_t ldt,
+                                                              float alpha) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= R * n) return;
+  const int64_t r = e / n;
+  const int i = (int)(e - r * n);
+  const T* x = X + r * ldx;
+  const T* w = W + (int64_t)i * ldw;
+  float s = 0.f;
+  for (int k = 0; k < K; ++k) s += to_f32(x[k]) * to_f32(w[k]);
+  Tm[r * ldt + i] = from_f32<T>(alpha * s);
+}
+
+// ------------------------------------------------------------------------------------------------ up_add
+// A operand = W^T (rows: Y columns), B operand = T^T (columns: tokens).  A wave owns the 64 columns cb ... cb + 63 for all rows
+// of its workgroup.  Row i of tile t is column cb + (i >> 2) * 16 + t * 4 + (i & 3), so that the accumulators of lane group g
+// over the four tiles are the 16 consecutive columns cb + 16 g ... + 15 of token l & 15.
+template <int KS>
+__global__ __launch_bounds__(256) void lora_up_add_bf16_kernel(int64_t R, int n, int N, const bf16_t* __restrict__ T, int64_t ldt,
+                                                               const bf16_t* __restrict__ W, int64_t ldw, bf16_t* __restrict__ Y,
+                                                               int64_t ldy, float alpha, int rows_per_wg) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, i = lane & 15;
+  const int cb = (blockIdx.x * 4 + wave) * 64;
+  if (cb >= N) return;
+  const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  bf16x8 wf[KS][4];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int c = cb + (i >> 2) * 16 + t * 4 + (i & 3);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = ks * 32 + 8 * g + j;
+        wf[ks][t][j] = (k < n && c < N) ? W[(int64_t)k * ldw + c] : (bf16_t)0.f;
+      }
+    }
+  const int64_t r_begin = (int64_t)blockIdx.y * rows_per_wg;
+  const int64_t r_end = r_begin + rows_per_wg < R ? r_begin + rows_per_wg : R;
+  const int c0 = cb + 16 * g;                  // N is a multiple of 16: the lane's 16 columns are inside or outside as a whole
+  for (int64_t r0 = r_begin; r0 < r_end; r0 += 16) {
+    const int64_t r = r0 + i;
+    const bool ok = r < r_end;
+    bf16x8 tf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) tf[ks] = (ok && ks * 32 + 8 * g < n) ? *(const bf16x8*)(T + r * ldt + ks * 32 + 8 * g) : zero;
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[t] = mfma_bf16(wf[ks][t], tf[ks], acc[t]);
+    if (ok && c0 < N) {
+      bf16_t* y = Y + r * ldy + c0;
+      bf16x8 y0 = *(const bf16x8*)y, y1 = *(const bf16x8*)(y + 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        y0[j] = (bf16_t)__builtin_fmaf(alpha, acc[j >> 2][j & 3], (float)y0[j]);
+        y1[j] = (bf16_t)__builtin_fmaf(alpha, acc[2 + (j >> 2)][j & 3], (float)y1[j]);
+      }
+      *(bf16x8*)y = y0;
+      *(bf16x8*)(y + 8) = y1;
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void lora_up_add_plain_kernel(int64_t R, int n, int N, const T* __restrict__ Tm, int64_t ldt,
+                                                                const T* __restrict__ W, int64_t ldw, T* __restrict__ Y, int64_t ldy,
+                                                                float alpha) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= R * N) return;
+  const int64_t r = e / N;
+  const int c = (int)(e - r * N);
+  const T* t = Tm + r * ldt;
+  float s = 0.f;
+  for (int k = 0; k < n; ++k) s += to_f32(t[k]) * to_f32(W[(int64_t)k * ldw + c]);
+  T* y = Y + r * ldy + c;
+  *y = from_f32<T>(__builtin_fmaf(alpha, s, to_f32(*y)));
+}
+
+// ------------------------------------------------------------------------------------------------ wgrad
+// Fragment of a row-major LDS image img[token][column] for tokens 0 ... 31 and columns c0 ... c0 + 15: element j of lane l is
+// img[8 (l >> 4) + j][c0 + (l & 15)] — the A operand (rows: columns of the image) and the B operand alike (attention.hip frag_km).
+__device__ __forceinline__ bf16x8 lora_frag_tr(const bf16_t* img, int ld, int c0, int lane) {
+  const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
+  const bf16_t* a = img + (g * 8 + q) * ld + c0 + pp * 4;
+  const bf16x4 lo = lds_read_tr16(a);
+  const bf16x4 hi = lds_read_tr16(a + 4 * ld);
+  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
+// NT: 16-row tiles of n; CTW: 16-column tiles per wave — a workgroup covers CW = 64 CTW columns.  The stage images hold 32 tokens;
+// the next stage's global loads are in flight while the MFMAs of this one run.
+template <int NT, int CTW>
+__global__ __launch_bounds__(256) void lora_wgrad_bf16_kernel(int64_t R, int n, int N, const bf16_t* __restrict__ T, int64_t ldt,
+                                                              const bf16_t* __restrict__ X, int64_t ldx, float* __restrict__ ws,
+                                                              float alpha) {
+  constexpr int CW = CTW * 64;
+  constexpr int LDX = CW + 16;                 // 544 / 288 / 160-byte rows: 8 consecutive rows start on 8 different 32-byte bank groups
+  constexpr int XCH = CW / 8;                  // 16-byte chunks per X stage row
+  constexpr int TCH = NT * 2;                  // and per T stage row
+  constexpr int XU = CTW;                      // X chunks per thread: 32 * XCH / 256
+  constexpr int TU = (32 * TCH + 255) / 256;   // T chunks per thread (the last round may be partial)
+  __shared__ __attribute__((aligned(16))) bf16_t sx[32 * LDX];
+  __shared__ __attribute__((aligned(16))) bf16_t st[32 * LORA_LDT];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int cb = blockIdx.x * CW;
+  const int64_t slab = blockIdx.y;
+  const int64_t r_begin = slab * LORA_SLAB;
+  const int64_t r_end = r_begin + LORA_SLAB < R ? r_begin + LORA_SLAB : R;
+  const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  bf16x8 xr[XU], tr[TU];
+  auto load = [&](int64_t r0) {
+#pragma unroll
+    for (int u = 0; u < XU; ++u) {
+      const int id = tid + u * 256, row = id / XCH, c = cb + (id % XCH) * 8;
+      const int64_t r = r0 + row;
+      xr[u] = (r < r_end && c < N) ? *(const bf16x8*)(X + r * ldx + c) : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < TU; ++u) {
+      const int id = tid + u * 256, row = id / TCH, c = (id % TCH) * 8;
+      const int64_t r = r0 + row;
+      tr[u] = (id < 32 * TCH && r < r_end && c < n) ? *(const bf16x8*)(T + r * ldt + c) : zero;
+    }
+  };
+  auto stage = [&]() {
+#pragma unroll
+    for (int u = 0; u < XU; ++u) {
+      const int id = tid + u * 256;
+      *(bf16x8*)(sx + (id / XCH) * LDX + (id % XCH) * 8) = xr[u];
+    }
+#pragma unroll
+    for (int u = 0; u < TU; ++u) {
+      const int id = tid + u * 256;
+      if (id < 32 * TCH) *(bf16x8*)(st + (id / TCH) * LORA_LDT + (id % TCH) * 8) = tr[u];
+    }
+  };
+  f32x4 acc[NT][CTW];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int c = 0; c < CTW; ++c) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int wc = wave * CTW * 16;              // the wave's first column inside the workgroup's tile
+  load(r_begin);
+  for (int64_t r0 = r_begin; r0 < r_end; r0 += 32) {
+    __syncthreads();                           // everybody has read the previous stage
+    stage();
+    __syncthreads();
+    if (r0 + 32 < r_end) load(r0 + 32);
+    if (cb + wc < N) {
+      bf16x8 af[NT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) af[t] = lora_frag_tr(st, LORA_LDT, t * 16, lane);
+#pragma unroll
+      for (int c = 0; c < CTW; ++c) {
+        const bf16x8 bf = lora_frag_tr(sx, LDX, wc + c * 16, lane);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t][c] = mfma_bf16(af[t], bf, acc[t][c]);
+      }
+    }
+  }
+  float* out = ws + slab * (int64_t)n * N;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int c = 0; c < CTW; ++c) {
+      const int col = cb + wc + c * 16 + (lane & 15);
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int row = t * 16 + 4 * (lane >> 4) + reg;
+        if (row < n && col < N) out[(int64_t)row * N + col] = alpha * acc[t][c][reg];
+      }
+    }
+}
+
+// one thread per (n index, column) of a slab: token rows in ascending order
+template <typename T>
+__global__ __launch_bounds__(256) void lora_wgrad_plain_kernel(int64_t R, int n, int N, const T* __restrict__ Tm, int64_t ldt,
+                                                               const T* __restrict__ X, int64_t ldx, float* __restrict__ ws,
+                                                               float alpha) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n * N) return;
+  const int i = e / N, c = e - i * N;
+  const int64_t slab = blockIdx.y;
+  const int64_t r_begin = slab * LORA_SLAB;
+  const int64_t r_end = r_begin + LORA_SLAB < R ? r_begin + LORA_SLAB : R;
+  float s = 0.f;
+  for (int64_t r = r_begin; r < r_end; ++r) s += to_f32(Tm[r * ldt + i]) * to_f32(X[r * ldx + c]);
+  ws[slab * (int64_t)n * N + e] = alpha * s;
+}
+
+// ------------------------------------------------------------------------------------------------ host
+// The contract the three entry points share: n a multiple of 8 in 8 ... 192, the wide dimension a multiple of 16, bf16 rows and
+// bases on 16-byte boundaries (fp32: 4-byte), row strides at least the width.
+struct LoraOperand {
+  const char* name;
+  const void* p;
+  int64_t ld;
+  int64_t width;
+  int elem;            // bytes per element
+};
+static int lora_check(const char* fn, int dtype, int64_t R, int n, int wide, const char* wide_name,
+                      std::initializer_list<LoraOperand> ops) {
+  MDT_CHECK_ARG(dtype == MDT_F32 || dtype == MDT_BF16, "%s: dtype %d is neither MDT_F32 nor MDT_BF16", fn, dtype);
+  MDT_CHECK_ARG(R >= 0, "%s: R=%lld is negative", fn, (long long)R);
+  MDT_CHECK_ARG(n >= 8 && n <= 192 && n % 8 == 0, "%s: n=%d is not a multiple of 8 in 8 ... 192", fn, n);
+  MDT_CHECK_ARG(wide >= 16 && wide % 16 == 0, "%s: %s=%d is not a positive multiple of 16", fn, wide_name, wide);
+  if (R == 0) return MDT_OK;            // a no-op: an empty tensor has no base to check
+  for (const LoraOperand& o : ops) {
+    MDT_CHECK_ARG(o.p != nullptr, "%s: %s is a null pointer", fn, o.name);
+    MDT_CHECK_ARG(o.ld >= o.width, "%s: row stride of %s (%lld) is shorter than its rows (%lld)", fn, o.name, (long long)o.ld,
+                  (long long)o.width);
+    const int align = o.elem == 2 ? 16 : 4;
+    MDT_CHECK_ARG(((uintptr_t)o.p % align) == 0 && (o.ld * o.elem) % align == 0,
+                  "%s: %s (base %p, row stride %lld elements) is not on %d-byte boundaries", fn, o.name, o.p, (long long)o.ld, align);
+  }
+  return MDT_OK;
+}
+
+template <int NT>
+static int lora_down_launch(hipStream_t st, int64_t R, int n, int K, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw,
+                            bf16_t* T, int64_t ldt, float alpha) {
+  constexpr int MT = NT > 8 ? 1 : 2;
+  const int64_t blocks = (R + 64 * MT - 1) / (64 * MT);
+  return launch_route<lora_down_bf16_kernel<NT, MT>>("lora_down", dim3((unsigned)blocks), dim3(256), 0, st, R, n, K, X, ldx, W, ldw,
+                                                      T, ldt, alpha);
+}
+
+template <int KS>
+static int lora_up_launch(hipStream_t st, int64_t R, int n, int N, const bf16_t* T, int64_t ldt, const bf16_t* W, int64_t ldw,
+                          bf16_t* Y, int64_t ldy, float alpha) {
+  const int rows_per_wg = 256;
+  const dim3 grid((unsigned)((N + 255) / 256), (unsigned)((R + rows_per_wg - 1) / rows_per_wg));
+  return launch_route<lora_up_add_bf16_kernel<KS>>("lora_up", grid, dim3(256), 0, st, R, n, N, T, ldt, W, ldw, Y, ldy, alpha, rows_per_wg);
+}
+
+template <int NT, int CTW>
+static int lora_wgrad_launch(hipStream_t st, int64_t R, int n, int N, int64_t slabs, const bf16_t* T, int64_t ldt, const bf16_t* X,
+                             int64_t ldx, float* ws, float alpha) {
+  const dim3 grid((unsigned)((N + CTW * 64 - 1) / (CTW * 64)), (unsigned)slabs);
+  return launch_route<lora_wgrad_bf16_kernel<NT, CTW>>("lora_wgrad", grid, dim3(256), 0, st, R, n, N, T, ldt, X, ldx, ws, alpha);
+}
+
+constexpr int64_t LORA_MAX_ROWS = (int64_t)65535 * 256;     // grid.y of up_add (256 rows) and of wgrad (LORA_SLAB rows)
+
+}  // namespace mdt
+
+using namespace mdt;
+
+extern "C" int mdt_lora_wgrad_slab_rows(void) { return LORA_SLAB; }
+
+extern "C" int mdt_lora_down(void* stream, int dtype, int64_t R, int n, int K, const void* X, int64_t ldx, const void* W,
+                             int64_t ldw, void* T, int64_t ldt, float alpha) {
+  const int es = (int)dtype_size(dtype);
+  if (int e = lora_check("mdt_lora_down", dtype, R, n, K, "K", {{"X", X, ldx, K, es}, {"W", W, ldw, K, es}, {"T", T, ldt, n, es}}))
+    return e;
+  MDT_CHECK_ARG(R <= LORA_MAX_ROWS, "mdt_lora_down: R=%lld exceeds %lld rows", (long long)R, (long long)LORA_MAX_ROWS);
+  if (R == 0) return MDT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MDT_F32) {
+    const int64_t blocks = (R * n + 255) / 256;
+    return launch_route<lora_down_plain_kernel<float>>("lora_down_f32", dim3((unsigned)blocks), dim3(256), 0, st, R, n, K, (const float*)X,
+                                                        ldx, (const float*)W, ldw, (float*)T, ldt, alpha);
+  }
+  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)W;
+  bf16_t* t = (bf16_t*)T;
+  const int nt = (n + 15) / 16;
+  if (nt <= 1) return lora_down_launch<1>(st, R, n, K, x, ldx, w, ldw, t, ldt, alpha);
+  if (nt <= 2) return lora_down_launch<2>(st, R, n, K, x, ldx, w, ldw, t, ldt, alpha);
+  if (nt <= 3) return lora_down_launch<3>(st, R, n, K, x, ldx, w, ldw, t, ldt, alpha);
+  if (nt <= 4) return lora_down_launch<4>(st, R, n, K, x, ldx, w, ldw, t, ldt, alpha);
+  if (nt <= 6) return lora_down_launch<6>(st, R, n, K, x, ldx, w, ldw, t, ldt, alpha);
+  if (nt <= 8) return lora_down_launch<8>(st, R, n, K, x, ldx, w, ldw, t, ldt, alpha);
+  return lora_down_launch<12>(st, R, n, K, x, ldx, w, ldw, t, ldt, alpha);
+}
+
+extern "C" int mdt_lora_up_add(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt, const void* W,
+                               int64_t ldw, void* Y, int64_t ldy, float alpha) {
+  const int es = (int)dtype_size(dtype);
+  if (int e = lora_check("mdt_lora_up_add", dtype, R, n, N, "N", {{"T", T, ldt, n, es}, {"W", W, ldw, N, es}, {"Y", Y, ldy, N, es}}))
+    return e;
+  MDT_CHECK_ARG(R <= LORA_MAX_ROWS, "mdt_lora_up_add: R=%lld exceeds %lld rows", (long long)R, (long long)LORA_MAX_ROWS);
+  if (R == 0) return MDT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MDT_F32) {
+    const int64_t blocks = (R * N + 255) / 256;
+    return launch_route<lora_up_add_plain_kernel<float>>("lora_up_f32", dim3((unsigned)blocks), dim3(256), 0, st, R, n, N, (const float*)T,
+                                                          ldt, (const float*)W, ldw, (float*)Y, ldy, alpha);
+  }
+  const bf16_t *t = (const bf16_t*)T, *w = (const bf16_t*)W;
+  bf16_t* y = (bf16_t*)Y;
+  const int ks = (n + 31) / 32;
+  if (ks <= 1) return lora_up_launch<1>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha);
+  if (ks <= 2) return lora_up_launch<2>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha);
+  if (ks <= 3) return lora_up_launch<3>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha);
+  if (ks <= 4) return lora_up_launch<4>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha);
+  return lora_up_launch<6>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha);
+}
+
+extern "C" size_t mdt_lora_wgrad_workspace_bytes(int64_t R, int n, int N) {
+  if (R <= 0 || n <= 0 || N <= 0) return 0;
+  const int64_t slabs = (R + LORA_SLAB - 1) / LORA_SLAB;
+  return (size_t)slabs * (size_t)n * (size_t)N * sizeof(float);
+}
+
+extern "C" int mdt_lora_wgrad(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt, const void* X,
+                              int64_t ldx, float* dW, int64_t lddw, float alpha, void* workspace, size_t workspace_bytes) {
+  const int es = (int)dtype_size(dtype);
+  if (int e = lora_check("mdt_lora_wgrad", dtype, R, n, N, "N", {{"T", T, ldt, n, es}, {"X", X, ldx, N, es}, {"dW", dW, lddw, N, 4}}))
+    return e;
+  MDT_CHECK_ARG(R <= LORA_MAX_ROWS, "mdt_lora_wgrad: R=%lld exceeds %lld rows", (long long)R, (long long)LORA_MAX_ROWS);
+  if (R == 0) return MDT_OK;
+  const size_t need = mdt_lora_wgrad_workspace_bytes(R, n, N);
+  MDT_CHECK_ARG(workspace && workspace_bytes >= need, "mdt_lora_wgrad: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+  MDT_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "mdt_lora_wgrad: workspace %p is not 16-byte aligned", workspace);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t slabs = (R + LORA_SLAB - 1) / LORA_SLAB;
+  float* ws = (float*)workspace;
+  int e;
+  if (dtype == MDT_F32) {
+    const dim3 grid((unsigned)((n * N + 255) / 256), (unsigned)slabs);
+    e = launch_route<lora_wgrad_plain_kernel<float>>("lora_wgrad_f32", grid, dim3(256), 0, st, R, n, N, (const float*)T, ldt, (const float*)X,
+                                                      ldx, ws, alpha);
+  } else {
+    const bf16_t *t = (const bf16_t*)T, *x = (const bf16_t*)X;
+    const int nt = (n + 15) / 16;
+    if (nt <= 1) e = lora_wgrad_launch<1, 4>(st, R, n, N, slabs, t, ldt, x, ldx, ws, alpha);
+    else if (nt <= 2) e = lora_wgrad_launch<2, 4>(st, R, n, N, slabs, t, ldt, x, ldx, ws, alpha);
+    else if (nt <= 3) e = lora_wgrad_launch<3, 4>(st, R, n, N, slabs, t, ldt, x, ldx, ws, alpha);
+    else if (nt <= 4) e = lora_wgrad_launch<4, 4>(st, R, n, N, slabs, t, ldt, x, ldx, ws, alpha);
+    else if (nt <= 6) e = lora_wgrad_launch<6, 2>(st, R, n, N, slabs, t, ldt, x, ldx, ws, alpha);
+    else if (nt <= 8) e = lora_wgrad_launch<8, 2>(st, R, n, N, slabs, t, ldt, x, ldx, ws, alpha);
+    else e = lora_wgrad_launch<12, 1>(st, R, n, N, slabs, t, ldt, x, ldx, ws, alpha);
+  }
+  if (e) return e;
+  // ascending slab order, dW's old value last
+  return sum_slices_f32(st, n, N, (int)slabs, ws, N, (int64_t)n * N, dW, lddw, 1);
+}

@@ -311,10 +311,17 @@ class BlockParams:
     fc2_b: torch.nn.Parameter
     ln2_w: torch.nn.Parameter
     ln2_b: torch.nn.Parameter
+    # low-rank adapters beside the (frozen) QKV projection, or None: lora_A / lora_Bt [|J| r, D] hold the rows of A_j / B_j^T
+    # target-major, lora_cols the thirds of the qkv buffer they add to (0 = q, 1 = k, 2 = v), lora_scale = alpha / r
+    lora_A: Optional[torch.nn.Parameter] = None
+    lora_Bt: Optional[torch.nn.Parameter] = None
+    lora_cols: Optional[tuple] = None
+    lora_scale: float = 1.0
 
     def all(self):
-        return [self.qkv_w, self.qkv_b, self.o_w, self.o_b, self.ln1_w, self.ln1_b, self.fc1_w, self.fc1_b,
+        base = [self.qkv_w, self.qkv_b, self.o_w, self.o_b, self.ln1_w, self.ln1_b, self.fc1_w, self.fc1_b,
                 self.fc2_w, self.fc2_b, self.ln2_w, self.ln2_b]
+        return base if self.lora_A is None else base + [self.lora_A, self.lora_Bt]
 
 
 @dataclass
@@ -449,6 +456,43 @@ def _ln_bwd_dense(tape, dy, x, w, b, mean, rstd, bias_param, p_drop, seed, add=N
                          want_dropped=True)
 
 
+def lora_fwd(P: BlockParams, src: torch.Tensor, qkv: torch.Tensor) -> torch.Tensor:
+    """Adapters of the QKV projection, forward: t = src A^T (stored in the working dtype), then
+    qkv[:, c_j : c_j + D] += s t_j Bt_j for every target, in place and before attention reads qkv.  → t"""
+    D = src.shape[1]
+    r = P.lora_A.shape[0] // len(P.lora_cols)
+    t = ops.lora_down(src, P.lora_A.data)
+    for j, c in enumerate(P.lora_cols):
+        ops.lora_up_add(t[:, j * r:(j + 1) * r], P.lora_Bt.data[j * r:(j + 1) * r], qkv[:, c * D:(c + 1) * D], alpha=P.lora_scale)
+    return t
+
+
+def lora_bwd(tape: Tape, P: BlockParams, src: torch.Tensor, t: torch.Tensor, dqkv: torch.Tensor, dx: Optional[torch.Tensor]) -> None:
+    """Adjoint of lora_fwd: dBt_j += s t_j^T dqkv_j, dt_j = s dqkv_j Bt_j^T, dA += dt^T src and, where the block wants its input
+    gradient, dx += dt A on the output of the frozen projection's dgrad.  The weight gradients are sums in a fixed order
+    (ops.lora_wgrad): the same launches in the default and in the deterministic mode; a frozen adapter costs nothing."""
+    D = src.shape[1]
+    n = P.lora_A.shape[0]
+    r = n // len(P.lora_cols)
+    s = P.lora_scale
+    gA, gBt = tape.pgrad(P.lora_A), tape.pgrad(P.lora_Bt)
+    want_dt = gA is not None or dx is not None
+    dt = torch.empty(src.shape[0], n, dtype=src.dtype, device=src.device) if want_dt else None
+    ws = None
+    if gA is not None or gBt is not None:
+        ws = ordered_workspace(ops.lib.mdt_lora_wgrad_workspace_bytes(src.shape[0], n, D), src.device)
+    for j, c in enumerate(P.lora_cols):
+        rows, dq = slice(j * r, (j + 1) * r), dqkv[:, c * D:(c + 1) * D]
+        if gBt is not None:
+            ops.lora_wgrad(t[:, rows], dq, gBt.view(n, D)[rows], alpha=s, ws=ws)
+        if want_dt:
+            ops.lora_down(dq, P.lora_Bt.data[rows], out=dt[:, rows], alpha=s)
+    if gA is not None:
+        ops.lora_wgrad(dt, src, gA.view(n, D), ws=ws)
+    if dx is not None:
+        ops.lora_up_add(dt, P.lora_A.data, dx)
+
+
 # ------------------------------------------------------------------------------------------
 # ops
 def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre_ln: bool, eps: float,
@@ -480,6 +524,9 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
         raise ValueError(f"transformer_block: unknown activation {act!r} (one of {sorted(ops.ACT_KINDS)})")
     if act != "gelu" and f8 is not None:
         raise NotImplementedError(f"fp8 GEMMs with the {act} activation: the fused fp8 producer of h is fc1's erf-GELU epilogue")
+    if P.lora_A is not None and f8 is not None:
+        raise NotImplementedError("fp8 GEMMs on a block with low-rank adapters: the adapter sum enters the bf16 qkv buffer only "
+                                  "(run adapters in bf16, or fp8 without --lora-rank)")
 
     def gather(src):
         """rows ``keep_rows`` of src (identity when the block keeps everything)"""
@@ -508,9 +555,14 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     def attn_fwd(src, src8):
         """attention half: QKV of ``src`` (all rows), attention, output projection + residual x on the kept rows"""
         qkv_, _ = linear(f8, src, P.qkv_w, "qkv", x8=src8, bias=P.qkv_b.data)
+        lt_ = None
+        if P.lora_A is not None:           # the adapters' sum joins qkv before attention reads it; t is kept for backward only
+            lt_ = lora_fwd(P, src, qkv_)
+            if tape.inference:
+                lt_ = None
         ctx_full_, lse_ = ops.attention_fwd(qkv_, spec.nseq, spec.S, spec.H, **kw)
         ctx_, xk = gather(ctx_full_), gather(xd)
-        return qkv_, ctx_full_, lse_, ctx_, ops.gemm(ctx_, P.o_w.data, bias=P.o_b.data, residual=xk, drop_p=p_hidden, drop_seed=s_o)
+        return qkv_, lt_, ctx_full_, lse_, ctx_, ops.gemm(ctx_, P.o_w.data, bias=P.o_b.data, residual=xk, drop_p=p_hidden, drop_seed=s_o)
 
     def ffn_fwd(src, src8, res):
         """FFN half: fc1 writes h and u (and, 8-bit, the quantised h that fc2 then reads), fc2 adds ``res``"""
@@ -526,13 +578,13 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     # a_in / f_in: what the attention / FFN half reads; t: the attention half's output (its residual is always x)
     if not pre_ln:
         a_in = xd
-        qkv, ctx_full, lse, ctx, t = attn_fwd(a_in, None)
+        qkv, lt, ctx_full, lse, ctx, t = attn_fwd(a_in, None)
         f_in, m1, r1, f_in8 = ln8(t, P.ln1_w, P.ln1_b, P.fc1_w, "fc1")
         u, h, y = ffn_fwd(f_in, f_in8, f_in)
         out, m2, r2 = ops.layernorm_fwd(y, P.ln2_w.data, P.ln2_b.data, eps)
     else:
         a_in, m1, r1, a_in8 = ln8(xd, P.ln1_w, P.ln1_b, P.qkv_w, "qkv")
-        qkv, ctx_full, lse, ctx, t = attn_fwd(a_in, a_in8)
+        qkv, lt, ctx_full, lse, ctx, t = attn_fwd(a_in, a_in8)
         f_in, m2, r2, f_in8 = ln8(t, P.ln2_w, P.ln2_b, P.fc1_w, "fc1")
         u, h, out = ffn_fwd(f_in, f_in8, t)
     o = Var(out)
@@ -557,7 +609,10 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
         dctx = ops.gemm(dtd, P.o_w.data, trans_b=True)
         dqkv = _attention_bwd(tape, spec, kw, dctx, qkv, ctx_full, lse, spread)
         wgrad(tape, dqkv, a_in, P.qkv_w, P.qkv_b)
-        return dgrad(dqkv, P.qkv_w, residual=None if dres is None else spread(dres)) if want_dx else None
+        dx_ = dgrad(dqkv, P.qkv_w, residual=None if dres is None else spread(dres)) if want_dx else None
+        if P.lora_A is not None:
+            lora_bwd(tape, P, a_in, lt, dqkv, dx_)
+        return dx_
 
     def bwd(g):
         ride = _WGRAD_ASUM and dyd_rides(g)     # bias gradients ride on the weight-gradient GEMMs (wgrad) where they can

@@ -102,6 +102,8 @@ class GraphormerModel(FairseqEncoderModel):
                                                        bert=getattr(args, "pretrained_bert", None) or hf_weights.BERT_NAME,
                                                        vit=getattr(args, "pretrained_vit", None) or hf_weights.VIT_NAME)
             logger.info("pretrained encoders: %s", info)
+        if getattr(args, "lora_rank", 0):          # after the pretrained weights: the adapters sit beside them
+            model.add_lora(int(args.lora_rank), getattr(args, "lora_alpha", None), getattr(args, "lora_targets", None) or "q,v")
         return model
 
     def forward(self, batched_data, **kwargs):
@@ -147,6 +149,71 @@ class GraphormerModel(FairseqEncoderModel):
             groups.setdefault((scale, wd), {"params": [], "lr_scale": scale, "weight_decay": wd})["params"].append(p)
         return list(groups.values())
 
+    # ---- low-rank adapters ---------------------------------------------------------------------
+    def pretrained_blocks(self):
+        """The BertLayer / ViTLayer blocks of the two pretrained encoders: the truncated prefixes first, then the fusion stacks."""
+        ge = self.encoder.graph_encoder
+        prefix = list(ge.text_model.encoder.layer) + list(ge.vit_model.encoder.layer)
+        fusion = [blk for st in ge.fusion_layers for fl in st.fusion_layers for blk in (fl.bert_encoder, fl.vit_encoder)]
+        return prefix, fusion
+
+    def lora_modules(self):
+        """The QKV projections that carry adapters."""
+        prefix, fusion = self.pretrained_blocks()
+        return [b.qkv_params() for b in prefix + fusion if b.qkv_params().lora_A is not None]
+
+    def add_lora(self, rank: int, alpha=None, targets=("q", "v")):
+        """Parameter-efficient fine-tuning: every parameter of the two pretrained encoders (``encoder_layer_ids``: embeddings and
+        blocks) is frozen and rank-``rank`` adapters are trained beside the fused QKV projection of every pretrained block —
+        of the fusion blocks only when the prefixes are frozen by --freeze_initial_encoders, which then keep running without a
+        tape.  Poolers, ViT's final LayerNorm, the graph stacks, bottleneck tokens and the head stay as they are.  ``alpha``
+        defaults to 2 * rank; the adapter sum is scaled by alpha / rank.  Call it after the pretrained weights are loaded and
+        before ``prepare_main_grads`` / FusedAdam.  → the number of adapted projections."""
+        import math
+        from .. import fp8
+        from ..modules._fused import LORA_RANKS, parse_lora_targets
+        if getattr(self, "main_grad_flat", None) is not None:
+            raise RuntimeError("add_lora after prepare_main_grads: the gradient arena was laid out without the adapters")
+        if fp8.ACTIVE is not None:
+            raise NotImplementedError("low-rank adapters with fp8 GEMMs enabled are not supported (the adapter sum enters the bf16 "
+                                      "qkv buffer only): disable fp8 first")
+        if self.lora_modules():
+            raise RuntimeError("add_lora: the model already has adapters")
+        if rank not in LORA_RANKS:
+            raise ValueError(f"add_lora: rank {rank} is not one of {LORA_RANKS}")
+        alpha = 2.0 * rank if alpha is None else float(alpha)
+        if not (math.isfinite(alpha) and alpha > 0):
+            raise ValueError(f"add_lora: alpha {alpha} is not a finite positive number")
+        targets = parse_lora_targets(targets)
+        ids = self.encoder_layer_ids()
+        for p in self.parameters():
+            if id(p) in ids:
+                p.requires_grad = False
+        prefix, fusion = self.pretrained_blocks()
+        blocks = fusion if getattr(self.args, "freeze_initial_encoders", False) else prefix + fusion
+        for b in blocks:
+            b.qkv_params().add_lora(rank, alpha, targets)
+        return len(blocks)
+
+    def merge_lora(self):
+        """Fold every adapter into its projection (W_j += s B_j A_j, fp32, one rounding) and remove it: ``state_dict()`` then has
+        exactly the keys of a model built without adapters.  → the number of projections merged."""
+        mods = self.lora_modules()
+        for m in mods:
+            m.merge_lora()
+        if mods:
+            E.weights_changed()
+        return len(mods)
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """As nn.Module's, with one allowance: a checkpoint WITHOUT adapter keys loads into an adapted model (fine-tuning from a
+        full checkpoint) — the adapters keep their values and their keys are reported in the returned ``missing_keys``."""
+        res = super().load_state_dict(state_dict, strict=strict, **kw)
+        for m in self.lora_modules():
+            res.missing_keys.extend(m._lora_missing)
+            m._lora_missing = []
+        return res
+
     # ---- fp32 gradient arena ----------------------------------------------------------------
     def prepare_main_grads(self):
         """Give every trainable parameter an fp32 ``main_grad`` view into one flat buffer (reverse
@@ -177,6 +244,9 @@ class GraphormerModel(FairseqEncoderModel):
         if on and act != "gelu":
             raise NotImplementedError(f"enable_fp8 with --activation-fn {act}: the fp8 path quantises h inside fc1's fused gelu "
                                       "epilogue, which the other activations do not go through")
+        if on and self.lora_modules():
+            raise NotImplementedError("enable_fp8 on a model with low-rank adapters is not supported: the adapter sum enters the "
+                                      "bf16 qkv buffer only (train the adapters in bf16, or merge_lora() first)")
         from .. import engine
         if on and engine.deterministic():
             raise NotImplementedError("enable_fp8 in deterministic mode: the fp8 path has no ordered reductions "

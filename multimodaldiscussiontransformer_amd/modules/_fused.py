@@ -59,12 +59,95 @@ def _hf_init_linear(lin: nn.Linear, std: float = 0.02):
         nn.init.zeros_(lin.bias)
 
 
+LORA_RANKS = (8, 16, 32, 64)
+LORA_TARGETS = ("q", "k", "v")
+
+
+def parse_lora_targets(targets) -> tuple:
+    """("q", "v") from "q,v" or a sequence: distinct names of q / k / v, returned in q, k, v order."""
+    names = [t.strip() for t in targets.split(",")] if isinstance(targets, str) else list(targets)
+    if not names or any(t not in LORA_TARGETS for t in names) or len(set(names)) != len(names):
+        raise ValueError(f"LoRA targets {targets!r}: a non-empty list of distinct names out of q, k, v")
+    return tuple(t for t in LORA_TARGETS if t in names)
+
+
 class _SelfAttentionParams(QKVFusedMixin, nn.Module):
+    """The fused QKV projection of a pretrained block and, after ``add_lora``, the low-rank adapters beside it: live parameters
+    ``lora_A`` / ``lora_Bt`` [|J| r, D] (rows of A_j and of B_j^T, target-major — one operand layout for every kernel), saved per
+    target under PEFT's names ``{query,key,value}.lora_A.weight`` [r, D] / ``.lora_B.weight`` [D, r] next to the split q/k/v keys."""
+
     def __init__(self, dim, names):
         super().__init__()
         self._qkv_names = names
         self._init_qkv(dim)
         nn.init.normal_(self.qkv_weight, 0.0, 0.02)
+        self.lora_A = self.lora_Bt = None
+        self.lora_targets, self.lora_rank, self.lora_alpha = (), 0, 0.0
+        self._lora_missing = []
+
+    # ---- adapters
+    def add_lora(self, rank: int, alpha: float, targets):
+        if self.lora_A is not None:
+            raise RuntimeError("add_lora: this projection already has adapters")
+        targets = parse_lora_targets(targets)
+        if rank not in LORA_RANKS:
+            raise ValueError(f"LoRA rank {rank}: one of {LORA_RANKS}")
+        w = self.qkv_weight
+        n = len(targets) * rank
+        a = torch.empty(n, self._qkv_dim, dtype=torch.float32)
+        for j in range(len(targets)):               # every A_j as an nn.Linear(D, r) weight; B = 0: the adapted model starts as the base
+            nn.init.kaiming_uniform_(a[j * rank:(j + 1) * rank], a=math.sqrt(5))
+        self.lora_A = nn.Parameter(a.to(device=w.device, dtype=w.dtype))
+        self.lora_Bt = nn.Parameter(torch.zeros(n, self._qkv_dim, device=w.device, dtype=w.dtype))
+        self.lora_targets, self.lora_rank, self.lora_alpha = targets, int(rank), float(alpha)
+
+    def lora_fields(self) -> dict:
+        """The adapter fields of engine.BlockParams ({} without adapters)."""
+        if self.lora_A is None:
+            return {}
+        return dict(lora_A=self.lora_A, lora_Bt=self.lora_Bt, lora_cols=tuple(LORA_TARGETS.index(t) for t in self.lora_targets),
+                    lora_scale=self.lora_alpha / self.lora_rank)
+
+    def merge_lora(self):
+        """W_j += s Bt_j^T A_j in fp32, rounded once to the parameter's dtype; the adapters are removed."""
+        if self.lora_A is None:
+            return
+        d, r, s = self._qkv_dim, self.lora_rank, self.lora_alpha / self.lora_rank
+        with torch.no_grad():
+            for j, t in enumerate(self.lora_targets):
+                c = LORA_TARGETS.index(t) * d
+                a, bt = self.lora_A[j * r:(j + 1) * r].float(), self.lora_Bt[j * r:(j + 1) * r].float()
+                wj = self.qkv_weight[c:c + d]
+                wj.copy_((wj.float() + s * (bt.t() @ a)).to(wj.dtype))
+        self.lora_A = self.lora_Bt = None
+        self.lora_targets, self.lora_rank, self.lora_alpha = (), 0, 0.0
+
+    def _lora_key(self, prefix, target, which):
+        return f"{prefix}{self._qkv_names[LORA_TARGETS.index(target)]}.lora_{which}.weight"
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        if self.lora_A is None:
+            return
+        a, bt, r = destination.pop(prefix + "lora_A"), destination.pop(prefix + "lora_Bt"), self.lora_rank
+        for j, t in enumerate(self.lora_targets):
+            destination[self._lora_key(prefix, t, "A")] = a[j * r:(j + 1) * r]
+            destination[self._lora_key(prefix, t, "B")] = bt[j * r:(j + 1) * r].t()
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        self._lora_missing = []
+        if self.lora_A is not None:
+            keys = [self._lora_key(prefix, t, w) for t in self.lora_targets for w in ("A", "B")]
+            have = [k for k in keys if k in state_dict]
+            if not have:
+                # a checkpoint of the full model: the adapters keep their values; GraphormerModel.load_state_dict reports the keys
+                self._lora_missing = keys
+                state_dict[prefix + "lora_A"], state_dict[prefix + "lora_Bt"] = self.lora_A.data, self.lora_Bt.data
+            elif len(have) == len(keys):
+                state_dict[prefix + "lora_A"] = torch.cat([state_dict.pop(self._lora_key(prefix, t, "A")) for t in self.lora_targets], dim=0)
+                state_dict[prefix + "lora_Bt"] = torch.cat([state_dict.pop(self._lora_key(prefix, t, "B")).t() for t in self.lora_targets], dim=0)
+            # some but not all: the strict loader names the absent ones (lora_A / lora_Bt missing, the rest unexpected)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
 
 class _DenseLN(nn.Module):
@@ -106,11 +189,15 @@ class BertLayer(nn.Module):
         t = self.training
         return dict(p_hidden=self.hidden_dropout_p if t else 0.0, p_attn=self.attention_dropout_p if t else 0.0)
 
+    def qkv_params(self) -> "_SelfAttentionParams":
+        return self.attention.self
+
     def block_params(self) -> BlockParams:
         a, o = self.attention, self.output
         return BlockParams(a.self.qkv_weight, a.self.qkv_bias, a.output.dense.weight, a.output.dense.bias,
                            a.output.LayerNorm.weight, a.output.LayerNorm.bias, self.intermediate.dense.weight,
-                           self.intermediate.dense.bias, o.dense.weight, o.dense.bias, o.LayerNorm.weight, o.LayerNorm.bias)
+                           self.intermediate.dense.bias, o.dense.weight, o.dense.bias, o.LayerNorm.weight, o.LayerNorm.bias,
+                           **a.self.lora_fields())
 
 
 class _ViTAttention(nn.Module):
@@ -138,12 +225,15 @@ class ViTLayer(nn.Module):
         t = self.training
         return dict(p_hidden=self.hidden_dropout_p if t else 0.0, p_attn=self.attention_dropout_p if t else 0.0)
 
+    def qkv_params(self) -> "_SelfAttentionParams":
+        return self.attention.attention
+
     def block_params(self) -> BlockParams:
         a = self.attention
         return BlockParams(a.attention.qkv_weight, a.attention.qkv_bias, a.output.dense.weight, a.output.dense.bias,
                            self.layernorm_before.weight, self.layernorm_before.bias, self.intermediate.dense.weight,
                            self.intermediate.dense.bias, self.output.dense.weight, self.output.dense.bias,
-                           self.layernorm_after.weight, self.layernorm_after.bias)
+                           self.layernorm_after.weight, self.layernorm_after.bias, **a.attention.lora_fields())
 
 
 class _Pooler(nn.Module):

@@ -21,7 +21,7 @@ __all__ = [
     "row_axpby", "row_scatter_add", "bert_embed_sum", "bert_embed_ln_rows", "vit_patchify", "vit_assemble", "vit_patch_embed", "graph_node_feature",
     "tanh_fwd", "tanh_bwd", "node_ce", "contrastive_loss", "fp8_quantize", "fp8_scale_update", "gemm_fp8", "cast", "transpose2d", "dropout", "dropout_mask",
     "sum_slices", "gemm_splitk_ordered", "colsum_ordered", "layernorm_bwd_ordered", "segments_of", "row_segment_sum",
-    "attn_bias_grad_ordered", "float_atomic_launches",
+    "attn_bias_grad_ordered", "float_atomic_launches", "lora_down", "lora_up_add", "lora_wgrad", "LORA_WGRAD_SLAB",
     "act_fwd", "ACT_KINDS", "ACT_GELU", "ACT_RELU", "ACT_GELU_ACCURATE", "ACT_TANH", "ACT_LINEAR",
     "EPI_BIAS", "EPI_GELU", "EPI_RESIDUAL", "EPI_DGELU", "EPI_ACCUM", "EPI_ATOMIC", "EPI_DROPOUT", "EPI_AUX_GRAD", "EPI_MULAUX", "EPI_ASUM",
 ]
@@ -328,6 +328,44 @@ def gemm_splitk_ordered(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, *, 
     check(lib.mdt_gemm_splitk_ordered(stream(), dt(a), int(trans_a), int(trans_b), M, N, K, ptr(a), lda, ptr(b), ldb, ptr(out),
                                       _2d(out), float(alpha), int(split_k), ptr(ws), nbytes), "mdt_gemm_splitk_ordered")
     return out
+
+
+# low-rank adapter products: include/mdt_hip.h "low-rank adapters".  Operands are row-major 2-D tensors (views with a row
+# stride wider than the row — column slices of the qkv / dqkv buffers — included); w is always [n, wide].
+LORA_WGRAD_SLAB = int(lib.mdt_lora_wgrad_slab_rows())      # token rows per slab of lora_wgrad's fixed-order sum
+
+
+def lora_down(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None, alpha=1.0) -> torch.Tensor:
+    """out[R, n] = alpha * x[R, K] @ w[n, K].T, stored in the operands' dtype."""
+    R, K = x.shape
+    n = w.shape[0]
+    assert w.shape[1] == K and x.dtype == w.dtype
+    if out is None:
+        out = torch.empty(R, n, dtype=x.dtype, device=x.device)
+    assert out.shape == (R, n) and out.dtype == x.dtype
+    check(lib.mdt_lora_down(stream(), dt(x), R, n, K, ptr(x), _2d(x), ptr(w), _2d(w), ptr(out), _2d(out), float(alpha)), "mdt_lora_down")
+    return out
+
+
+def lora_up_add(t: torch.Tensor, w: torch.Tensor, y: torch.Tensor, alpha=1.0) -> torch.Tensor:
+    """y[R, N] += alpha * t[R, n] @ w[n, N], in place: one rounding of y_old + product."""
+    R, n = t.shape
+    N = w.shape[1]
+    assert w.shape[0] == n and y.shape == (R, N) and t.dtype == w.dtype == y.dtype
+    check(lib.mdt_lora_up_add(stream(), dt(t), R, n, N, ptr(t), _2d(t), ptr(w), _2d(w), ptr(y), _2d(y), float(alpha)), "mdt_lora_up_add")
+    return y
+
+
+def lora_wgrad(t: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, alpha=1.0, ws=None) -> torch.Tensor:
+    """dw[n, N] (fp32) += alpha * t[R, n].T @ x[R, N]: slabs of LORA_WGRAD_SLAB token rows added in ascending order, no float
+    atomics — the same bits on every call with these operands."""
+    R, n = t.shape
+    N = x.shape[1]
+    assert x.shape[0] == R and t.dtype == x.dtype and dw.dtype == torch.float32 and dw.shape == (n, N)
+    ws, nbytes = _workspace(ws, lib.mdt_lora_wgrad_workspace_bytes(R, n, N), t.device)
+    check(lib.mdt_lora_wgrad(stream(), dt(t), R, n, N, ptr(t), _2d(t), ptr(x), _2d(x), ptr(dw), _2d(dw), float(alpha), ptr(ws), nbytes),
+          "mdt_lora_wgrad")
+    return dw
 
 
 def colsum_ordered(x: torch.Tensor, out: Optional[torch.Tensor] = None, row_weight=None, ws=None) -> torch.Tensor:

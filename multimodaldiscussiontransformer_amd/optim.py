@@ -310,7 +310,8 @@ class FusedAdam:
             for beg, end, p in spans:
                 if beg <= v.data_ptr() < end and v.dtype == p.dtype:
                     off = (v.data_ptr() - beg) // p.element_size()
-                    yield k, self.state[id(p)]["ema"].view(-1)[off:off + v.numel()].view(v.shape)
+                    e = self.state[id(p)]["ema"]      # the entry's own view (a transposed adapter slice is strided) of the average
+                    yield k, e.as_strided(tuple(v.shape), tuple(v.stride()), e.storage_offset() + off)
                     break
 
     def ema_state_dict(self, model):

@@ -86,6 +86,16 @@ def build_parser():
                         "of a depth-L encoder runs at --encoder-lr-scale * G^(L - i), its embeddings at G^(L + 1)")
     p.add_argument("--no-decay-bias-norm", action="store_true", default=False,
                    help="not a reference flag: weight decay 0 for biases and LayerNorm weights (every parameter with ndim <= 1)")
+    # parameter-efficient fine-tuning (not reference flags): GraphormerModel.add_lora
+    p.add_argument("--lora-rank", type=int, default=0,
+                   help="not a reference flag: freeze the pretrained BERT / ViT embeddings and blocks and train rank-N adapters (8, 16, 32 "
+                        "or 64) beside the QKV projection of every pretrained block (with --freeze_initial_encoders: of the fusion "
+                        "blocks); 0: off")
+    p.add_argument("--lora-alpha", type=float, default=None, help="adapter scale numerator: the adapter sum is scaled by alpha / rank "
+                   "(finite, > 0; default 2 * rank)")
+    p.add_argument("--lora-targets", default=None, help="comma list out of q,k,v: the projections that get adapters (default q,v)")
+    p.add_argument("--save-merged", default="", help="with --lora-rank: also write, at the end, a plain checkpoint with the adapters "
+                   "folded into the projections (GraphormerModel.merge_lora) — it loads into a model built without --lora-rank")
     p.add_argument("--log-interval", type=int, default=10)
     # criterion flags: every field of every registered criterion's config dataclass (FairSeq derives them the same way)
     from .registry import CRITERION_REGISTRY as _CR
@@ -200,6 +210,29 @@ def main(argv=None):
     if not use_groups:
         for f in group_flags:                    # flags left at their defaults: the optimiser, the log lines and the checkpoint cfg of a run without them
             delattr(args, f)
+    lora_rank, save_merged = int(args.lora_rank or 0), args.save_merged
+    lora_flags = [f for f in ("lora_alpha", "lora_targets") if getattr(args, f) is not None] + (["save_merged"] if save_merged else [])
+    if lora_flags and not lora_rank:
+        raise SystemExit("[mdt-train] " + ", ".join("--" + f.replace("_", "-") for f in lora_flags) + " without --lora-rank: there are no "
+                         "adapters to configure or merge — add --lora-rank")
+    delattr(args, "save_merged")                 # where a file goes is no property of the model: not part of a checkpoint's cfg
+    if lora_rank:
+        from .modules._fused import LORA_RANKS, parse_lora_targets
+        if lora_rank not in LORA_RANKS:
+            raise SystemExit(f"[mdt-train] --lora-rank must be one of {', '.join(map(str, LORA_RANKS))} (0: off)")
+        args.lora_alpha = 2.0 * lora_rank if args.lora_alpha is None else args.lora_alpha
+        if not (math.isfinite(args.lora_alpha) and args.lora_alpha > 0.0):
+            raise SystemExit("[mdt-train] --lora-alpha must be finite and > 0")
+        try:
+            args.lora_targets = ",".join(parse_lora_targets(args.lora_targets or "q,v"))
+        except ValueError as e:
+            raise SystemExit(f"[mdt-train] --lora-targets: {e}")
+        if args.fp8:
+            raise SystemExit("[mdt-train] --fp8 with --lora-rank: low-rank adapters with fp8 GEMMs are not supported (the adapter sum "
+                             "enters the bf16 qkv buffer only) — train the adapters in bf16")
+    else:
+        for f in ("lora_rank", "lora_alpha", "lora_targets"):      # a run without adapters writes the checkpoint cfg it always wrote
+            delattr(args, f)
     from . import engine
     was_deterministic = engine.deterministic()
     if args.deterministic:
@@ -234,6 +267,11 @@ def main(argv=None):
     except FileNotFoundError as e:
         raise SystemExit(f"[mdt-train] {e}\n[mdt-train] give --pretrained-bert / --pretrained-vit a local path, start from a "
                          f"checkpoint (--restore-file), or pass --random-init-encoders to train from random weights")
+    if lora_rank and rank == 0:
+        n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
+        n_frozen = sum(p.numel() for p in model.parameters() if not p.requires_grad)
+        print(f"[mdt-train] --lora-rank {lora_rank}: {len(model.lora_modules())} adapted QKV projections (targets {args.lora_targets}, "
+              f"alpha {args.lora_alpha:g}), {n_train} trainable / {n_frozen} frozen parameter elements", file=sys.stderr)
     model = model.cuda()
     half = args.fp16 or args.bf16 or args.fp8
     if half:
@@ -474,6 +512,12 @@ def main(argv=None):
         save(args.save_checkpoint, max_update)
     if rank == 0 and args.save_dir and not args.no_save:
         save(os.path.join(args.save_dir, "checkpoint_last.pt"), max_update)
+    if rank == 0 and save_merged:
+        # the adapters folded into the projections, under the cfg of a run without --lora-rank: a plain mDT checkpoint
+        check_guard(max_update)
+        plain = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("lora_rank", "lora_alpha", "lora_targets")})
+        ckpt.save_checkpoint(save_merged, model, plain, model_state=ckpt.merged_model_state(model, opt), num_updates=max_update,
+                             criterion_name=crit_cls.__name__, training_time=time.time() - t0)
     main.last_run = dict(model=model, criterion=crit, valid_batches=valid_batches, optimizer=opt, fp8=fp8_state)     # for tests / notebooks
     if fp8_state is not None:
         from . import fp8 as _fp8
