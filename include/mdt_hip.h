@@ -608,6 +608,26 @@ int mdt_lora_down(void* stream, int dtype, int64_t R, int n, int K, const void* 
                   const void* W, int64_t ldw, void* T, int64_t ldt, float alpha);
 int mdt_lora_up_add(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt,
                     const void* W, int64_t ldw, void* Y, int64_t ldy, float alpha);
+/* Epilogue forms of mdt_lora_up_add, for the adapters of the dense layers whose GEMM has a fused epilogue (the attention output
+ * projection, fc1, fc2): the same kernel, the same contract (lora_check), p = (T W)[r, c] in its fp32 accumulator, a lane owning
+ * 16 consecutive columns of one token; fp32 arithmetic, ONE rounding per stored element.
+ *   mdt_last_route(): "lora_up_drop", "lora_up_mul", "lora_up_act" (bf16), the same with "_f32" (fp32).
+ * mdt_lora_up_add_drop  Y[r, c] = Y[r, c] + (alpha s(r, c)) p,  s = keep(drop_seed, r N + c) / (1 - drop_p): the counters of
+ *                  MDT_EPI_DROPOUT and mdt_dropout, so the adapter sum enters res + dropout(x W^T + b) UNDER that GEMM's mask.
+ *                  An element whose counter is dropped keeps its bits; drop_p = 0 is mdt_lora_up_add bit for bit.
+ *                  0 <= drop_p < 1 and R N < 2^33, else MDT_ERR_ARG.
+ * mdt_lora_up_add_mul   Y[r, c] = Y[r, c] + (alpha p) aux[r, c], aux [R, N] of Y's type: the adapter's share of the FFN's du behind
+ *                  MDT_EPI_MULAUX (aux = u, the saved activation derivative).
+ * mdt_lora_up_act       v = pre[r, c] + alpha p (fp32, not rounded);  h = act(v) s,  u = act'(v) s: kinds, formulas and dropout
+ *                  counters of mdt_act_fwd (one device function serves both), so with T = 0 the two agree bit for bit.
+ *                  h may be pre; u may be NULL (a forward without a tape). */
+int mdt_lora_up_add_drop(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt,
+                         const void* W, int64_t ldw, void* Y, int64_t ldy, float alpha, float drop_p, uint64_t drop_seed);
+int mdt_lora_up_add_mul(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt,
+                        const void* W, int64_t ldw, void* Y, int64_t ldy, const void* aux, int64_t ld_aux, float alpha);
+int mdt_lora_up_act(void* stream, int dtype, int kind, int64_t R, int n, int N, const void* T, int64_t ldt,
+                    const void* W, int64_t ldw, const void* pre, int64_t ld_pre, void* h, int64_t ld_h,
+                    void* u, int64_t ld_u, float alpha, float drop_p, uint64_t drop_seed);
 int mdt_lora_wgrad_slab_rows(void);
 size_t mdt_lora_wgrad_workspace_bytes(int64_t R, int n, int N);
 int mdt_lora_wgrad(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt,

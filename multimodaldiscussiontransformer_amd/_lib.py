@@ -83,6 +83,9 @@ _SIGS = {
     "mdt_float_atomic_launches": ([_i], _i64),
     "mdt_lora_down": ([_vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _f], _i),
     "mdt_lora_up_add": ([_vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _f], _i),
+    "mdt_lora_up_add_drop": ([_vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f, C.c_uint64], _i),
+    "mdt_lora_up_add_mul": ([_vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f], _i),
+    "mdt_lora_up_act": ([_vp, _i, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f, C.c_uint64], _i),
     "mdt_lora_wgrad_slab_rows": ([], _i),
     "mdt_lora_wgrad_workspace_bytes": ([_i64, _i, _i], C.c_size_t),
     "mdt_lora_wgrad": ([_vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _f, _vp, C.c_size_t], _i),

@@ -190,6 +190,10 @@ def merged_model_state(model, optimizer=None) -> "OrderedDict[str, torch.Tensor]
         if getattr(m, "lora_A", None) is None:
             continue
         s = m.lora_alpha / m.lora_rank
+        if not hasattr(m, "lora_targets"):      # an adapted dense layer (modules/_fused.py AdaptedLinear): one pair beside its weight
+            a, b = sd.pop(name + ".lora_A.weight").float(), sd.pop(name + ".lora_B.weight").float()
+            sd[name + ".weight"] = sd[name + ".weight"].float() + s * (b @ a)
+            continue
         for t in m.lora_targets:
             a, b = sd.pop(m._lora_key(name + ".", t, "A")).float(), sd.pop(m._lora_key(name + ".", t, "B")).float()
             wkey = m._lora_key(name + ".", t, "A")[:-len("lora_A.weight")] + "weight"

@@ -9,33 +9,7 @@
 
 namespace mdt {
 
-template <int KIND>
-__device__ __forceinline__ void act_pair(float x, float s, float& h, float& u) {
-  if constexpr (KIND == MDT_ACT_GELU) {
-    h = gelu_erf(x) * s;
-    u = gelu_erf_grad(x) * s;
-  } else if constexpr (KIND == MDT_ACT_RELU) {
-    // not fmaxf: that returns the other operand for a NaN, and the optimiser's non-finite guard wants to see it
-    const bool pos = x > 0.f;
-    h = (pos || x != x ? x : 0.f) * s;
-    u = pos ? s : 0.f;
-  } else if constexpr (KIND == MDT_ACT_GELU_ACCURATE) {
-    // 0.5 x (1 + tanh(k (x + c x^3))), k = sqrt(2 / pi); derivative 0.5 (1 + t) + 0.5 x (1 - t^2) k (1 + 3 c x^2)
-    const float k = 0.7978845608028654f, c = 0.044715f;
-    const float x2 = x * x;
-    const float t = tanhf(k * (x + c * (x2 * x)));
-    h = 0.5f * x * (1.0f + t) * s;
-    u = (0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * (k * (1.0f + 3.0f * c * x2))) * s;
-  } else if constexpr (KIND == MDT_ACT_TANH) {
-    const float t = tanhf(x);
-    h = t * s;
-    u = (1.0f - t * t) * s;
-  } else {
-    h = x * s;
-    u = s;
-  }
-}
-
+// act_pair<KIND> (common.hpp): the five kinds, one element.
 // Flat grid-stride walk over the rows * (N / VN) vectors of the matrix (VN = 1: the scalar path, any N, stride and
 // alignment).  (r, cv) = (row, vector of the row) advances by the grid's stride without a division per step.
 // h may be pre: a lane reads its vector before it writes it, and no other lane touches it.

@@ -7,7 +7,10 @@
 //   lora_down_bf16_kernel     T^T = W X^T: both operands k-contiguous, 16-byte loads are the fragments; a lane ends up with four
 //                             consecutive T columns of one token (one 8-byte store)
 //   lora_up_add_bf16_kernel   Y^T += W^T T^T: a wave keeps the W fragments of its 64 columns in registers for all its rows; the
-//                             tile rows are interleaved so that a lane owns 16 consecutive Y columns (two 16-byte read-modify-writes)
+//                             tile rows are interleaved so that a lane owns 16 consecutive Y columns (two 16-byte read-modify-writes).
+//                             Its epilogue is a template parameter: the plain add (QKV, dx), and for the adapters of the dense layers
+//                             whose GEMMs end in fused epilogues the add under a dropout mask (o, fc2), the add times the saved
+//                             activation derivative (fc2's input gradient) and the add in front of the activation (fc1: h and u)
 //   lora_wgrad_bf16_kernel    dW = T^T X: both operands run along the token axis — 32-token stages of T and X in row-major LDS
 //                             images, fragments by ds_read_b64_tr_b16 (the situation of gemm_wgrad.hip).  A workgroup owns
 //                             (slab of LORA_SLAB token rows, column tile) and stores its fp32 partial [n, tile] with plain stores;
@@ -101,10 +104,37 @@ __global__ __launch_bounds__(256) void lora_down_plain_kernel(int64_t R, int n, 
 // A operand = W^T (rows: Y columns), B operand = T^T (columns: tokens).  A wave owns the 64 columns cb ... cb + 63 for all rows
 // of its workgroup.  Row i of tile t is column cb + (i >> 2) * 16 + t * 4 + (i & 3), so that the accumulators of lane group g
 // over the four tiles are the 16 consecutive columns cb + 16 g ... + 15 of token l & 15.
-template <int KS>
+//
+// Epilogues (EPI): what happens to p = (T W)[r, c] once it is in the accumulator.  Y is always read in its type, the arithmetic is
+// fp32, every stored element is rounded once.
+//   UP_ADD    Y = Y + alpha p                                        (mdt_lora_up_add)
+//   UP_DROP   Y = Y + (alpha s) p, s the dropout scale of counter r N + c; a dropped element keeps its bits   (..._up_add_drop)
+//   UP_MUL    Y = Y + (alpha p) aux                                  (mdt_lora_up_add_mul)
+//   UP_ACT+k  v = Y + alpha p (Y: the pre-activation, only read);  h = act_k(v) s,  u = act_k'(v) s, act_pair<k> (mdt_lora_up_act)
+enum { UP_ADD = 0, UP_DROP = 1, UP_MUL = 2, UP_ACT = 3 };
+template <typename T>
+struct UpEpi {
+  const T* aux;        // UP_MUL
+  int64_t ld_aux;
+  T* h;                // UP_ACT: h may be Y; u may be null
+  int64_t ld_h;
+  T* u;
+  int64_t ld_u;
+  DropCfg d;           // UP_DROP, UP_ACT (thresh 0: no dropout, every scale 1)
+};
+// one element: o0 = the new Y (UP_ACT: h), o1 = u.  y: Y's old value, s: the dropout scale, a: aux
+template <int EPI>
+__device__ __forceinline__ void up_elem(float p, float y, float alpha, float s, float a, float& o0, float& o1) {
+  if constexpr (EPI == UP_ADD) o0 = __builtin_fmaf(alpha, p, y);
+  else if constexpr (EPI == UP_DROP) o0 = __builtin_fmaf(alpha * s, p, y);
+  else if constexpr (EPI == UP_MUL) o0 = __builtin_fmaf(alpha * p, a, y);
+  else act_pair<EPI - UP_ACT>(__builtin_fmaf(alpha, p, y), s, o0, o1);
+}
+
+template <int KS, int EPI = UP_ADD>
 __global__ __launch_bounds__(256) void lora_up_add_bf16_kernel(int64_t R, int n, int N, const bf16_t* __restrict__ T, int64_t ldt,
                                                                const bf16_t* __restrict__ W, int64_t ldw, bf16_t* __restrict__ Y,
-                                                               int64_t ldy, float alpha, int rows_per_wg) {
+                                                               int64_t ldy, float alpha, int rows_per_wg, UpEpi<bf16_t> E) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, i = lane & 15;
   const int cb = (blockIdx.x * 4 + wave) * 64;
@@ -141,13 +171,52 @@ __global__ __launch_bounds__(256) void lora_up_add_bf16_kernel(int64_t R, int n,
     if (ok && c0 < N) {
       bf16_t* y = Y + r * ldy + c0;
       bf16x8 y0 = *(const bf16x8*)y, y1 = *(const bf16x8*)(y + 8);
+      if constexpr (EPI == UP_ADD) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        y0[j] = (bf16_t)__builtin_fmaf(alpha, acc[j >> 2][j & 3], (float)y0[j]);
-        y1[j] = (bf16_t)__builtin_fmaf(alpha, acc[2 + (j >> 2)][j & 3], (float)y1[j]);
+        for (int j = 0; j < 8; ++j) {
+          y0[j] = (bf16_t)__builtin_fmaf(alpha, acc[j >> 2][j & 3], (float)y0[j]);
+          y1[j] = (bf16_t)__builtin_fmaf(alpha, acc[2 + (j >> 2)][j & 3], (float)y1[j]);
+        }
+        *(bf16x8*)y = y0;
+        *(bf16x8*)(y + 8) = y1;
+      } else {
+        // column c0 + j of the row is acc[j >> 2][j & 3], j = 0 ... 15; its dropout counter r N + c0 + j (c0 and N are multiples
+        // of 16: every pair starts on an even counter)
+        float s[16];
+        const bool drop = (EPI == UP_DROP || EPI >= UP_ACT) && E.d.thresh != 0;
+#pragma unroll
+        for (int j = 0; j < 16; j += 2) {
+          if (drop) drop_scale2(E.d, (uint64_t)r * N + c0 + j, s[j], s[j + 1]);
+          else s[j] = s[j + 1] = 1.0f;
+        }
+        bf16x8 a0 = zero, a1 = zero, u0, u1;
+        if constexpr (EPI == UP_MUL) {
+          const bf16_t* a = E.aux + r * E.ld_aux + c0;
+          a0 = *(const bf16x8*)a;
+          a1 = *(const bf16x8*)(a + 8);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float o, v = 0.f;
+          up_elem<EPI>(acc[j >> 2][j & 3], (float)y0[j], alpha, s[j], (float)a0[j], o, v);
+          if (EPI != UP_DROP || s[j] != 0.f) y0[j] = (bf16_t)o;
+          u0[j] = (bf16_t)v;
+          up_elem<EPI>(acc[2 + (j >> 2)][j & 3], (float)y1[j], alpha, s[8 + j], (float)a1[j], o, v);
+          if (EPI != UP_DROP || s[8 + j] != 0.f) y1[j] = (bf16_t)o;
+          u1[j] = (bf16_t)v;
+        }
+        // h may be Y itself: this lane has read its 16 elements, and no other lane touches them
+        bf16_t* out = (EPI < UP_ACT || E.h == Y) ? y : E.h + r * E.ld_h + c0;
+        *(bf16x8*)out = y0;
+        *(bf16x8*)(out + 8) = y1;
+        if constexpr (EPI >= UP_ACT) {
+          if (E.u) {
+            bf16_t* up = E.u + r * E.ld_u + c0;
+            *(bf16x8*)up = u0;
+            *(bf16x8*)(up + 8) = u1;
+          }
+        }
       }
-      *(bf16x8*)y = y0;
-      *(bf16x8*)(y + 8) = y1;
     }
   }
 }
@@ -165,6 +234,30 @@ __global__ __launch_bounds__(256) void lora_up_add_plain_kernel(int64_t R, int n
   for (int k = 0; k < n; ++k) s += to_f32(t[k]) * to_f32(W[(int64_t)k * ldw + c]);
   T* y = Y + r * ldy + c;
   *y = from_f32<T>(__builtin_fmaf(alpha, s, to_f32(*y)));
+}
+
+// the three other epilogues, one thread per element (Y is not __restrict__: h may be Y)
+template <typename T, int EPI>
+__global__ __launch_bounds__(256) void lora_up_epi_plain_kernel(int64_t R, int n, int N, const T* __restrict__ Tm, int64_t ldt,
+                                                                const T* __restrict__ W, int64_t ldw, T* Y, int64_t ldy, float alpha,
+                                                                UpEpi<T> E) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= R * N) return;
+  const int64_t r = e / N;
+  const int c = (int)(e - r * N);
+  const T* t = Tm + r * ldt;
+  float p = 0.f;
+  for (int k = 0; k < n; ++k) p += to_f32(t[k]) * to_f32(W[(int64_t)k * ldw + c]);
+  const float s = ((EPI == UP_DROP || EPI >= UP_ACT) && E.d.thresh != 0) ? drop_scale(E.d, (uint64_t)e) : 1.0f;
+  const float a = EPI == UP_MUL ? to_f32(E.aux[r * E.ld_aux + c]) : 0.f;
+  float o, v = 0.f;
+  up_elem<EPI>(p, to_f32(Y[r * ldy + c]), alpha, s, a, o, v);
+  if constexpr (EPI >= UP_ACT) {
+    E.h[r * E.ld_h + c] = from_f32<T>(o);
+    if (E.u) E.u[r * E.ld_u + c] = from_f32<T>(v);
+  } else if (EPI != UP_DROP || s != 0.f) {
+    Y[r * ldy + c] = from_f32<T>(o);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ wgrad
@@ -316,12 +409,35 @@ static int lora_down_launch(hipStream_t st, int64_t R, int n, int K, const bf16_
                                                       T, ldt, alpha);
 }
 
-template <int KS>
+template <int KS, int EPI = UP_ADD>
 static int lora_up_launch(hipStream_t st, int64_t R, int n, int N, const bf16_t* T, int64_t ldt, const bf16_t* W, int64_t ldw,
-                          bf16_t* Y, int64_t ldy, float alpha) {
+                          bf16_t* Y, int64_t ldy, float alpha, const char* route = "lora_up", const UpEpi<bf16_t>& E = {}) {
   const int rows_per_wg = 256;
   const dim3 grid((unsigned)((N + 255) / 256), (unsigned)((R + rows_per_wg - 1) / rows_per_wg));
-  return launch_route<lora_up_add_bf16_kernel<KS>>("lora_up", grid, dim3(256), 0, st, R, n, N, T, ldt, W, ldw, Y, ldy, alpha, rows_per_wg);
+  return launch_route<lora_up_add_bf16_kernel<KS, EPI>>(route, grid, dim3(256), 0, st, R, n, N, T, ldt, W, ldw, Y, ldy, alpha,
+                                                        rows_per_wg, E);
+}
+
+// One of the epilogue forms of up_add (EPI != UP_ADD) in either dtype, after the entry point's checks.  ``route``: the bf16 name.
+template <int EPI>
+static int lora_up_epi(hipStream_t st, int dtype, const char* route, const char* route_f32, int64_t R, int n, int N, const void* T,
+                       int64_t ldt, const void* W, int64_t ldw, void* Y, int64_t ldy, float alpha, const void* aux, int64_t ld_aux,
+                       void* h, int64_t ld_h, void* u, int64_t ld_u, const DropCfg& d) {
+  if (dtype == MDT_F32) {
+    const UpEpi<float> E{(const float*)aux, ld_aux, (float*)h, ld_h, (float*)u, ld_u, d};
+    const int64_t blocks = (R * N + 255) / 256;
+    return launch_route<lora_up_epi_plain_kernel<float, EPI>>(route_f32, dim3((unsigned)blocks), dim3(256), 0, st, R, n, N, (const float*)T,
+                                                              ldt, (const float*)W, ldw, (float*)Y, ldy, alpha, E);
+  }
+  const UpEpi<bf16_t> E{(const bf16_t*)aux, ld_aux, (bf16_t*)h, ld_h, (bf16_t*)u, ld_u, d};
+  const bf16_t *t = (const bf16_t*)T, *w = (const bf16_t*)W;
+  bf16_t* y = (bf16_t*)Y;
+  const int ks = (n + 31) / 32;
+  if (ks <= 1) return lora_up_launch<1, EPI>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha, route, E);
+  if (ks <= 2) return lora_up_launch<2, EPI>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha, route, E);
+  if (ks <= 3) return lora_up_launch<3, EPI>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha, route, E);
+  if (ks <= 4) return lora_up_launch<4, EPI>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha, route, E);
+  return lora_up_launch<6, EPI>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha, route, E);
 }
 
 template <int NT, int CTW>
@@ -385,6 +501,68 @@ extern "C" int mdt_lora_up_add(void* stream, int dtype, int64_t R, int n, int N,
   if (ks <= 3) return lora_up_launch<3>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha);
   if (ks <= 4) return lora_up_launch<4>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha);
   return lora_up_launch<6>(st, R, n, N, t, ldt, w, ldw, y, ldy, alpha);
+}
+
+// what the two entry points with a dropout site check on top of lora_check
+static int lora_drop_check(const char* fn, int64_t R, int N, float drop_p) {
+  MDT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p=%f is not in [0, 1)", fn, drop_p);
+  MDT_CHECK_ARG(R * N < DROP_MAX_ELEMS, "%s: dropout site of %lld elements (R=%lld, N=%d; limit 2^33)", fn, (long long)(R * N),
+                (long long)R, N);
+  return MDT_OK;
+}
+
+extern "C" int mdt_lora_up_add_drop(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt, const void* W,
+                                    int64_t ldw, void* Y, int64_t ldy, float alpha, float drop_p, uint64_t drop_seed) {
+  const char* fn = "mdt_lora_up_add_drop";
+  const int es = (int)dtype_size(dtype);
+  if (int e = lora_check(fn, dtype, R, n, N, "N", {{"T", T, ldt, n, es}, {"W", W, ldw, N, es}, {"Y", Y, ldy, N, es}})) return e;
+  MDT_CHECK_ARG(R <= LORA_MAX_ROWS, "%s: R=%lld exceeds %lld rows", fn, (long long)R, (long long)LORA_MAX_ROWS);
+  if (int e = lora_drop_check(fn, R, N, drop_p)) return e;
+  if (R == 0) return MDT_OK;
+  return lora_up_epi<UP_DROP>((hipStream_t)stream, dtype, "lora_up_drop", "lora_up_drop_f32", R, n, N, T, ldt, W, ldw, Y, ldy, alpha,
+                              nullptr, 0, nullptr, 0, nullptr, 0, make_drop(drop_p, drop_seed));
+}
+
+extern "C" int mdt_lora_up_add_mul(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt, const void* W,
+                                   int64_t ldw, void* Y, int64_t ldy, const void* aux, int64_t ld_aux, float alpha) {
+  const char* fn = "mdt_lora_up_add_mul";
+  const int es = (int)dtype_size(dtype);
+  if (int e = lora_check(fn, dtype, R, n, N, "N",
+                         {{"T", T, ldt, n, es}, {"W", W, ldw, N, es}, {"Y", Y, ldy, N, es}, {"aux", aux, ld_aux, N, es}}))
+    return e;
+  MDT_CHECK_ARG(R <= LORA_MAX_ROWS, "%s: R=%lld exceeds %lld rows", fn, (long long)R, (long long)LORA_MAX_ROWS);
+  if (R == 0) return MDT_OK;
+  return lora_up_epi<UP_MUL>((hipStream_t)stream, dtype, "lora_up_mul", "lora_up_mul_f32", R, n, N, T, ldt, W, ldw, Y, ldy, alpha, aux,
+                             ld_aux, nullptr, 0, nullptr, 0, DropCfg{0, 0, 1.0f});
+}
+
+extern "C" int mdt_lora_up_act(void* stream, int dtype, int kind, int64_t R, int n, int N, const void* T, int64_t ldt, const void* W,
+                               int64_t ldw, const void* pre, int64_t ld_pre, void* h, int64_t ld_h, void* u, int64_t ld_u, float alpha,
+                               float drop_p, uint64_t drop_seed) {
+  const char* fn = "mdt_lora_up_act";
+  const int es = (int)dtype_size(dtype);
+  MDT_CHECK_ARG(kind >= MDT_ACT_GELU && kind <= MDT_ACT_LINEAR, "%s: kind %d is not an activation (0 ... 4)", fn, kind);
+  if (int e = lora_check(fn, dtype, R, n, N, "N",
+                         {{"T", T, ldt, n, es}, {"W", W, ldw, N, es}, {"pre", pre, ld_pre, N, es}, {"h", h, ld_h, N, es}}))
+    return e;
+  if (u)
+    if (int e = lora_check(fn, dtype, R, n, N, "N", {{"u", u, ld_u, N, es}})) return e;
+  MDT_CHECK_ARG(R <= LORA_MAX_ROWS, "%s: R=%lld exceeds %lld rows", fn, (long long)R, (long long)LORA_MAX_ROWS);
+  if (int e = lora_drop_check(fn, R, N, drop_p)) return e;
+  if (R == 0) return MDT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const DropCfg d = make_drop(drop_p, drop_seed);
+  void* y = const_cast<void*>(pre);        // the kernel's Y operand: only read by this epilogue (written only where h is pre)
+#define MDT_UP_ACT(K) \
+  case K: return lora_up_epi<UP_ACT + K>(st, dtype, "lora_up_act", "lora_up_act_f32", R, n, N, T, ldt, W, ldw, y, ld_pre, alpha, nullptr, 0, h, ld_h, u, ld_u, d)
+  switch (kind) {
+    MDT_UP_ACT(MDT_ACT_GELU);
+    MDT_UP_ACT(MDT_ACT_RELU);
+    MDT_UP_ACT(MDT_ACT_GELU_ACCURATE);
+    MDT_UP_ACT(MDT_ACT_TANH);
+    default: MDT_UP_ACT(MDT_ACT_LINEAR);
+  }
+#undef MDT_UP_ACT
 }
 
 extern "C" size_t mdt_lora_wgrad_workspace_bytes(int64_t R, int n, int N) {

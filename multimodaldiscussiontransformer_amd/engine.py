@@ -297,6 +297,15 @@ class Tape:
 # ------------------------------------------------------------------------------------------
 # parameter bundles
 @dataclass
+class LoraSlot:
+    """A low-rank adapter beside one dense layer [out, in] of a block: ``A`` [r, in], ``Bt`` [r, out] (the rows of B^T),
+    ``scale`` = alpha / r.  The layer computes x W^T + b + scale (x A^T) Bt."""
+    A: torch.nn.Parameter
+    Bt: torch.nn.Parameter
+    scale: float = 1.0
+
+
+@dataclass
 class BlockParams:
     """One transformer block.  ``qkv_w`` is the row-concatenation [Wq; Wk; Wv] (3D x D)."""
     qkv_w: torch.nn.Parameter
@@ -317,11 +326,20 @@ class BlockParams:
     lora_Bt: Optional[torch.nn.Parameter] = None
     lora_cols: Optional[tuple] = None
     lora_scale: float = 1.0
+    # adapters beside the attention output projection (A [r, D], Bt [r, D]), fc1 (A [r, D], Bt [r, F]) and fc2 (A [r, F], Bt [r, D])
+    lora_o: Optional[LoraSlot] = None
+    lora_fc1: Optional[LoraSlot] = None
+    lora_fc2: Optional[LoraSlot] = None
+
+    def dense_lora(self):
+        return [s for s in (self.lora_o, self.lora_fc1, self.lora_fc2) if s is not None]
 
     def all(self):
         base = [self.qkv_w, self.qkv_b, self.o_w, self.o_b, self.ln1_w, self.ln1_b, self.fc1_w, self.fc1_b,
                 self.fc2_w, self.fc2_b, self.ln2_w, self.ln2_b]
-        return base if self.lora_A is None else base + [self.lora_A, self.lora_Bt]
+        if self.lora_A is not None:
+            base = base + [self.lora_A, self.lora_Bt]
+        return base + [p for s in self.dense_lora() for p in (s.A, s.Bt)]
 
 
 @dataclass
@@ -493,6 +511,27 @@ def lora_bwd(tape: Tape, P: BlockParams, src: torch.Tensor, t: torch.Tensor, dqk
         ops.lora_up_add(dt, P.lora_A.data, dx)
 
 
+def lora_dense_bwd(tape: Tape, L: LoraSlot, src: torch.Tensor, t: torch.Tensor, g: torch.Tensor, dx: Optional[torch.Tensor]) -> torch.Tensor:
+    """Adjoint of a dense layer's adapter y += s (src A^T) Bt, ``g`` the gradient of that sum [R, out], ``t`` the stored src A^T:
+    dBt += s t^T g, dt = s g Bt^T, dA += dt^T src, and dx += dt A where ``dx`` (the output of the base layer's dgrad) is given.
+    → dt, for the caller whose dx takes another epilogue (fc2: times u).  Fixed-order weight gradients as in lora_bwd; a frozen
+    adapter launches nothing for them."""
+    r = L.A.shape[0]
+    gA, gBt = tape.pgrad(L.A), tape.pgrad(L.Bt)
+    ws = None
+    if gA is not None or gBt is not None:
+        wide = max(src.shape[1], g.shape[1])
+        ws = ordered_workspace(ops.lib.mdt_lora_wgrad_workspace_bytes(src.shape[0], r, wide), src.device)
+    if gBt is not None:
+        ops.lora_wgrad(t, g, gBt.view(r, g.shape[1]), alpha=L.scale, ws=ws)
+    dt = ops.lora_down(g, L.Bt.data, alpha=L.scale)
+    if gA is not None:
+        ops.lora_wgrad(dt, src, gA.view(r, src.shape[1]), ws=ws)
+    if dx is not None:
+        ops.lora_up_add(dt, L.A.data, dx)
+    return dt
+
+
 # ------------------------------------------------------------------------------------------
 # ops
 def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre_ln: bool, eps: float,
@@ -509,6 +548,12 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     the pre-activation itself, so the backward epilogue is a single multiply.  ``act``: the FFN activation, a name of
     ``ops.ACT_KINDS``.  "gelu" (erf form) is fused into fc1's epilogue; every other kind runs fc1 as a plain bias GEMM and
     ``ops.act_fwd`` then turns the pre-activation into h (in place) and u — the adjoint is the same for all of them.
+
+    Low-rank adapters (``P.lora_A`` on QKV; ``P.lora_o`` / ``P.lora_fc1`` / ``P.lora_fc2`` on the dense layers): t = x A^T by
+    ``ops.lora_down``, then the sum s t Bt joins the base GEMM's output in one pass — under the hidden-dropout mask the GEMM's
+    epilogue applied (``lora_up_add_drop``: o, fc2) or in front of the non-linearity (``lora_up_act``: fc1, which then runs as
+    a plain bias GEMM for every ``act``).  Backward: ``lora_dense_bwd``; fc2's share of du takes the multiply by u in
+    ``lora_up_add_mul``.  The block still takes exactly four dropout seeds.
 
     ``keep_rows`` (i32[R]): only these token rows of the block's OUTPUT are needed downstream (the last fusion
     layer feeds nothing but bottleneck token 0 and [CLS] of every comment to the graph / the head).  Keys and
@@ -527,6 +572,10 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     if P.lora_A is not None and f8 is not None:
         raise NotImplementedError("fp8 GEMMs on a block with low-rank adapters: the adapter sum enters the bf16 qkv buffer only "
                                   "(run adapters in bf16, or fp8 without --lora-rank)")
+    Lo, L1, L2 = P.lora_o, P.lora_fc1, P.lora_fc2
+    if P.dense_lora() and f8 is not None:
+        raise NotImplementedError("fp8 GEMMs on a block with low-rank adapters: the adapter sums of the output projection, fc1 and "
+                                  "fc2 enter bf16 buffers only (run adapters in bf16, or fp8 without --lora-rank)")
 
     def gather(src):
         """rows ``keep_rows`` of src (identity when the block keeps everything)"""
@@ -562,19 +611,43 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
                 lt_ = None
         ctx_full_, lse_ = ops.attention_fwd(qkv_, spec.nseq, spec.S, spec.H, **kw)
         ctx_, xk = gather(ctx_full_), gather(xd)
-        return qkv_, lt_, ctx_full_, lse_, ctx_, ops.gemm(ctx_, P.o_w.data, bias=P.o_b.data, residual=xk, drop_p=p_hidden, drop_seed=s_o)
+        t_ = ops.gemm(ctx_, P.o_w.data, bias=P.o_b.data, residual=xk, drop_p=p_hidden, drop_seed=s_o)
+        if Lo is not None:                 # the adapter's sum joins under the mask the GEMM's epilogue applied
+            lto = ops.lora_down(ctx_, Lo.A.data)
+            ops.lora_up_add_drop(lto, Lo.Bt.data, t_, alpha=Lo.scale, drop_p=p_hidden, drop_seed=s_o)
+            if not tape.inference:
+                lts["o"] = lto
+        return qkv_, lt_, ctx_full_, lse_, ctx_, t_
+
+    def fc2_fwd(h_, h8, res):
+        y_ = linear(f8, h_, P.fc2_w, "fc2", x8=h8, bias=P.fc2_b.data, residual=res, drop_p=p_hidden, drop_seed=s_f2)[0]
+        if L2 is not None:
+            lt2 = ops.lora_down(h_, L2.A.data)
+            ops.lora_up_add_drop(lt2, L2.Bt.data, y_, alpha=L2.scale, drop_p=p_hidden, drop_seed=s_f2)
+            if not tape.inference:
+                lts["fc2"] = lt2
+        return y_
 
     def ffn_fwd(src, src8, res):
         """FFN half: fc1 writes h and u (and, 8-bit, the quantised h that fc2 then reads), fc2 adds ``res``"""
+        if L1 is not None:      # the adapter's sum joins the stored pre-activation in front of the non-linearity, whatever its kind
+            pre_ = ops.gemm(src, P.fc1_w.data, bias=P.fc1_b.data)
+            lt1 = ops.lora_down(src, L1.A.data)
+            h_, u_ = ops.lora_up_act(lt1, L1.Bt.data, pre_, act, alpha=L1.scale, drop_p=p_act, drop_seed=s_act, out=pre_,
+                                     want_u=not tape.inference)
+            if not tape.inference:
+                lts["fc1"] = lt1
+            return u_, h_, fc2_fwd(h_, None, res)
         if act != "gelu":       # fc1 leaves the pre-activation; one more launch makes h (in place) and u of it
             pre_ = ops.gemm(src, P.fc1_w.data, bias=P.fc1_b.data)
             h_, u_ = ops.act_fwd(pre_, act, drop_p=p_act, drop_seed=s_act, out=pre_, want_u=not tape.inference)
-            return u_, h_, ops.gemm(h_, P.fc2_w.data, bias=P.fc2_b.data, residual=res, drop_p=p_hidden, drop_seed=s_f2)
+            return u_, h_, fc2_fwd(h_, None, res)
         u_ = torch.empty(src.shape[0], P.fc1_w.shape[0], dtype=src.dtype, device=src.device)
         h_, h8 = linear(f8, src, P.fc1_w, "fc1", x8=src8, q8_site=("fc2", id(P.fc2_w)), bias=P.fc1_b.data, aux=u_,
                         epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD, drop_p=p_act, drop_seed=s_act)
-        return u_, h_, linear(f8, h_, P.fc2_w, "fc2", x8=h8, bias=P.fc2_b.data, residual=res, drop_p=p_hidden, drop_seed=s_f2)[0]
+        return u_, h_, fc2_fwd(h_, h8, res)
 
+    lts = {}        # the stored t = x A^T of the dense adapters, for backward only
     # a_in / f_in: what the attention / FFN half reads; t: the attention half's output (its residual is always x)
     if not pre_ln:
         a_in = xd
@@ -595,18 +668,28 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
         wgrad(tape, gd, h, P.fc2_w, fc2_b)
         gb1 = tape.pgrad(P.fc1_b)           # fc1 bias gradient = colsum(du): fused into the GEMM epilogue
         det = _DETERMINISTIC                # ... or, in deterministic mode, summed from the stored du in a fixed order
+        # an fc2 adapter adds its share of du behind the GEMM, so the bias sum cannot ride on that GEMM's epilogue either
+        late = det or L2 is not None
+        dt2 = lora_dense_bwd(tape, L2, h, lts["fc2"], gd, None) if L2 is not None else None
         du, du8 = linear(f8, gd, P.fc2_w, "d_fc2", grad=True, q8_site=("d_fc1", id(P.fc1_w)), q8_grad=True, aux=u,
-                         epilogue=ops.EPI_MULAUX, colsum=None if (gb1 is None or det) else gb1.view(-1))
-        if det and gb1 is not None:
+                         epilogue=ops.EPI_MULAUX, colsum=None if (gb1 is None or late) else gb1.view(-1))
+        if L2 is not None:                  # dh is never materialised: the adapter's share takes the same multiply by u
+            ops.lora_up_add_mul(dt2, L2.A.data, du, u)
+        if late and gb1 is not None:
             colsum(du, out=gb1.view(-1))
         wgrad(tape, du, f_in, P.fc1_w, None)
-        return linear(f8, du, P.fc1_w, "d_fc1", grad=True, x8=du8, residual=dres)[0]     # 8-bit when the GEMM above handed over the quantised du
+        df = linear(f8, du, P.fc1_w, "d_fc1", grad=True, x8=du8, residual=dres)[0]     # 8-bit when the GEMM above handed over the quantised du
+        if L1 is not None:
+            lora_dense_bwd(tape, L1, f_in, lts["fc1"], du, df)
+        return df
 
     def attn_bwd(dtd, o_b, want_dx, dres=None):
         """attention half: ``dtd`` = gradient of the output projection behind its dropout (R rows; attention backward and the
         QKV weight gradient see all rows).  → gradient of the half's input (+ ``dres`` at the kept rows), None unless wanted"""
         wgrad(tape, dtd, ctx, P.o_w, o_b)
         dctx = ops.gemm(dtd, P.o_w.data, trans_b=True)
+        if Lo is not None:
+            lora_dense_bwd(tape, Lo, ctx, lts["o"], dtd, dctx)
         dqkv = _attention_bwd(tape, spec, kw, dctx, qkv, ctx_full, lse, spread)
         wgrad(tape, dqkv, a_in, P.qkv_w, P.qkv_b)
         dx_ = dgrad(dqkv, P.qkv_w, residual=None if dres is None else spread(dres)) if want_dx else None

@@ -162,22 +162,28 @@ class GraphormerModel(FairseqEncoderModel):
         prefix, fusion = self.pretrained_blocks()
         return [b.qkv_params() for b in prefix + fusion if b.qkv_params().lora_A is not None]
 
+    def lora_dense_modules(self):
+        """The dense layers (attention output projection, fc1, fc2: modules/_fused.py AdaptedLinear) that carry an adapter."""
+        prefix, fusion = self.pretrained_blocks()
+        return [m for b in prefix + fusion for m in b.dense_lora_layers().values() if m.lora_A is not None]
+
     def add_lora(self, rank: int, alpha=None, targets=("q", "v")):
         """Parameter-efficient fine-tuning: every parameter of the two pretrained encoders (``encoder_layer_ids``: embeddings and
-        blocks) is frozen and rank-``rank`` adapters are trained beside the fused QKV projection of every pretrained block —
+        blocks) is frozen and rank-``rank`` adapters are trained beside the targets of every pretrained block — q / k / v of the
+        fused QKV projection, ``out`` (attention output projection), ``fc1``, ``fc2``; "all": the six —
         of the fusion blocks only when the prefixes are frozen by --freeze_initial_encoders, which then keep running without a
         tape.  Poolers, ViT's final LayerNorm, the graph stacks, bottleneck tokens and the head stay as they are.  ``alpha``
         defaults to 2 * rank; the adapter sum is scaled by alpha / rank.  Call it after the pretrained weights are loaded and
-        before ``prepare_main_grads`` / FusedAdam.  → the number of adapted projections."""
+        before ``prepare_main_grads`` / FusedAdam.  → the number of adapted blocks."""
         import math
         from .. import fp8
-        from ..modules._fused import LORA_RANKS, parse_lora_targets
+        from ..modules._fused import LORA_RANKS, LORA_TARGETS, parse_lora_targets
         if getattr(self, "main_grad_flat", None) is not None:
             raise RuntimeError("add_lora after prepare_main_grads: the gradient arena was laid out without the adapters")
         if fp8.ACTIVE is not None:
             raise NotImplementedError("low-rank adapters with fp8 GEMMs enabled are not supported (the adapter sum enters the bf16 "
                                       "qkv buffer only): disable fp8 first")
-        if self.lora_modules():
+        if self.lora_modules() or self.lora_dense_modules():
             raise RuntimeError("add_lora: the model already has adapters")
         if rank not in LORA_RANKS:
             raise ValueError(f"add_lora: rank {rank} is not one of {LORA_RANKS}")
@@ -191,14 +197,19 @@ class GraphormerModel(FairseqEncoderModel):
                 p.requires_grad = False
         prefix, fusion = self.pretrained_blocks()
         blocks = fusion if getattr(self.args, "freeze_initial_encoders", False) else prefix + fusion
+        qkv = tuple(t for t in targets if t in LORA_TARGETS)
         for b in blocks:
-            b.qkv_params().add_lora(rank, alpha, targets)
+            if qkv:
+                b.qkv_params().add_lora(rank, alpha, qkv)
+            for name, m in b.dense_lora_layers().items():
+                if name in targets:
+                    m.add_lora(rank, alpha)
         return len(blocks)
 
     def merge_lora(self):
         """Fold every adapter into its projection (W_j += s B_j A_j, fp32, one rounding) and remove it: ``state_dict()`` then has
-        exactly the keys of a model built without adapters.  → the number of projections merged."""
-        mods = self.lora_modules()
+        exactly the keys of a model built without adapters.  → the number of layers merged (QKV projections and dense layers)."""
+        mods = self.lora_modules() + self.lora_dense_modules()
         for m in mods:
             m.merge_lora()
         if mods:
@@ -209,7 +220,7 @@ class GraphormerModel(FairseqEncoderModel):
         """As nn.Module's, with one allowance: a checkpoint WITHOUT adapter keys loads into an adapted model (fine-tuning from a
         full checkpoint) — the adapters keep their values and their keys are reported in the returned ``missing_keys``."""
         res = super().load_state_dict(state_dict, strict=strict, **kw)
-        for m in self.lora_modules():
+        for m in self.lora_modules() + self.lora_dense_modules():
             res.missing_keys.extend(m._lora_missing)
             m._lora_missing = []
         return res
@@ -244,7 +255,7 @@ class GraphormerModel(FairseqEncoderModel):
         if on and act != "gelu":
             raise NotImplementedError(f"enable_fp8 with --activation-fn {act}: the fp8 path quantises h inside fc1's fused gelu "
                                       "epilogue, which the other activations do not go through")
-        if on and self.lora_modules():
+        if on and (self.lora_modules() or self.lora_dense_modules()):
             raise NotImplementedError("enable_fp8 on a model with low-rank adapters is not supported: the adapter sum enters the "
                                       "bf16 qkv buffer only (train the adapters in bf16, or merge_lora() first)")
         from .. import engine

@@ -15,7 +15,7 @@ from types import SimpleNamespace
 import torch
 import torch.nn as nn
 
-from ..engine import BlockParams
+from ..engine import BlockParams, LoraSlot
 
 
 class QKVFusedMixin:
@@ -60,15 +60,84 @@ def _hf_init_linear(lin: nn.Linear, std: float = 0.02):
 
 
 LORA_RANKS = (8, 16, 32, 64)
-LORA_TARGETS = ("q", "k", "v")
+LORA_TARGETS = ("q", "k", "v")                      # the thirds of the fused QKV projection
+LORA_DENSE_TARGETS = ("out", "fc1", "fc2")          # attention.output.dense, intermediate.dense, output.dense
+LORA_ALL_TARGETS = LORA_TARGETS + LORA_DENSE_TARGETS
 
 
 def parse_lora_targets(targets) -> tuple:
-    """("q", "v") from "q,v" or a sequence: distinct names of q / k / v, returned in q, k, v order."""
+    """("q", "v") from "q,v" or a sequence: distinct names of q / k / v / out / fc1 / fc2, returned in that (canonical) order;
+    "all" stands for the six of them."""
     names = [t.strip() for t in targets.split(",")] if isinstance(targets, str) else list(targets)
-    if not names or any(t not in LORA_TARGETS for t in names) or len(set(names)) != len(names):
-        raise ValueError(f"LoRA targets {targets!r}: a non-empty list of distinct names out of q, k, v")
-    return tuple(t for t in LORA_TARGETS if t in names)
+    names = [u for t in names for u in (LORA_ALL_TARGETS if t == "all" else (t,))]
+    if not names or any(t not in LORA_ALL_TARGETS for t in names) or len(set(names)) != len(names):
+        raise ValueError(f"LoRA targets {targets!r}: a non-empty list of distinct names out of q, k, v, out, fc1, fc2 (or all)")
+    return tuple(t for t in LORA_ALL_TARGETS if t in names)
+
+
+class AdaptedLinear(nn.Linear):
+    """An ``nn.Linear`` of a pretrained block (attention.output.dense, intermediate.dense, output.dense) that may carry a low-rank
+    adapter: live parameters ``lora_A`` [r, in] and ``lora_Bt`` [r, out] (the rows of B^T — the operand layout of the kernels),
+    saved under PEFT's names ``lora_A.weight`` [r, in] / ``lora_B.weight`` [out, r].  Without an adapter it is an nn.Linear."""
+
+    def __init__(self, d_in, d_out):
+        super().__init__(d_in, d_out)
+        self.lora_A = self.lora_Bt = None
+        self.lora_rank, self.lora_alpha = 0, 0.0
+        self._lora_missing = []
+
+    def add_lora(self, rank: int, alpha: float):
+        if self.lora_A is not None:
+            raise RuntimeError("add_lora: this layer already has an adapter")
+        if rank not in LORA_RANKS:
+            raise ValueError(f"LoRA rank {rank}: one of {LORA_RANKS}")
+        w = self.weight
+        a = torch.empty(rank, self.in_features, dtype=torch.float32)
+        nn.init.kaiming_uniform_(a, a=math.sqrt(5))         # as an nn.Linear(in, r) weight; B = 0: the adapted layer starts as the base
+        self.lora_A = nn.Parameter(a.to(device=w.device, dtype=w.dtype))
+        self.lora_Bt = nn.Parameter(torch.zeros(rank, self.out_features, device=w.device, dtype=w.dtype))
+        self.lora_rank, self.lora_alpha = int(rank), float(alpha)
+
+    def lora_slot(self):
+        """The engine.LoraSlot of this layer, None without an adapter."""
+        return None if self.lora_A is None else LoraSlot(self.lora_A, self.lora_Bt, self.lora_alpha / self.lora_rank)
+
+    def merge_lora(self):
+        """W += s Bt^T A in fp32, rounded once to the parameter's dtype; the adapter is removed."""
+        if self.lora_A is None:
+            return
+        s = self.lora_alpha / self.lora_rank
+        with torch.no_grad():
+            self.weight.copy_((self.weight.float() + s * (self.lora_Bt.float().t() @ self.lora_A.float())).to(self.weight.dtype))
+        self.lora_A = self.lora_Bt = None
+        self.lora_rank, self.lora_alpha = 0, 0.0
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        if self.lora_A is None:
+            return
+        destination[prefix + "lora_A.weight"] = destination.pop(prefix + "lora_A")
+        destination[prefix + "lora_B.weight"] = destination.pop(prefix + "lora_Bt").t()
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        self._lora_missing = []
+        if self.lora_A is not None:
+            ka, kb = prefix + "lora_A.weight", prefix + "lora_B.weight"
+            if ka not in state_dict and kb not in state_dict:
+                # a checkpoint of the full model: the adapter keeps its values; GraphormerModel.load_state_dict reports the keys
+                self._lora_missing = [ka, kb]
+                state_dict[prefix + "lora_A"], state_dict[prefix + "lora_Bt"] = self.lora_A.data, self.lora_Bt.data
+            elif ka in state_dict and kb in state_dict:
+                state_dict[prefix + "lora_A"] = state_dict.pop(ka)
+                state_dict[prefix + "lora_Bt"] = state_dict.pop(kb).t()
+            # one of the two: the strict loader names the absent one
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+
+def _dense_lora_fields(out_dense, fc1_dense, fc2_dense) -> dict:
+    """The dense-adapter fields of engine.BlockParams of a block's three AdaptedLinear layers ({} without adapters)."""
+    slots = dict(lora_o=out_dense.lora_slot(), lora_fc1=fc1_dense.lora_slot(), lora_fc2=fc2_dense.lora_slot())
+    return {k: v for k, v in slots.items() if v is not None}
 
 
 class _SelfAttentionParams(QKVFusedMixin, nn.Module):
@@ -90,6 +159,8 @@ class _SelfAttentionParams(QKVFusedMixin, nn.Module):
         if self.lora_A is not None:
             raise RuntimeError("add_lora: this projection already has adapters")
         targets = parse_lora_targets(targets)
+        if any(t not in LORA_TARGETS for t in targets):
+            raise ValueError(f"LoRA targets {targets!r}: the fused QKV projection takes q, k, v only")
         if rank not in LORA_RANKS:
             raise ValueError(f"LoRA rank {rank}: one of {LORA_RANKS}")
         w = self.qkv_weight
@@ -153,7 +224,7 @@ class _SelfAttentionParams(QKVFusedMixin, nn.Module):
 class _DenseLN(nn.Module):
     def __init__(self, d_in, d_out, eps, with_ln=True):
         super().__init__()
-        self.dense = nn.Linear(d_in, d_out)
+        self.dense = AdaptedLinear(d_in, d_out)
         _hf_init_linear(self.dense)
         if with_ln:
             self.LayerNorm = nn.LayerNorm(d_out, eps=eps)
@@ -162,7 +233,7 @@ class _DenseLN(nn.Module):
 class _Dense(nn.Module):
     def __init__(self, d_in, d_out):
         super().__init__()
-        self.dense = nn.Linear(d_in, d_out)
+        self.dense = AdaptedLinear(d_in, d_out)
         _hf_init_linear(self.dense)
 
 
@@ -192,12 +263,16 @@ class BertLayer(nn.Module):
     def qkv_params(self) -> "_SelfAttentionParams":
         return self.attention.self
 
+    def dense_lora_layers(self) -> dict:
+        """{target name: AdaptedLinear} of the block's three dense layers"""
+        return {"out": self.attention.output.dense, "fc1": self.intermediate.dense, "fc2": self.output.dense}
+
     def block_params(self) -> BlockParams:
         a, o = self.attention, self.output
         return BlockParams(a.self.qkv_weight, a.self.qkv_bias, a.output.dense.weight, a.output.dense.bias,
                            a.output.LayerNorm.weight, a.output.LayerNorm.bias, self.intermediate.dense.weight,
                            self.intermediate.dense.bias, o.dense.weight, o.dense.bias, o.LayerNorm.weight, o.LayerNorm.bias,
-                           **a.self.lora_fields())
+                           **a.self.lora_fields(), **_dense_lora_fields(*self.dense_lora_layers().values()))
 
 
 class _ViTAttention(nn.Module):
@@ -228,12 +303,17 @@ class ViTLayer(nn.Module):
     def qkv_params(self) -> "_SelfAttentionParams":
         return self.attention.attention
 
+    def dense_lora_layers(self) -> dict:
+        """{target name: AdaptedLinear} of the block's three dense layers"""
+        return {"out": self.attention.output.dense, "fc1": self.intermediate.dense, "fc2": self.output.dense}
+
     def block_params(self) -> BlockParams:
         a = self.attention
         return BlockParams(a.attention.qkv_weight, a.attention.qkv_bias, a.output.dense.weight, a.output.dense.bias,
                            self.layernorm_before.weight, self.layernorm_before.bias, self.intermediate.dense.weight,
                            self.intermediate.dense.bias, self.output.dense.weight, self.output.dense.bias,
-                           self.layernorm_after.weight, self.layernorm_after.bias, **a.attention.lora_fields())
+                           self.layernorm_after.weight, self.layernorm_after.bias, **a.attention.lora_fields(),
+                           **_dense_lora_fields(*self.dense_lora_layers().values()))
 
 
 class _Pooler(nn.Module):

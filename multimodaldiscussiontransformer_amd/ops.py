@@ -21,7 +21,8 @@ __all__ = [
     "row_axpby", "row_scatter_add", "bert_embed_sum", "bert_embed_ln_rows", "vit_patchify", "vit_assemble", "vit_patch_embed", "graph_node_feature",
     "tanh_fwd", "tanh_bwd", "node_ce", "contrastive_loss", "fp8_quantize", "fp8_scale_update", "gemm_fp8", "cast", "transpose2d", "dropout", "dropout_mask",
     "sum_slices", "gemm_splitk_ordered", "colsum_ordered", "layernorm_bwd_ordered", "segments_of", "row_segment_sum",
-    "attn_bias_grad_ordered", "float_atomic_launches", "lora_down", "lora_up_add", "lora_wgrad", "LORA_WGRAD_SLAB",
+    "attn_bias_grad_ordered", "float_atomic_launches", "lora_down", "lora_up_add", "lora_up_add_drop", "lora_up_add_mul", "lora_up_act", "lora_wgrad",
+    "LORA_WGRAD_SLAB",
     "act_fwd", "ACT_KINDS", "ACT_GELU", "ACT_RELU", "ACT_GELU_ACCURATE", "ACT_TANH", "ACT_LINEAR",
     "EPI_BIAS", "EPI_GELU", "EPI_RESIDUAL", "EPI_DGELU", "EPI_ACCUM", "EPI_ATOMIC", "EPI_DROPOUT", "EPI_AUX_GRAD", "EPI_MULAUX", "EPI_ASUM",
 ]
@@ -354,6 +355,46 @@ def lora_up_add(t: torch.Tensor, w: torch.Tensor, y: torch.Tensor, alpha=1.0) ->
     assert w.shape[0] == n and y.shape == (R, N) and t.dtype == w.dtype == y.dtype
     check(lib.mdt_lora_up_add(stream(), dt(t), R, n, N, ptr(t), _2d(t), ptr(w), _2d(w), ptr(y), _2d(y), float(alpha)), "mdt_lora_up_add")
     return y
+
+
+def lora_up_add_drop(t: torch.Tensor, w: torch.Tensor, y: torch.Tensor, alpha=1.0, drop_p=0.0, drop_seed=0) -> torch.Tensor:
+    """y[R, N] += alpha * s * (t @ w), s the dropout scale of counter row*N + col of site ``drop_seed`` (the GEMM epilogue's and
+    ``dropout``'s): the adapter sum under the mask of ``res + dropout(x W^T + b)``.  Dropped elements keep their bits."""
+    R, n = t.shape
+    N = w.shape[1]
+    assert w.shape[0] == n and y.shape == (R, N) and t.dtype == w.dtype == y.dtype
+    check(lib.mdt_lora_up_add_drop(stream(), dt(t), R, n, N, ptr(t), _2d(t), ptr(w), _2d(w), ptr(y), _2d(y), float(alpha),
+                                   float(drop_p), int(drop_seed)), "mdt_lora_up_add_drop")
+    return y
+
+
+def lora_up_add_mul(t: torch.Tensor, w: torch.Tensor, y: torch.Tensor, aux: torch.Tensor, alpha=1.0) -> torch.Tensor:
+    """y[R, N] += alpha * (t @ w) * aux, in place (aux [R, N]: the saved activation derivative behind EPI_MULAUX)."""
+    R, n = t.shape
+    N = w.shape[1]
+    assert w.shape[0] == n and y.shape == (R, N) and aux.shape == (R, N) and t.dtype == w.dtype == y.dtype == aux.dtype
+    check(lib.mdt_lora_up_add_mul(stream(), dt(t), R, n, N, ptr(t), _2d(t), ptr(w), _2d(w), ptr(y), _2d(y), ptr(aux), _2d(aux),
+                                  float(alpha)), "mdt_lora_up_add_mul")
+    return y
+
+
+def lora_up_act(t: torch.Tensor, w: torch.Tensor, pre: torch.Tensor, kind, *, alpha=1.0, drop_p=0.0, drop_seed=0, want_u=True,
+                out=None, u=None):
+    """(h, u) = (act(v) * s, act'(v) * s) of v = pre + alpha * t @ w (fp32, not rounded): ``act_fwd`` with the adapter sum joining
+    the pre-activation.  ``out`` may be ``pre``; u as in ``act_fwd``."""
+    k = ACT_KINDS[kind] if isinstance(kind, str) else int(kind)
+    R, n = t.shape
+    N = w.shape[1]
+    assert w.shape[0] == n and pre.shape == (R, N) and t.dtype == w.dtype == pre.dtype
+    if out is None:
+        out = torch.empty_like(pre)
+    assert out.dtype == pre.dtype and out.shape == pre.shape
+    if u is None and want_u:
+        u = torch.empty(pre.shape, dtype=pre.dtype, device=pre.device)
+    assert u is None or (u.dtype == pre.dtype and u.shape == pre.shape)
+    check(lib.mdt_lora_up_act(stream(), dt(t), k, R, n, N, ptr(t), _2d(t), ptr(w), _2d(w), ptr(pre), _2d(pre), ptr(out), _2d(out),
+                              ptr(u), _2d(u) if u is not None else 0, float(alpha), float(drop_p), int(drop_seed)), "mdt_lora_up_act")
+    return out, u
 
 
 def lora_wgrad(t: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, alpha=1.0, ws=None) -> torch.Tensor:

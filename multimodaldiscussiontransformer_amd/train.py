@@ -89,11 +89,12 @@ def build_parser():
     # parameter-efficient fine-tuning (not reference flags): GraphormerModel.add_lora
     p.add_argument("--lora-rank", type=int, default=0,
                    help="not a reference flag: freeze the pretrained BERT / ViT embeddings and blocks and train rank-N adapters (8, 16, 32 "
-                        "or 64) beside the QKV projection of every pretrained block (with --freeze_initial_encoders: of the fusion "
+                        "or 64) beside the --lora-targets layers of every pretrained block (with --freeze_initial_encoders: of the fusion "
                         "blocks); 0: off")
     p.add_argument("--lora-alpha", type=float, default=None, help="adapter scale numerator: the adapter sum is scaled by alpha / rank "
                    "(finite, > 0; default 2 * rank)")
-    p.add_argument("--lora-targets", default=None, help="comma list out of q,k,v: the projections that get adapters (default q,v)")
+    p.add_argument("--lora-targets", default=None, help="comma list out of q,k,v,out,fc1,fc2 (out: the attention output "
+                   "projection; fc1 / fc2: the FFN's two dense layers), or all: the layers that get adapters (default q,v)")
     p.add_argument("--save-merged", default="", help="with --lora-rank: also write, at the end, a plain checkpoint with the adapters "
                    "folded into the projections (GraphormerModel.merge_lora) — it loads into a model built without --lora-rank")
     p.add_argument("--log-interval", type=int, default=10)
@@ -270,7 +271,9 @@ def main(argv=None):
     if lora_rank and rank == 0:
         n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
         n_frozen = sum(p.numel() for p in model.parameters() if not p.requires_grad)
-        print(f"[mdt-train] --lora-rank {lora_rank}: {len(model.lora_modules())} adapted QKV projections (targets {args.lora_targets}, "
+        n_dense = len(model.lora_dense_modules())
+        print(f"[mdt-train] --lora-rank {lora_rank}: {len(model.lora_modules())} adapted QKV projections"
+              f"{f' and {n_dense} adapted dense layers' if n_dense else ''} (targets {args.lora_targets}, "
               f"alpha {args.lora_alpha:g}), {n_train} trainable / {n_frozen} frozen parameter elements", file=sys.stderr)
     model = model.cuda()
     half = args.fp16 or args.bf16 or args.fp8
