@@ -50,6 +50,39 @@ def deterministic() -> bool:
     return _DETERMINISTIC
 
 
+# ------------------------------------------------------------------------------------------
+# activation recomputation: a process-wide policy, read by the modules when they record a pretrained BERT / ViT block and handed
+# to transformer_block, which captures it in the block's adjoint.  "none" (the default): the tape keeps every activation of
+# every block until backward reaches it.  "ffn": u, h and the fc1 / fc2 adapters' t are dropped after the forward and made
+# again from the kept FFN input right before the FFN's adjoint (one more fc1 GEMM per block).  "block": nothing of a block is
+# kept but its input and output; the adjoint first runs the block's forward again from the same seeds.  The forward has no float
+# atomics and dropout masks are functions of the seeds, so a replay writes the bits the first pass wrote.
+RECOMPUTE_POLICIES = ("none", "ffn", "block")
+
+
+def _checked_policy(policy) -> str:
+    if policy not in RECOMPUTE_POLICIES:
+        raise ValueError(f"activation recomputation policy {policy!r} is not one of {', '.join(RECOMPUTE_POLICIES)}")
+    return policy
+
+
+RECOMPUTE_FP8_WHY = ("a replayed forward would record the step's amax a second time and take the fp8 producer slots again, so the "
+                     "delayed scales of the next step would differ from a run without recomputation")
+_RECOMPUTE = _checked_policy(os.environ.get("MDT_RECOMPUTE", "none") or "none")
+
+
+def set_recompute(policy: str) -> None:
+    global _RECOMPUTE
+    _checked_policy(policy)
+    if policy != "none" and F8.ACTIVE is not None:
+        raise NotImplementedError(f"activation recomputation with fp8 GEMMs: {RECOMPUTE_FP8_WHY} (disable fp8 first)")
+    _RECOMPUTE = policy
+
+
+def recompute() -> str:
+    return _RECOMPUTE
+
+
 _ORDERED_WS: dict = {}
 
 
@@ -158,6 +191,11 @@ class Tape:
     #     an image-branch activation — is allocated from the side stream's pool (``grad_buf``), so the allocator
     #     recycles it in side-stream order; a dense gradient handed over by an op (``add_grad``) falls back to
     #     ``record_stream``.
+    #   * buffer lifetime: the buffer of a Var is written only between the op that made it and the forward of the first block
+    #     that reads it (``rows_mix`` is the only in-place writer, and every exchange sits in front of its reader); afterwards
+    #     nothing writes it until the tape is dropped.  Adjoints read ``x.data`` at backward time, and a block recorded under the
+    #     "block" recomputation policy replays its whole forward from it — on the stream its adjoint runs on, so the replay of
+    #     an image-branch block allocates and frees on the side stream inside the recorded ``on_side`` region.
     def enable_side(self, device):
         # Deterministic mode runs the tape on ONE stream.  Both branch streams accumulate (read-modify-write) into shared
         # destinations — the bottleneck exchanges' gradient buffers (rows_mix, take_rows, scatter_rows, graph_node_features
@@ -535,7 +573,8 @@ def lora_dense_bwd(tape: Tape, L: LoraSlot, src: torch.Tensor, t: torch.Tensor, 
 # ------------------------------------------------------------------------------------------
 # ops
 def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre_ln: bool, eps: float,
-                      p_hidden: float = 0.0, p_attn: float = 0.0, p_act: float = 0.0, keep_rows=None, act: str = "gelu") -> Var:
+                      p_hidden: float = 0.0, p_attn: float = 0.0, p_act: float = 0.0, keep_rows=None, act: str = "gelu",
+                      recompute: str = "none") -> Var:
     """One encoder block (post-LN: HF BertLayer / Graphormer layer; pre-LN: HF ViTLayer or
     Graphormer with --pre-layernorm).  7 GEMM-class launches + attention + 2 LayerNorms
     forward; the adjoint mirrors it with the residual adds folded into epilogues.  The attention half
@@ -559,7 +598,12 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     layer feeds nothing but bottleneck token 0 and [CLS] of every comment to the graph / the head).  Keys and
     values still come from every row, but the output projection, both LayerNorms and the FFN — three quarters of
     the block's GEMM work — run on the R kept rows only, and the block returns [R, D] in ``keep_rows`` order.
-    Exact: the dropped rows' outputs are dead values in the reference too."""
+    Exact: the dropped rows' outputs are dead values in the reference too.
+
+    ``recompute`` (a name of RECOMPUTE_POLICIES; ignored by a forward-only tape): "ffn" drops u, h and the fc1 / fc2 adapters' t
+    after the forward and makes them again from the kept FFN input in front of ``ffn_bwd``; "block" keeps nothing but ``x`` and
+    the output, and the adjoint runs ``run`` — the same launches, seeds, ``keep_rows`` and ``spec`` — a second time before the
+    unchanged ``bwd``.  Neither draws a seed, so every dropout site of the tape keeps its seed under every policy."""
     xd = x.data
     s_attn, s_o, s_act, s_f2 = (tape.next_seed() for _ in range(4))
     kw = dict(spec.kwargs(), drop_p=p_attn, drop_seed=s_attn)
@@ -576,6 +620,11 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     if P.dense_lora() and f8 is not None:
         raise NotImplementedError("fp8 GEMMs on a block with low-rank adapters: the adapter sums of the output projection, fc1 and "
                                   "fc2 enter bf16 buffers only (run adapters in bf16, or fp8 without --lora-rank)")
+    # read here, once, and captured by the adjoint: autograd runs the backward on another thread, after the caller may have
+    # switched the process-wide policy.  A forward-only tape (or region of one) keeps nothing, so there is nothing to recompute
+    policy = "none" if tape.inference else _checked_policy(recompute)
+    if policy != "none" and f8 is not None:
+        raise NotImplementedError(f"transformer_block(recompute={policy!r}) with fp8 GEMMs: {RECOMPUTE_FP8_WHY}")
 
     def gather(src):
         """rows ``keep_rows`` of src (identity when the block keeps everything)"""
@@ -601,123 +650,154 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
             return (*ops.layernorm_fwd(x_, lw.data, lb.data, eps), None)
         return (*ops.layernorm_fwd(x_, lw.data, lb.data, eps, q8=slot[:4]), (slot[0], slot[4]))
 
-    def attn_fwd(src, src8):
-        """attention half: QKV of ``src`` (all rows), attention, output projection + residual x on the kept rows"""
-        qkv_, _ = linear(f8, src, P.qkv_w, "qkv", x8=src8, bias=P.qkv_b.data)
-        lt_ = None
-        if P.lora_A is not None:           # the adapters' sum joins qkv before attention reads it; t is kept for backward only
-            lt_ = lora_fwd(P, src, qkv_)
-            if tape.inference:
-                lt_ = None
-        ctx_full_, lse_ = ops.attention_fwd(qkv_, spec.nseq, spec.S, spec.H, **kw)
-        ctx_, xk = gather(ctx_full_), gather(xd)
-        t_ = ops.gemm(ctx_, P.o_w.data, bias=P.o_b.data, residual=xk, drop_p=p_hidden, drop_seed=s_o)
-        if Lo is not None:                 # the adapter's sum joins under the mask the GEMM's epilogue applied
-            lto = ops.lora_down(ctx_, Lo.A.data)
-            ops.lora_up_add_drop(lto, Lo.Bt.data, t_, alpha=Lo.scale, drop_p=p_hidden, drop_seed=s_o)
-            if not tape.inference:
-                lts["o"] = lto
-        return qkv_, lt_, ctx_full_, lse_, ctx_, t_
+    def run():
+        """The block's forward from ``xd`` with the seeds drawn above → (output, adjoint).  The adjoint's closure is what keeps
+        the activations: a caller that drops it keeps nothing of the block, and a second call makes the same tensors again."""
+        def attn_fwd(src, src8):
+            """attention half: QKV of ``src`` (all rows), attention, output projection + residual x on the kept rows"""
+            qkv_, _ = linear(f8, src, P.qkv_w, "qkv", x8=src8, bias=P.qkv_b.data)
+            lt_ = None
+            if P.lora_A is not None:           # the adapters' sum joins qkv before attention reads it; t is kept for backward only
+                lt_ = lora_fwd(P, src, qkv_)
+                if tape.inference:
+                    lt_ = None
+            ctx_full_, lse_ = ops.attention_fwd(qkv_, spec.nseq, spec.S, spec.H, **kw)
+            ctx_, xk = gather(ctx_full_), gather(xd)
+            t_ = ops.gemm(ctx_, P.o_w.data, bias=P.o_b.data, residual=xk, drop_p=p_hidden, drop_seed=s_o)
+            if Lo is not None:                 # the adapter's sum joins under the mask the GEMM's epilogue applied
+                lto = ops.lora_down(ctx_, Lo.A.data)
+                ops.lora_up_add_drop(lto, Lo.Bt.data, t_, alpha=Lo.scale, drop_p=p_hidden, drop_seed=s_o)
+                if not tape.inference:
+                    lts["o"] = lto
+            return qkv_, lt_, ctx_full_, lse_, ctx_, t_
 
-    def fc2_fwd(h_, h8, res):
-        y_ = linear(f8, h_, P.fc2_w, "fc2", x8=h8, bias=P.fc2_b.data, residual=res, drop_p=p_hidden, drop_seed=s_f2)[0]
-        if L2 is not None:
-            lt2 = ops.lora_down(h_, L2.A.data)
-            ops.lora_up_add_drop(lt2, L2.Bt.data, y_, alpha=L2.scale, drop_p=p_hidden, drop_seed=s_f2)
-            if not tape.inference:
-                lts["fc2"] = lt2
-        return y_
+        def fc2_fwd(h_, h8, res):
+            y_ = linear(f8, h_, P.fc2_w, "fc2", x8=h8, bias=P.fc2_b.data, residual=res, drop_p=p_hidden, drop_seed=s_f2)[0]
+            if L2 is not None:
+                lt2 = ops.lora_down(h_, L2.A.data)
+                ops.lora_up_add_drop(lt2, L2.Bt.data, y_, alpha=L2.scale, drop_p=p_hidden, drop_seed=s_f2)
+                if not tape.inference:
+                    lts["fc2"] = lt2
+            return y_
 
-    def ffn_fwd(src, src8, res):
-        """FFN half: fc1 writes h and u (and, 8-bit, the quantised h that fc2 then reads), fc2 adds ``res``"""
-        if L1 is not None:      # the adapter's sum joins the stored pre-activation in front of the non-linearity, whatever its kind
-            pre_ = ops.gemm(src, P.fc1_w.data, bias=P.fc1_b.data)
-            lt1 = ops.lora_down(src, L1.A.data)
-            h_, u_ = ops.lora_up_act(lt1, L1.Bt.data, pre_, act, alpha=L1.scale, drop_p=p_act, drop_seed=s_act, out=pre_,
-                                     want_u=not tape.inference)
-            if not tape.inference:
-                lts["fc1"] = lt1
-            return u_, h_, fc2_fwd(h_, None, res)
-        if act != "gelu":       # fc1 leaves the pre-activation; one more launch makes h (in place) and u of it
-            pre_ = ops.gemm(src, P.fc1_w.data, bias=P.fc1_b.data)
-            h_, u_ = ops.act_fwd(pre_, act, drop_p=p_act, drop_seed=s_act, out=pre_, want_u=not tape.inference)
-            return u_, h_, fc2_fwd(h_, None, res)
-        u_ = torch.empty(src.shape[0], P.fc1_w.shape[0], dtype=src.dtype, device=src.device)
-        h_, h8 = linear(f8, src, P.fc1_w, "fc1", x8=src8, q8_site=("fc2", id(P.fc2_w)), bias=P.fc1_b.data, aux=u_,
-                        epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD, drop_p=p_act, drop_seed=s_act)
-        return u_, h_, fc2_fwd(h_, h8, res)
+        def fc1_fwd(src, src8):
+            """fc1 and the activation: → (u, h, the 8-bit h or None).  The "ffn" policy's adjoint calls it a second time."""
+            if L1 is not None:      # the adapter's sum joins the stored pre-activation in front of the non-linearity, whatever its kind
+                pre_ = ops.gemm(src, P.fc1_w.data, bias=P.fc1_b.data)
+                lt1 = ops.lora_down(src, L1.A.data)
+                h_, u_ = ops.lora_up_act(lt1, L1.Bt.data, pre_, act, alpha=L1.scale, drop_p=p_act, drop_seed=s_act, out=pre_,
+                                         want_u=not tape.inference)
+                if not tape.inference:
+                    lts["fc1"] = lt1
+                return u_, h_, None
+            if act != "gelu":       # fc1 leaves the pre-activation; one more launch makes h (in place) and u of it
+                pre_ = ops.gemm(src, P.fc1_w.data, bias=P.fc1_b.data)
+                h_, u_ = ops.act_fwd(pre_, act, drop_p=p_act, drop_seed=s_act, out=pre_, want_u=not tape.inference)
+                return u_, h_, None
+            u_ = torch.empty(src.shape[0], P.fc1_w.shape[0], dtype=src.dtype, device=src.device)
+            h_, h8 = linear(f8, src, P.fc1_w, "fc1", x8=src8, q8_site=("fc2", id(P.fc2_w)), bias=P.fc1_b.data, aux=u_,
+                            epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD, drop_p=p_act, drop_seed=s_act)
+            return u_, h_, h8
 
-    lts = {}        # the stored t = x A^T of the dense adapters, for backward only
-    # a_in / f_in: what the attention / FFN half reads; t: the attention half's output (its residual is always x)
-    if not pre_ln:
-        a_in = xd
-        qkv, lt, ctx_full, lse, ctx, t = attn_fwd(a_in, None)
-        f_in, m1, r1, f_in8 = ln8(t, P.ln1_w, P.ln1_b, P.fc1_w, "fc1")
-        u, h, y = ffn_fwd(f_in, f_in8, f_in)
-        out, m2, r2 = ops.layernorm_fwd(y, P.ln2_w.data, P.ln2_b.data, eps)
-    else:
-        a_in, m1, r1, a_in8 = ln8(xd, P.ln1_w, P.ln1_b, P.qkv_w, "qkv")
-        qkv, lt, ctx_full, lse, ctx, t = attn_fwd(a_in, a_in8)
-        f_in, m2, r2, f_in8 = ln8(t, P.ln2_w, P.ln2_b, P.fc1_w, "fc1")
-        u, h, out = ffn_fwd(f_in, f_in8, t)
-    o = Var(out)
+        def ffn_fwd(src, src8, res):
+            """FFN half: fc1 writes h and u (and, 8-bit, the quantised h that fc2 then reads), fc2 adds ``res``"""
+            u_, h_, h8 = fc1_fwd(src, src8)
+            return u_, h_, fc2_fwd(h_, h8, res)
 
-    def ffn_bwd(gd, fc2_b, dres):
-        """FFN half: ``gd`` = gradient of fc2's output behind its dropout; ``fc2_b``: the bias whose gradient rides on the
-        weight-gradient GEMM (None: summed elsewhere).  → gradient of the half's input (+ ``dres``)"""
-        wgrad(tape, gd, h, P.fc2_w, fc2_b)
-        gb1 = tape.pgrad(P.fc1_b)           # fc1 bias gradient = colsum(du): fused into the GEMM epilogue
-        det = _DETERMINISTIC                # ... or, in deterministic mode, summed from the stored du in a fixed order
-        # an fc2 adapter adds its share of du behind the GEMM, so the bias sum cannot ride on that GEMM's epilogue either
-        late = det or L2 is not None
-        dt2 = lora_dense_bwd(tape, L2, h, lts["fc2"], gd, None) if L2 is not None else None
-        du, du8 = linear(f8, gd, P.fc2_w, "d_fc2", grad=True, q8_site=("d_fc1", id(P.fc1_w)), q8_grad=True, aux=u,
-                         epilogue=ops.EPI_MULAUX, colsum=None if (gb1 is None or late) else gb1.view(-1))
-        if L2 is not None:                  # dh is never materialised: the adapter's share takes the same multiply by u
-            ops.lora_up_add_mul(dt2, L2.A.data, du, u)
-        if late and gb1 is not None:
-            colsum(du, out=gb1.view(-1))
-        wgrad(tape, du, f_in, P.fc1_w, None)
-        df = linear(f8, du, P.fc1_w, "d_fc1", grad=True, x8=du8, residual=dres)[0]     # 8-bit when the GEMM above handed over the quantised du
-        if L1 is not None:
-            lora_dense_bwd(tape, L1, f_in, lts["fc1"], du, df)
-        return df
-
-    def attn_bwd(dtd, o_b, want_dx, dres=None):
-        """attention half: ``dtd`` = gradient of the output projection behind its dropout (R rows; attention backward and the
-        QKV weight gradient see all rows).  → gradient of the half's input (+ ``dres`` at the kept rows), None unless wanted"""
-        wgrad(tape, dtd, ctx, P.o_w, o_b)
-        dctx = ops.gemm(dtd, P.o_w.data, trans_b=True)
-        if Lo is not None:
-            lora_dense_bwd(tape, Lo, ctx, lts["o"], dtd, dctx)
-        dqkv = _attention_bwd(tape, spec, kw, dctx, qkv, ctx_full, lse, spread)
-        wgrad(tape, dqkv, a_in, P.qkv_w, P.qkv_b)
-        dx_ = dgrad(dqkv, P.qkv_w, residual=None if dres is None else spread(dres)) if want_dx else None
-        if P.lora_A is not None:
-            lora_bwd(tape, P, a_in, lt, dqkv, dx_)
-        return dx_
-
-    def bwd(g):
-        ride = _WGRAD_ASUM and dyd_rides(g)     # bias gradients ride on the weight-gradient GEMMs (wgrad) where they can
+        lts = {}        # the stored t = x A^T of the dense adapters, for backward only
+        # a_in / f_in: what the attention / FFN half reads; t: the attention half's output (its residual is always x)
         if not pre_ln:
-            dy, dyd = _ln_bwd_dense(tape, g, y, P.ln2_w, P.ln2_b, m2, r2, None if ride else P.fc2_b, p_hidden, s_f2)
-            df = ffn_bwd(dyd, P.fc2_b if ride else None, dy)
-            dt_, dtd = _ln_bwd_dense(tape, df, t, P.ln1_w, P.ln1_b, m1, r1, None if ride else P.o_b, p_hidden, s_o)
-            dx = attn_bwd(dtd, P.o_b if ride else None, x.needs_grad, dt_)
-            if x.needs_grad:
-                tape.add_grad(x, dx)
+            a_in = xd
+            qkv, lt, ctx_full, lse, ctx, t = attn_fwd(a_in, None)
+            f_in, m1, r1, f_in8 = ln8(t, P.ln1_w, P.ln1_b, P.fc1_w, "fc1")
+            u, h, y = ffn_fwd(f_in, f_in8, f_in)
+            out, m2, r2 = ops.layernorm_fwd(y, P.ln2_w.data, P.ln2_b.data, eps)
         else:
-            gd = ops.dropout(g, p_hidden, s_f2) if p_hidden > 0 else g     # fc2's output went through hidden dropout
-            df = ffn_bwd(gd, P.fc2_b, None)
-            dt_, dtd = _ln_bwd_dense(tape, df, t, P.ln2_w, P.ln2_b, m2, r2, None if ride else P.o_b, p_hidden, s_o, add=g)
-            da = attn_bwd(dtd, P.o_b if ride else None, True)
-            if x.needs_grad:
-                tape.add_grad(x, _ln_bwd(tape, da, xd, P.ln1_w, P.ln1_b, m1, r1, add=spread(dt_)))
-            else:   # LayerNorm parameters still need their gradients
-                _ln_bwd(tape, da, xd, P.ln1_w, P.ln1_b, m1, r1)
-        if tape.on_params_ready:
-            tape.on_params_ready(P.all())
+            a_in, m1, r1, a_in8 = ln8(xd, P.ln1_w, P.ln1_b, P.qkv_w, "qkv")
+            qkv, lt, ctx_full, lse, ctx, t = attn_fwd(a_in, a_in8)
+            f_in, m2, r2, f_in8 = ln8(t, P.ln2_w, P.ln2_b, P.fc1_w, "fc1")
+            u, h, out = ffn_fwd(f_in, f_in8, t)
+        if policy == "ffn":     # fc2 has been enqueued behind h: u, h and the FFN adapters' t are made again from f_in in ffn_bwd
+            u = h = None
+            lts.pop("fc1", None)
+            lts.pop("fc2", None)
 
+        def ffn_bwd(gd, fc2_b, dres):
+            """FFN half: ``gd`` = gradient of fc2's output behind its dropout; ``fc2_b``: the bias whose gradient rides on the
+            weight-gradient GEMM (None: summed elsewhere).  → gradient of the half's input (+ ``dres``)"""
+            nonlocal u, h
+            if policy == "ffn":     # the fc1 path the forward took, from the same seed: the same bits
+                u, h, _ = fc1_fwd(f_in, None)
+                if L2 is not None:
+                    lts["fc2"] = ops.lora_down(h, L2.A.data)
+            wgrad(tape, gd, h, P.fc2_w, fc2_b)
+            gb1 = tape.pgrad(P.fc1_b)           # fc1 bias gradient = colsum(du): fused into the GEMM epilogue
+            det = _DETERMINISTIC                # ... or, in deterministic mode, summed from the stored du in a fixed order
+            # an fc2 adapter adds its share of du behind the GEMM, so the bias sum cannot ride on that GEMM's epilogue either
+            late = det or L2 is not None
+            dt2 = lora_dense_bwd(tape, L2, h, lts["fc2"], gd, None) if L2 is not None else None
+            du, du8 = linear(f8, gd, P.fc2_w, "d_fc2", grad=True, q8_site=("d_fc1", id(P.fc1_w)), q8_grad=True, aux=u,
+                             epilogue=ops.EPI_MULAUX, colsum=None if (gb1 is None or late) else gb1.view(-1))
+            if L2 is not None:                  # dh is never materialised: the adapter's share takes the same multiply by u
+                ops.lora_up_add_mul(dt2, L2.A.data, du, u)
+            if late and gb1 is not None:
+                colsum(du, out=gb1.view(-1))
+            wgrad(tape, du, f_in, P.fc1_w, None)
+            df = linear(f8, du, P.fc1_w, "d_fc1", grad=True, x8=du8, residual=dres)[0]     # 8-bit when the GEMM above handed over the quantised du
+            if L1 is not None:
+                lora_dense_bwd(tape, L1, f_in, lts["fc1"], du, df)
+            if policy == "ffn":
+                u = h = None
+            return df
+
+        def attn_bwd(dtd, o_b, want_dx, dres=None):
+            """attention half: ``dtd`` = gradient of the output projection behind its dropout (R rows; attention backward and the
+            QKV weight gradient see all rows).  → gradient of the half's input (+ ``dres`` at the kept rows), None unless wanted"""
+            wgrad(tape, dtd, ctx, P.o_w, o_b)
+            dctx = ops.gemm(dtd, P.o_w.data, trans_b=True)
+            if Lo is not None:
+                lora_dense_bwd(tape, Lo, ctx, lts["o"], dtd, dctx)
+            dqkv = _attention_bwd(tape, spec, kw, dctx, qkv, ctx_full, lse, spread)
+            wgrad(tape, dqkv, a_in, P.qkv_w, P.qkv_b)
+            dx_ = dgrad(dqkv, P.qkv_w, residual=None if dres is None else spread(dres)) if want_dx else None
+            if P.lora_A is not None:
+                lora_bwd(tape, P, a_in, lt, dqkv, dx_)
+            return dx_
+
+        def bwd(g):
+            ride = _WGRAD_ASUM and dyd_rides(g)     # bias gradients ride on the weight-gradient GEMMs (wgrad) where they can
+            if not pre_ln:
+                dy, dyd = _ln_bwd_dense(tape, g, y, P.ln2_w, P.ln2_b, m2, r2, None if ride else P.fc2_b, p_hidden, s_f2)
+                df = ffn_bwd(dyd, P.fc2_b if ride else None, dy)
+                dt_, dtd = _ln_bwd_dense(tape, df, t, P.ln1_w, P.ln1_b, m1, r1, None if ride else P.o_b, p_hidden, s_o)
+                dx = attn_bwd(dtd, P.o_b if ride else None, x.needs_grad, dt_)
+                if x.needs_grad:
+                    tape.add_grad(x, dx)
+            else:
+                gd = ops.dropout(g, p_hidden, s_f2) if p_hidden > 0 else g     # fc2's output went through hidden dropout
+                df = ffn_bwd(gd, P.fc2_b, None)
+                dt_, dtd = _ln_bwd_dense(tape, df, t, P.ln2_w, P.ln2_b, m2, r2, None if ride else P.o_b, p_hidden, s_o, add=g)
+                da = attn_bwd(dtd, P.o_b if ride else None, True)
+                if x.needs_grad:
+                    tape.add_grad(x, _ln_bwd(tape, da, xd, P.ln1_w, P.ln1_b, m1, r1, add=spread(dt_)))
+                else:   # LayerNorm parameters still need their gradients
+                    _ln_bwd(tape, da, xd, P.ln1_w, P.ln1_b, m1, r1)
+            if tape.on_params_ready:
+                tape.on_params_ready(P.all())
+
+        return out, bwd
+
+    if policy == "block":
+        out = run()[0]          # the adjoint of this pass, and with it everything it would have kept, is dropped here
+
+        def bwd(g):
+            # on the stream the adjoint runs on (an image-branch block: the side stream, inside the recorded on_side region);
+            # reads x.data, which nothing has written since this block's forward (DESIGN.md §5, the buffer-lifetime rule)
+            replayed = run()[1]
+            replayed(g)
+    else:
+        out, bwd = run()
+    o = Var(out)
     tape.adjoint(o, bwd)
     return o
 

@@ -262,6 +262,9 @@ class GraphormerModel(FairseqEncoderModel):
         if on and engine.deterministic():
             raise NotImplementedError("enable_fp8 in deterministic mode: the fp8 path has no ordered reductions "
                                       "(engine.set_deterministic(False) first)")
+        if on and engine.recompute() != "none":
+            raise NotImplementedError(f"enable_fp8 with activation recomputation ({engine.recompute()}): {engine.RECOMPUTE_FP8_WHY} "
+                                      "(engine.set_recompute(\"none\") first)")
         fp8.ACTIVE = fp8.Fp8State(next(self.parameters()).device, sites=sites) if on else None
         return fp8.ACTIVE
 

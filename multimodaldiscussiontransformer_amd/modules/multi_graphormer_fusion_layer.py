@@ -62,10 +62,10 @@ class GraphFusionLayer(nn.Module):
             with tape.on_side():
                 spec_v = E.AttnSpec(nseq=I, S=Sv, H=ve.heads, q_limit=0 if prune is None else 1)
                 vit_out = E.transformer_block(tape, vit, ve.block_params(), spec_v, pre_ln=True, eps=ve.eps, **ve.drop_kwargs(),
-                                              keep_rows=None if prune is None else prune["vit_keep"])
+                                              keep_rows=None if prune is None else prune["vit_keep"], recompute=E.recompute())
         spec_t = E.AttnSpec(nseq=M, H=be.heads, q_limit=0 if prune is None else nb + 1, **text_spec)
         text_out = E.transformer_block(tape, text, be.block_params(), spec_t, pre_ln=False, eps=be.eps, **be.drop_kwargs(),
-                                       keep_rows=None if prune is None else prune["text_keep"])
+                                       keep_rows=None if prune is None else prune["text_keep"], recompute=E.recompute())
         if vit is not None:
             tape.join()
             if prune is None:

@@ -260,7 +260,7 @@ class MultiGraphormerGraphEncoder(nn.Module):
                 specv = E.AttnSpec(nseq=I, S=P, H=vm.heads)
                 for layer in vm.encoder.layer:
                     v = E.transformer_block(tape, v, layer.block_params(), specv, pre_ln=True, eps=vm.eps,
-                                            **layer.drop_kwargs())
+                                            **layer.drop_kwargs(), recompute=E.recompute())
                 v = E.layernorm(tape, v, vm.layernorm.weight, vm.layernorm.bias, vm.eps)      # quirk 5: final LN mid-network
                 v.needs_grad = vit_live
                 vit = E.expand_sequences(tape, v, I, P, nb, None)     # zero bottleneck rows in front: no parameter involved
@@ -283,7 +283,7 @@ class MultiGraphormerGraphEncoder(nn.Module):
         spec0 = E.AttnSpec(nseq=M, H=tm.heads, **ix["spec_pre"])
         for layer in tm.encoder.layer:
             text = E.transformer_block(tape, text, layer.block_params(), spec0, pre_ln=False, eps=tm.eps,
-                                       **layer.drop_kwargs())
+                                       **layer.drop_kwargs(), recompute=E.recompute())
         text.needs_grad = text_live
         tape.inference = was_inference
         if I > 0:

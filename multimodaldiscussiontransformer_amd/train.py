@@ -65,6 +65,13 @@ def build_parser():
     p.add_argument("--deterministic", action="store_true", default=False,
                    help="not a reference flag: ordered gradient reductions instead of fp32 atomics (engine.set_deterministic) — loss, "
                         "gradients and parameters are bit-for-bit reproducible in one process on one GPU; bf16 / fp32 only, not with --fp8")
+    p.add_argument("--checkpoint-activations", action="store_true", default=False,
+                   help="FairSeq's flag: recompute the activations of the pretrained BERT / ViT blocks in backward instead of keeping them "
+                        "(engine.set_recompute) — the same loss and gradients from a fraction of the activation memory, for one more "
+                        "forward of those blocks; bf16 / fp32 only, not with --fp8")
+    p.add_argument("--checkpoint-policy", choices=("block", "ffn"), default=None,
+                   help="with --checkpoint-activations: block (default) keeps only each block's input and output and replays its forward; "
+                        "ffn keeps everything but the two F-wide FFN tensors and repeats one fc1 GEMM per block")
     # FairSeq's EMA flags (fairseq/dataclass/configs.py EMAConfig); defaults are filled in main() so that a flag given without
     # --store-ema can be told from one left alone
     p.add_argument("--store-ema", action="store_true", default=False,
@@ -164,6 +171,17 @@ def synthetic_batches(args, task, rank):
 
 
 def main(argv=None):
+    """Train; → the logged metrics.  The activation-recomputation policy is a process-wide switch that ``_main`` sets before
+    it builds the model: it is put back however the run ends, so a later run in this process starts as this one found it."""
+    from . import engine
+    was_recompute = engine.recompute()
+    try:
+        return _main(argv)
+    finally:
+        engine.set_recompute(was_recompute)
+
+
+def _main(argv):
     parser = build_parser()
     args, unknown = parser.parse_known_args(argv)
     if unknown:
@@ -242,6 +260,16 @@ def main(argv=None):
         engine.set_deterministic(True)
         print("[mdt-train] --deterministic: ordered gradient reductions, no float atomics, one stream (one process, one GPU: "
               "the all-reduce order of several ranks is not fixed)", file=sys.stderr)
+    ckpt_act, ckpt_policy = bool(args.checkpoint_activations), args.checkpoint_policy
+    if ckpt_policy is not None and not ckpt_act:
+        raise SystemExit("[mdt-train] --checkpoint-policy without --checkpoint-activations: there is nothing to recompute — add "
+                         "--checkpoint-activations")
+    if ckpt_act and args.fp8:
+        raise SystemExit(f"[mdt-train] --checkpoint-activations with --fp8: {engine.RECOMPUTE_FP8_WHY}")
+    for f in ("checkpoint_activations", "checkpoint_policy"):      # how activations are kept is no property of the model: the
+        delattr(args, f)                                           # checkpoint cfg is that of a run without the flag
+    if ckpt_act:
+        engine.set_recompute(ckpt_policy or "block")               # before the model is built; main() puts it back
     import torch.distributed as dist
     from .ddp import DataParallel
     from .optim import FusedAdam, PolynomialDecayLR
@@ -275,6 +303,18 @@ def main(argv=None):
         print(f"[mdt-train] --lora-rank {lora_rank}: {len(model.lora_modules())} adapted QKV projections"
               f"{f' and {n_dense} adapted dense layers' if n_dense else ''} (targets {args.lora_targets}, "
               f"alpha {args.lora_alpha:g}), {n_train} trainable / {n_frozen} frozen parameter elements", file=sys.stderr)
+    if engine.recompute() != "none" and rank == 0:
+        ge = model.encoder.graph_encoder
+        tm, vm = ge.text_model, ge.vit_model
+
+        def live(*mods):        # a prefix without a trainable parameter runs without a tape: nothing is kept there anyway
+            return any(p.requires_grad for m in mods for p in m.parameters())
+
+        n_blocks = (len(model.pretrained_blocks()[1]) + (len(tm.encoder.layer) if live(tm.embeddings, tm.encoder) else 0)
+                    + (len(vm.encoder.layer) if live(vm.embeddings, vm.encoder, vm.layernorm) else 0))
+        what = dict(block="input and output kept, forward replayed in backward", ffn="u and h recomputed from the FFN input")
+        print(f"[mdt-train] activation recomputation: policy {engine.recompute()} ({what[engine.recompute()]}) on {n_blocks} "
+              "pretrained BERT / ViT blocks; the graph layers keep their activations", file=sys.stderr)
     model = model.cuda()
     half = args.fp16 or args.bf16 or args.fp8
     if half:
