@@ -633,6 +633,29 @@ size_t mdt_lora_wgrad_workspace_bytes(int64_t R, int n, int N);
 int mdt_lora_wgrad(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt,
                    const void* X, int64_t ldx, float* dW, int64_t lddw, float alpha,
                    void* workspace, size_t workspace_bytes);
+/* Adapter-input dropout (PEFT's lora_dropout: y = base(x) + s B A dropout(x)): the forms of the entry points above whose [R, wide]
+ * operand X is dropped on its way into the product.  The keep decision of X[r, c] is that of counter r W + c of site drop_seed
+ * (mdt_dropout / mdt_dropout_mask over R W elements), r the row of X AS PASSED (of a view: the row of the view) and W its logical
+ * width K or N, never its row stride.  A dropped element is replaced by +0 by a select before it enters the MFMA fragment (down)
+ * or the LDS image (wgrad): kept elements stay exact, nothing is rounded to x / (1 - p), a non-finite value at a dropped position
+ * does not reach the result, and no dropped copy of X is written anywhere.  1 / (1 - drop_p) (fp32, make_drop's) joins alpha as
+ * ONE fp32 factor fl(alpha / (1 - p)), applied where alpha is applied.  Contract of the plain forms plus 0 <= drop_p < 1 and
+ * R W < 2^33 (MDT_ERR_ARG); drop_p = 0 is the plain entry point bit for bit.
+ *   mdt_last_route(): "lora_down_drop", "lora_wgrad_drop", "lora_up_mul_drop" (bf16), the same with "_f32" (fp32).
+ * mdt_lora_down_drop        T[R, n] = fl(alpha / (1 - p)) * (m o X)[R, K] W[n, K]^T, counters r K + k
+ * mdt_lora_wgrad_drop       dW[n, N] += fl(alpha / (1 - p)) * T[R, n]^T (m o X)[R, N], counters r N + c: slabs, order, workspace and
+ *                           the absence of float atomics as in mdt_lora_wgrad
+ * mdt_lora_up_add_mul_drop  Y[r, c] = Y[r, c] + (alpha s(r, c) p) aux[r, c], s as in mdt_lora_up_add_drop: the share of fc2's du of
+ *                           an adapter whose input h was dropped.  An element whose counter is dropped keeps its bits.
+ * The adapter's share of every other input gradient, dx += s o (dt A), is mdt_lora_up_add_drop with N = K and the site's seed. */
+int mdt_lora_down_drop(void* stream, int dtype, int64_t R, int n, int K, const void* X, int64_t ldx,
+                       const void* W, int64_t ldw, void* T, int64_t ldt, float alpha, float drop_p, uint64_t drop_seed);
+int mdt_lora_wgrad_drop(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt,
+                        const void* X, int64_t ldx, float* dW, int64_t lddw, float alpha, float drop_p, uint64_t drop_seed,
+                        void* workspace, size_t workspace_bytes);
+int mdt_lora_up_add_mul_drop(void* stream, int dtype, int64_t R, int n, int N, const void* T, int64_t ldt,
+                             const void* W, int64_t ldw, void* Y, int64_t ldy, const void* aux, int64_t ld_aux,
+                             float alpha, float drop_p, uint64_t drop_seed);
 
 /* ------------------------------------------------------------------ packer (host, C++)
  * Native replacement of preprocess_item + collator (data/pyg_datasets/pre_processing.py:18-69,

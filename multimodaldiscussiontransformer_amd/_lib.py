@@ -89,6 +89,9 @@ _SIGS = {
     "mdt_lora_wgrad_slab_rows": ([], _i),
     "mdt_lora_wgrad_workspace_bytes": ([_i64, _i, _i], C.c_size_t),
     "mdt_lora_wgrad": ([_vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _f, _vp, C.c_size_t], _i),
+    "mdt_lora_down_drop": ([_vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f, C.c_uint64], _i),
+    "mdt_lora_wgrad_drop": ([_vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f, C.c_uint64, _vp, C.c_size_t], _i),
+    "mdt_lora_up_add_mul_drop": ([_vp, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _f, _f, C.c_uint64], _i),
     "mdt_bert_embed_sum": ([_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i64, _i64], _i),
     "mdt_bert_embed_rows": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64], _i),
     "mdt_bert_embed_ln_rows": ([_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _i64, _vp, _i64, _vp, _vp], _i),

@@ -512,21 +512,44 @@ def _ln_bwd_dense(tape, dy, x, w, b, mean, rstd, bias_param, p_drop, seed, add=N
                          want_dropped=True)
 
 
-def lora_fwd(P: BlockParams, src: torch.Tensor, qkv: torch.Tensor) -> torch.Tensor:
-    """Adapters of the QKV projection, forward: t = src A^T (stored in the working dtype), then
-    qkv[:, c_j : c_j + D] += s t_j Bt_j for every target, in place and before attention reads qkv.  → t"""
+def lora_down_site(src: torch.Tensor, A: torch.Tensor, p: float = 0.0, seed: int = 0) -> torch.Tensor:
+    """t = dropout_p(src) A^T of one adapter site: the mask is made inside the kernel from ``seed`` (counters row * width + col of
+    ``src`` as passed) and no dropped copy of ``src`` exists; p = 0 is the plain ``ops.lora_down`` launch."""
+    return ops.lora_down_drop(src, A, drop_p=p, drop_seed=seed) if p > 0 else ops.lora_down(src, A)
+
+
+def lora_site_bwd(dt: torch.Tensor, src: torch.Tensor, A: torch.Tensor, gA, dx, ws, p: float, seed: int) -> None:
+    """What a site's input dropout changes in the adjoint: dA += dt^T dropout_p(src) and dx += s o (dt A) under the same mask."""
+    if gA is not None:
+        if p > 0:
+            ops.lora_wgrad_drop(dt, src, gA, drop_p=p, drop_seed=seed, ws=ws)
+        else:
+            ops.lora_wgrad(dt, src, gA, ws=ws)
+    if dx is not None:
+        if p > 0:
+            ops.lora_up_add_drop(dt, A, dx, drop_p=p, drop_seed=seed)
+        else:
+            ops.lora_up_add(dt, A, dx)
+
+
+def lora_fwd(P: BlockParams, src: torch.Tensor, qkv: torch.Tensor, p: float = 0.0, seed: int = 0) -> torch.Tensor:
+    """Adapters of the QKV projection, forward: t = dropout_p(src) A^T (stored in the working dtype; one site: the q, k and v
+    adapters read the same dropped source), then qkv[:, c_j : c_j + D] += s t_j Bt_j for every target, in place and before
+    attention reads qkv.  → t"""
     D = src.shape[1]
     r = P.lora_A.shape[0] // len(P.lora_cols)
-    t = ops.lora_down(src, P.lora_A.data)
+    t = lora_down_site(src, P.lora_A.data, p, seed)
     for j, c in enumerate(P.lora_cols):
         ops.lora_up_add(t[:, j * r:(j + 1) * r], P.lora_Bt.data[j * r:(j + 1) * r], qkv[:, c * D:(c + 1) * D], alpha=P.lora_scale)
     return t
 
 
-def lora_bwd(tape: Tape, P: BlockParams, src: torch.Tensor, t: torch.Tensor, dqkv: torch.Tensor, dx: Optional[torch.Tensor]) -> None:
+def lora_bwd(tape: Tape, P: BlockParams, src: torch.Tensor, t: torch.Tensor, dqkv: torch.Tensor, dx: Optional[torch.Tensor],
+             p: float = 0.0, seed: int = 0) -> None:
     """Adjoint of lora_fwd: dBt_j += s t_j^T dqkv_j, dt_j = s dqkv_j Bt_j^T, dA += dt^T src and, where the block wants its input
     gradient, dx += dt A on the output of the frozen projection's dgrad.  The weight gradients are sums in a fixed order
-    (ops.lora_wgrad): the same launches in the default and in the deterministic mode; a frozen adapter costs nothing."""
+    (ops.lora_wgrad): the same launches in the default and in the deterministic mode; a frozen adapter costs nothing.  ``p``,
+    ``seed``: the site's input dropout (lora_site_bwd)."""
     D = src.shape[1]
     n = P.lora_A.shape[0]
     r = n // len(P.lora_cols)
@@ -543,17 +566,16 @@ def lora_bwd(tape: Tape, P: BlockParams, src: torch.Tensor, t: torch.Tensor, dqk
             ops.lora_wgrad(t[:, rows], dq, gBt.view(n, D)[rows], alpha=s, ws=ws)
         if want_dt:
             ops.lora_down(dq, P.lora_Bt.data[rows], out=dt[:, rows], alpha=s)
-    if gA is not None:
-        ops.lora_wgrad(dt, src, gA.view(n, D), ws=ws)
-    if dx is not None:
-        ops.lora_up_add(dt, P.lora_A.data, dx)
+    if want_dt:
+        lora_site_bwd(dt, src, P.lora_A.data, None if gA is None else gA.view(n, D), dx, ws, p, seed)
 
 
-def lora_dense_bwd(tape: Tape, L: LoraSlot, src: torch.Tensor, t: torch.Tensor, g: torch.Tensor, dx: Optional[torch.Tensor]) -> torch.Tensor:
+def lora_dense_bwd(tape: Tape, L: LoraSlot, src: torch.Tensor, t: torch.Tensor, g: torch.Tensor, dx: Optional[torch.Tensor],
+                   p: float = 0.0, seed: int = 0) -> torch.Tensor:
     """Adjoint of a dense layer's adapter y += s (src A^T) Bt, ``g`` the gradient of that sum [R, out], ``t`` the stored src A^T:
     dBt += s t^T g, dt = s g Bt^T, dA += dt^T src, and dx += dt A where ``dx`` (the output of the base layer's dgrad) is given.
     → dt, for the caller whose dx takes another epilogue (fc2: times u).  Fixed-order weight gradients as in lora_bwd; a frozen
-    adapter launches nothing for them."""
+    adapter launches nothing for them.  ``p``, ``seed``: the site's input dropout (``t`` was made from dropout_p(src))."""
     r = L.A.shape[0]
     gA, gBt = tape.pgrad(L.A), tape.pgrad(L.Bt)
     ws = None
@@ -563,10 +585,7 @@ def lora_dense_bwd(tape: Tape, L: LoraSlot, src: torch.Tensor, t: torch.Tensor, 
     if gBt is not None:
         ops.lora_wgrad(t, g, gBt.view(r, g.shape[1]), alpha=L.scale, ws=ws)
     dt = ops.lora_down(g, L.Bt.data, alpha=L.scale)
-    if gA is not None:
-        ops.lora_wgrad(dt, src, gA.view(r, src.shape[1]), ws=ws)
-    if dx is not None:
-        ops.lora_up_add(dt, L.A.data, dx)
+    lora_site_bwd(dt, src, L.A.data, None if gA is None else gA.view(r, src.shape[1]), dx, ws, p, seed)
     return dt
 
 
@@ -574,7 +593,7 @@ def lora_dense_bwd(tape: Tape, L: LoraSlot, src: torch.Tensor, t: torch.Tensor, 
 # ops
 def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre_ln: bool, eps: float,
                       p_hidden: float = 0.0, p_attn: float = 0.0, p_act: float = 0.0, keep_rows=None, act: str = "gelu",
-                      recompute: str = "none") -> Var:
+                      recompute: str = "none", p_lora: float = 0.0) -> Var:
     """One encoder block (post-LN: HF BertLayer / Graphormer layer; pre-LN: HF ViTLayer or
     Graphormer with --pre-layernorm).  7 GEMM-class launches + attention + 2 LayerNorms
     forward; the adjoint mirrors it with the residual adds folded into epilogues.  The attention half
@@ -594,6 +613,12 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     a plain bias GEMM for every ``act``).  Backward: ``lora_dense_bwd``; fc2's share of du takes the multiply by u in
     ``lora_up_add_mul``.  The block still takes exactly four dropout seeds.
 
+    ``p_lora`` (PEFT's lora_dropout, one probability for all adapters of the block): every adapter reads dropout(x), t =
+    dropout(x) A^T.  The mask is made inside the adapter kernels (``lora_down_drop`` forward, ``lora_wgrad_drop`` for dA,
+    ``lora_up_add_drop`` for dx += s o (dt A), ``lora_up_add_mul_drop`` for fc2's share of du) from one further seed per adapter
+    site present, drawn after the four above in the order qkv, out, fc1, fc2; the fused QKV adapters are ONE site.  0 draws
+    no seed and launches what the block launched before.
+
     ``keep_rows`` (i32[R]): only these token rows of the block's OUTPUT are needed downstream (the last fusion
     layer feeds nothing but bottleneck token 0 and [CLS] of every comment to the graph / the head).  Keys and
     values still come from every row, but the output projection, both LayerNorms and the FFN — three quarters of
@@ -606,6 +631,15 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
     unchanged ``bwd``.  Neither draws a seed, so every dropout site of the tape keeps its seed under every policy."""
     xd = x.data
     s_attn, s_o, s_act, s_f2 = (tape.next_seed() for _ in range(4))
+    if not 0.0 <= p_lora < 1.0:
+        raise ValueError(f"transformer_block: p_lora={p_lora} is not in [0, 1)")
+    # adapter-input dropout: drawn here, outside run(), so that the "block" replay and the "ffn" re-run see the same masks
+    sl_qkv = sl_o = sl_f1 = sl_f2 = 0
+    if p_lora > 0:
+        sl_qkv = tape.next_seed() if P.lora_A is not None else 0
+        sl_o = tape.next_seed() if P.lora_o is not None else 0
+        sl_f1 = tape.next_seed() if P.lora_fc1 is not None else 0
+        sl_f2 = tape.next_seed() if P.lora_fc2 is not None else 0
     kw = dict(spec.kwargs(), drop_p=p_attn, drop_seed=s_attn)
     R = None if keep_rows is None else int(keep_rows.numel())
     f8 = F8.ACTIVE
@@ -658,14 +692,14 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
             qkv_, _ = linear(f8, src, P.qkv_w, "qkv", x8=src8, bias=P.qkv_b.data)
             lt_ = None
             if P.lora_A is not None:           # the adapters' sum joins qkv before attention reads it; t is kept for backward only
-                lt_ = lora_fwd(P, src, qkv_)
+                lt_ = lora_fwd(P, src, qkv_, p_lora, sl_qkv)
                 if tape.inference:
                     lt_ = None
             ctx_full_, lse_ = ops.attention_fwd(qkv_, spec.nseq, spec.S, spec.H, **kw)
             ctx_, xk = gather(ctx_full_), gather(xd)
             t_ = ops.gemm(ctx_, P.o_w.data, bias=P.o_b.data, residual=xk, drop_p=p_hidden, drop_seed=s_o)
             if Lo is not None:                 # the adapter's sum joins under the mask the GEMM's epilogue applied
-                lto = ops.lora_down(ctx_, Lo.A.data)
+                lto = lora_down_site(ctx_, Lo.A.data, p_lora, sl_o)
                 ops.lora_up_add_drop(lto, Lo.Bt.data, t_, alpha=Lo.scale, drop_p=p_hidden, drop_seed=s_o)
                 if not tape.inference:
                     lts["o"] = lto
@@ -674,7 +708,7 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
         def fc2_fwd(h_, h8, res):
             y_ = linear(f8, h_, P.fc2_w, "fc2", x8=h8, bias=P.fc2_b.data, residual=res, drop_p=p_hidden, drop_seed=s_f2)[0]
             if L2 is not None:
-                lt2 = ops.lora_down(h_, L2.A.data)
+                lt2 = lora_down_site(h_, L2.A.data, p_lora, sl_f2)
                 ops.lora_up_add_drop(lt2, L2.Bt.data, y_, alpha=L2.scale, drop_p=p_hidden, drop_seed=s_f2)
                 if not tape.inference:
                     lts["fc2"] = lt2
@@ -684,7 +718,7 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
             """fc1 and the activation: → (u, h, the 8-bit h or None).  The "ffn" policy's adjoint calls it a second time."""
             if L1 is not None:      # the adapter's sum joins the stored pre-activation in front of the non-linearity, whatever its kind
                 pre_ = ops.gemm(src, P.fc1_w.data, bias=P.fc1_b.data)
-                lt1 = ops.lora_down(src, L1.A.data)
+                lt1 = lora_down_site(src, L1.A.data, p_lora, sl_f1)
                 h_, u_ = ops.lora_up_act(lt1, L1.Bt.data, pre_, act, alpha=L1.scale, drop_p=p_act, drop_seed=s_act, out=pre_,
                                          want_u=not tape.inference)
                 if not tape.inference:
@@ -729,23 +763,26 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
             if policy == "ffn":     # the fc1 path the forward took, from the same seed: the same bits
                 u, h, _ = fc1_fwd(f_in, None)
                 if L2 is not None:
-                    lts["fc2"] = ops.lora_down(h, L2.A.data)
+                    lts["fc2"] = lora_down_site(h, L2.A.data, p_lora, sl_f2)
             wgrad(tape, gd, h, P.fc2_w, fc2_b)
             gb1 = tape.pgrad(P.fc1_b)           # fc1 bias gradient = colsum(du): fused into the GEMM epilogue
             det = _DETERMINISTIC                # ... or, in deterministic mode, summed from the stored du in a fixed order
             # an fc2 adapter adds its share of du behind the GEMM, so the bias sum cannot ride on that GEMM's epilogue either
             late = det or L2 is not None
-            dt2 = lora_dense_bwd(tape, L2, h, lts["fc2"], gd, None) if L2 is not None else None
+            dt2 = lora_dense_bwd(tape, L2, h, lts["fc2"], gd, None, p_lora, sl_f2) if L2 is not None else None
             du, du8 = linear(f8, gd, P.fc2_w, "d_fc2", grad=True, q8_site=("d_fc1", id(P.fc1_w)), q8_grad=True, aux=u,
                              epilogue=ops.EPI_MULAUX, colsum=None if (gb1 is None or late) else gb1.view(-1))
             if L2 is not None:                  # dh is never materialised: the adapter's share takes the same multiply by u
-                ops.lora_up_add_mul(dt2, L2.A.data, du, u)
+                if p_lora > 0:                  # ... under the mask the adapter read h through
+                    ops.lora_up_add_mul_drop(dt2, L2.A.data, du, u, drop_p=p_lora, drop_seed=sl_f2)
+                else:
+                    ops.lora_up_add_mul(dt2, L2.A.data, du, u)
             if late and gb1 is not None:
                 colsum(du, out=gb1.view(-1))
             wgrad(tape, du, f_in, P.fc1_w, None)
             df = linear(f8, du, P.fc1_w, "d_fc1", grad=True, x8=du8, residual=dres)[0]     # 8-bit when the GEMM above handed over the quantised du
             if L1 is not None:
-                lora_dense_bwd(tape, L1, f_in, lts["fc1"], du, df)
+                lora_dense_bwd(tape, L1, f_in, lts["fc1"], du, df, p_lora, sl_f1)
             if policy == "ffn":
                 u = h = None
             return df
@@ -756,12 +793,12 @@ def transformer_block(tape: Tape, x: Var, P: BlockParams, spec: AttnSpec, *, pre
             wgrad(tape, dtd, ctx, P.o_w, o_b)
             dctx = ops.gemm(dtd, P.o_w.data, trans_b=True)
             if Lo is not None:
-                lora_dense_bwd(tape, Lo, ctx, lts["o"], dtd, dctx)
+                lora_dense_bwd(tape, Lo, ctx, lts["o"], dtd, dctx, p_lora, sl_o)
             dqkv = _attention_bwd(tape, spec, kw, dctx, qkv, ctx_full, lse, spread)
             wgrad(tape, dqkv, a_in, P.qkv_w, P.qkv_b)
             dx_ = dgrad(dqkv, P.qkv_w, residual=None if dres is None else spread(dres)) if want_dx else None
             if P.lora_A is not None:
-                lora_bwd(tape, P, a_in, lt, dqkv, dx_)
+                lora_bwd(tape, P, a_in, lt, dqkv, dx_, p_lora, sl_qkv)
             return dx_
 
         def bwd(g):

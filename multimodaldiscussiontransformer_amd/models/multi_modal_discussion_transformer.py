@@ -103,7 +103,8 @@ class GraphormerModel(FairseqEncoderModel):
                                                        vit=getattr(args, "pretrained_vit", None) or hf_weights.VIT_NAME)
             logger.info("pretrained encoders: %s", info)
         if getattr(args, "lora_rank", 0):          # after the pretrained weights: the adapters sit beside them
-            model.add_lora(int(args.lora_rank), getattr(args, "lora_alpha", None), getattr(args, "lora_targets", None) or "q,v")
+            model.add_lora(int(args.lora_rank), getattr(args, "lora_alpha", None), getattr(args, "lora_targets", None) or "q,v",
+                           dropout=float(getattr(args, "lora_dropout", None) or 0.0))
         return model
 
     def forward(self, batched_data, **kwargs):
@@ -167,14 +168,16 @@ class GraphormerModel(FairseqEncoderModel):
         prefix, fusion = self.pretrained_blocks()
         return [m for b in prefix + fusion for m in b.dense_lora_layers().values() if m.lora_A is not None]
 
-    def add_lora(self, rank: int, alpha=None, targets=("q", "v")):
+    def add_lora(self, rank: int, alpha=None, targets=("q", "v"), dropout: float = 0.0):
         """Parameter-efficient fine-tuning: every parameter of the two pretrained encoders (``encoder_layer_ids``: embeddings and
         blocks) is frozen and rank-``rank`` adapters are trained beside the targets of every pretrained block — q / k / v of the
         fused QKV projection, ``out`` (attention output projection), ``fc1``, ``fc2``; "all": the six —
         of the fusion blocks only when the prefixes are frozen by --freeze_initial_encoders, which then keep running without a
         tape.  Poolers, ViT's final LayerNorm, the graph stacks, bottleneck tokens and the head stay as they are.  ``alpha``
-        defaults to 2 * rank; the adapter sum is scaled by alpha / rank.  Call it after the pretrained weights are loaded and
-        before ``prepare_main_grads`` / FusedAdam.  → the number of adapted blocks."""
+        defaults to 2 * rank; the adapter sum is scaled by alpha / rank.  ``dropout`` (PEFT's lora_dropout, 0 <= p < 1): in training
+        mode every adapter of an adapted block reads dropout(x), one probability for all of them (the fused q / k / v adapters
+        share one mask); it adds no parameter and no state-dict key, and ``merge_lora`` is unaffected.  Call it after the
+        pretrained weights are loaded and before ``prepare_main_grads`` / FusedAdam.  → the number of adapted blocks."""
         import math
         from .. import fp8
         from ..modules._fused import LORA_RANKS, LORA_TARGETS, parse_lora_targets
@@ -190,6 +193,9 @@ class GraphormerModel(FairseqEncoderModel):
         alpha = 2.0 * rank if alpha is None else float(alpha)
         if not (math.isfinite(alpha) and alpha > 0):
             raise ValueError(f"add_lora: alpha {alpha} is not a finite positive number")
+        dropout = float(dropout)
+        if not 0.0 <= dropout < 1.0:           # NaN fails both comparisons
+            raise ValueError(f"add_lora: dropout {dropout} is not in [0, 1)")
         targets = parse_lora_targets(targets)
         ids = self.encoder_layer_ids()
         for p in self.parameters():
@@ -199,6 +205,7 @@ class GraphormerModel(FairseqEncoderModel):
         blocks = fusion if getattr(self.args, "freeze_initial_encoders", False) else prefix + fusion
         qkv = tuple(t for t in targets if t in LORA_TARGETS)
         for b in blocks:
+            b.lora_dropout_p = dropout
             if qkv:
                 b.qkv_params().add_lora(rank, alpha, qkv)
             for name, m in b.dense_lora_layers().items():
@@ -212,6 +219,8 @@ class GraphormerModel(FairseqEncoderModel):
         mods = self.lora_modules() + self.lora_dense_modules()
         for m in mods:
             m.merge_lora()
+        for b in sum(self.pretrained_blocks(), []):
+            b.lora_dropout_p = 0.0
         if mods:
             E.weights_changed()
         return len(mods)

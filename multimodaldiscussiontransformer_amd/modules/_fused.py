@@ -252,13 +252,17 @@ class BertLayer(nn.Module):
         super().__init__()
         self.dim, self.heads, self.eps = dim, heads, eps
         self.hidden_dropout_p, self.attention_dropout_p = 0.0, 0.0     # hidden_dropout_prob / attention_probs_dropout_prob
+        self.lora_dropout_p = 0.0       # PEFT's lora_dropout, set by the model's add_lora
         self.attention = _BertAttention(dim, eps)
         self.intermediate = _Dense(dim, intermediate)
         self.output = _DenseLN(intermediate, dim, eps)
 
     def drop_kwargs(self):
         t = self.training
-        return dict(p_hidden=self.hidden_dropout_p if t else 0.0, p_attn=self.attention_dropout_p if t else 0.0)
+        kw = dict(p_hidden=self.hidden_dropout_p if t else 0.0, p_attn=self.attention_dropout_p if t else 0.0)
+        if t and self.lora_dropout_p > 0:      # adapter-input dropout (add_lora(dropout=...)): training only, like the two above
+            kw["p_lora"] = self.lora_dropout_p
+        return kw
 
     def qkv_params(self) -> "_SelfAttentionParams":
         return self.attention.self
@@ -290,6 +294,7 @@ class ViTLayer(nn.Module):
         super().__init__()
         self.dim, self.heads, self.eps = dim, heads, eps
         self.hidden_dropout_p, self.attention_dropout_p = 0.0, 0.0
+        self.lora_dropout_p = 0.0
         self.attention = _ViTAttention(dim)
         self.intermediate = _Dense(dim, intermediate)
         self.output = _Dense(intermediate, dim)
@@ -298,7 +303,10 @@ class ViTLayer(nn.Module):
 
     def drop_kwargs(self):
         t = self.training
-        return dict(p_hidden=self.hidden_dropout_p if t else 0.0, p_attn=self.attention_dropout_p if t else 0.0)
+        kw = dict(p_hidden=self.hidden_dropout_p if t else 0.0, p_attn=self.attention_dropout_p if t else 0.0)
+        if t and self.lora_dropout_p > 0:      # adapter-input dropout (add_lora(dropout=...)): training only, like the two above
+            kw["p_lora"] = self.lora_dropout_p
+        return kw
 
     def qkv_params(self) -> "_SelfAttentionParams":
         return self.attention.attention

@@ -22,7 +22,7 @@ __all__ = [
     "tanh_fwd", "tanh_bwd", "node_ce", "contrastive_loss", "fp8_quantize", "fp8_scale_update", "gemm_fp8", "cast", "transpose2d", "dropout", "dropout_mask",
     "sum_slices", "gemm_splitk_ordered", "colsum_ordered", "layernorm_bwd_ordered", "segments_of", "row_segment_sum",
     "attn_bias_grad_ordered", "float_atomic_launches", "lora_down", "lora_up_add", "lora_up_add_drop", "lora_up_add_mul", "lora_up_act", "lora_wgrad",
-    "LORA_WGRAD_SLAB",
+    "lora_down_drop", "lora_wgrad_drop", "lora_up_add_mul_drop", "LORA_WGRAD_SLAB",
     "act_fwd", "ACT_KINDS", "ACT_GELU", "ACT_RELU", "ACT_GELU_ACCURATE", "ACT_TANH", "ACT_LINEAR",
     "EPI_BIAS", "EPI_GELU", "EPI_RESIDUAL", "EPI_DGELU", "EPI_ACCUM", "EPI_ATOMIC", "EPI_DROPOUT", "EPI_AUX_GRAD", "EPI_MULAUX", "EPI_ASUM",
 ]
@@ -407,6 +407,44 @@ def lora_wgrad(t: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, alpha=1.0, ws
     check(lib.mdt_lora_wgrad(stream(), dt(t), R, n, N, ptr(t), _2d(t), ptr(x), _2d(x), ptr(dw), _2d(dw), float(alpha), ptr(ws), nbytes),
           "mdt_lora_wgrad")
     return dw
+
+
+# adapter-input dropout (include/mdt_hip.h "Adapter-input dropout"): x is dropped inside the kernel with the counters row * width +
+# col of site ``drop_seed`` — ``dropout_mask(R * width, drop_p, drop_seed)`` — and no dropped copy of it is written
+def lora_down_drop(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None, alpha=1.0, drop_p=0.0, drop_seed=0) -> torch.Tensor:
+    """out[R, n] = alpha / (1 - p) * (m * x)[R, K] @ w[n, K].T: ``lora_down`` of dropout(x); drop_p = 0 is ``lora_down`` bit for bit."""
+    R, K = x.shape
+    n = w.shape[0]
+    assert w.shape[1] == K and x.dtype == w.dtype
+    if out is None:
+        out = torch.empty(R, n, dtype=x.dtype, device=x.device)
+    assert out.shape == (R, n) and out.dtype == x.dtype
+    check(lib.mdt_lora_down_drop(stream(), dt(x), R, n, K, ptr(x), _2d(x), ptr(w), _2d(w), ptr(out), _2d(out), float(alpha),
+                                 float(drop_p), int(drop_seed)), "mdt_lora_down_drop")
+    return out
+
+
+def lora_wgrad_drop(t: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, alpha=1.0, drop_p=0.0, drop_seed=0, ws=None) -> torch.Tensor:
+    """dw[n, N] (fp32) += alpha / (1 - p) * t[R, n].T @ (m * x)[R, N]: ``lora_wgrad`` against dropout(x), the same fixed order."""
+    R, n = t.shape
+    N = x.shape[1]
+    assert x.shape[0] == R and t.dtype == x.dtype and dw.dtype == torch.float32 and dw.shape == (n, N)
+    ws, nbytes = _workspace(ws, lib.mdt_lora_wgrad_workspace_bytes(R, n, N), t.device)
+    check(lib.mdt_lora_wgrad_drop(stream(), dt(t), R, n, N, ptr(t), _2d(t), ptr(x), _2d(x), ptr(dw), _2d(dw), float(alpha),
+                                  float(drop_p), int(drop_seed), ptr(ws), nbytes), "mdt_lora_wgrad_drop")
+    return dw
+
+
+def lora_up_add_mul_drop(t: torch.Tensor, w: torch.Tensor, y: torch.Tensor, aux: torch.Tensor, alpha=1.0, drop_p=0.0,
+                         drop_seed=0) -> torch.Tensor:
+    """y[R, N] += alpha * s * (t @ w) * aux, s the dropout scale of counter row*N + col of site ``drop_seed``: ``lora_up_add_mul``
+    for an adapter whose input was dropped.  Dropped elements keep their bits."""
+    R, n = t.shape
+    N = w.shape[1]
+    assert w.shape[0] == n and y.shape == (R, N) and aux.shape == (R, N) and t.dtype == w.dtype == y.dtype == aux.dtype
+    check(lib.mdt_lora_up_add_mul_drop(stream(), dt(t), R, n, N, ptr(t), _2d(t), ptr(w), _2d(w), ptr(y), _2d(y), ptr(aux), _2d(aux),
+                                       float(alpha), float(drop_p), int(drop_seed)), "mdt_lora_up_add_mul_drop")
+    return y
 
 
 def colsum_ordered(x: torch.Tensor, out: Optional[torch.Tensor] = None, row_weight=None, ws=None) -> torch.Tensor:

@@ -102,6 +102,8 @@ def build_parser():
                    "(finite, > 0; default 2 * rank)")
     p.add_argument("--lora-targets", default=None, help="comma list out of q,k,v,out,fc1,fc2 (out: the attention output "
                    "projection; fc1 / fc2: the FFN's two dense layers), or all: the layers that get adapters (default q,v)")
+    p.add_argument("--lora-dropout", type=float, default=None, help="with --lora-rank: PEFT's lora_dropout — in training every adapter "
+                   "reads dropout(x) with this probability (0 <= P < 1; default 0: off); the masks are made inside the adapter kernels")
     p.add_argument("--save-merged", default="", help="with --lora-rank: also write, at the end, a plain checkpoint with the adapters "
                    "folded into the projections (GraphormerModel.merge_lora) — it loads into a model built without --lora-rank")
     p.add_argument("--log-interval", type=int, default=10)
@@ -230,7 +232,7 @@ def _main(argv):
         for f in group_flags:                    # flags left at their defaults: the optimiser, the log lines and the checkpoint cfg of a run without them
             delattr(args, f)
     lora_rank, save_merged = int(args.lora_rank or 0), args.save_merged
-    lora_flags = [f for f in ("lora_alpha", "lora_targets") if getattr(args, f) is not None] + (["save_merged"] if save_merged else [])
+    lora_flags = [f for f in ("lora_alpha", "lora_targets", "lora_dropout") if getattr(args, f) is not None] + (["save_merged"] if save_merged else [])
     if lora_flags and not lora_rank:
         raise SystemExit("[mdt-train] " + ", ".join("--" + f.replace("_", "-") for f in lora_flags) + " without --lora-rank: there are no "
                          "adapters to configure or merge — add --lora-rank")
@@ -246,11 +248,15 @@ def _main(argv):
             args.lora_targets = ",".join(parse_lora_targets(args.lora_targets or "q,v"))
         except ValueError as e:
             raise SystemExit(f"[mdt-train] --lora-targets: {e}")
+        if args.lora_dropout is not None and not 0.0 <= args.lora_dropout < 1.0:      # NaN fails both comparisons
+            raise SystemExit("[mdt-train] --lora-dropout must be in [0, 1)")
+        if not args.lora_dropout:                # not given, or 0: the log line and the checkpoint cfg of a run without the flag
+            delattr(args, "lora_dropout")
         if args.fp8:
             raise SystemExit("[mdt-train] --fp8 with --lora-rank: low-rank adapters with fp8 GEMMs are not supported (the adapter sum "
                              "enters the bf16 qkv buffer only) — train the adapters in bf16")
     else:
-        for f in ("lora_rank", "lora_alpha", "lora_targets"):      # a run without adapters writes the checkpoint cfg it always wrote
+        for f in ("lora_rank", "lora_alpha", "lora_targets", "lora_dropout"):      # a run without adapters writes the checkpoint cfg it always wrote
             delattr(args, f)
     from . import engine
     was_deterministic = engine.deterministic()
@@ -302,7 +308,7 @@ def _main(argv):
         n_dense = len(model.lora_dense_modules())
         print(f"[mdt-train] --lora-rank {lora_rank}: {len(model.lora_modules())} adapted QKV projections"
               f"{f' and {n_dense} adapted dense layers' if n_dense else ''} (targets {args.lora_targets}, "
-              f"alpha {args.lora_alpha:g}), {n_train} trainable / {n_frozen} frozen parameter elements", file=sys.stderr)
+              f"alpha {args.lora_alpha:g}{f', dropout {args.lora_dropout:g}' if getattr(args, 'lora_dropout', 0) else ''}), {n_train} trainable / {n_frozen} frozen parameter elements", file=sys.stderr)
     if engine.recompute() != "none" and rank == 0:
         ge = model.encoder.graph_encoder
         tm, vm = ge.text_model, ge.vit_model
@@ -463,6 +469,12 @@ def _main(argv):
         meter["checked"] = upd
         return g
 
+    # --lora-dropout: every step's site seeds come from torch's CPU generator (engine.Tape.next_seed).  So that a resumed run
+    # continues the masks of the uninterrupted one, the generator's state rides in the checkpoint's extra_state and a validation
+    # pass (whose forward-only tapes draw from it too) leaves it as it found it.  Without the flag none of this happens: the
+    # checkpoint bytes and the generator's sequence are those of a run before the flag existed.
+    keep_rng = bool(getattr(args, "lora_dropout", 0))
+
     def save(path, upd):
         check_guard(upd)
         done = skip_batches + it                     # batches consumed since the restored epoch began
@@ -471,7 +483,8 @@ def _main(argv):
                              training_time=time.time() - t0,
                              extra_state={"train_iterator": {"version": 2, "epoch": epoch0 + done // max(1, n_batches),
                                                              "iterations_in_epoch": done % max(1, n_batches), "shuffle": True},
-                                          "val_loss": best["value"], **({"ema": opt.ema_state_dict(model)} if store_ema else {})})
+                                          "val_loss": best["value"], **({"ema": opt.ema_state_dict(model)} if store_ema else {}),
+                                          **({"rng_state": torch.get_rng_state()} if keep_rng else {})})
 
     valid_history = []
     main.valid_history = valid_history
@@ -484,6 +497,7 @@ def _main(argv):
             return None
         check_guard(upd)
         was = model.training
+        rng = torch.get_rng_state() if keep_rng else None
         model.eval()
         tot = torch.zeros(6, dtype=torch.float32, device="cuda")
         keys = None
@@ -496,6 +510,8 @@ def _main(argv):
                 tot[1] += float(sample_size)
                 tot[2:6] += torch.stack([log[k] for k in keys]).float()
         model.train(was)
+        if rng is not None:
+            torch.set_rng_state(rng)
         if world > 1:
             dist.all_reduce(tot)
         if keys is None:
@@ -515,6 +531,8 @@ def _main(argv):
             print(json.dumps(m), flush=True)
         return m
 
+    if keep_rng and args.restore_file and info["extra_state"].get("rng_state") is not None:
+        torch.set_rng_state(info["extra_state"]["rng_state"])
     for upd in range(start_update + 1, max_update + 1):
         dp.zero_grad()
         acc = torch.zeros(6, dtype=torch.float32, device="cuda")
@@ -558,7 +576,7 @@ def _main(argv):
     if rank == 0 and save_merged:
         # the adapters folded into the projections, under the cfg of a run without --lora-rank: a plain mDT checkpoint
         check_guard(max_update)
-        plain = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("lora_rank", "lora_alpha", "lora_targets")})
+        plain = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("lora_rank", "lora_alpha", "lora_targets", "lora_dropout")})
         ckpt.save_checkpoint(save_merged, model, plain, model_state=ckpt.merged_model_state(model, opt), num_updates=max_update,
                              criterion_name=crit_cls.__name__, training_time=time.time() - t0)
     main.last_run = dict(model=model, criterion=crit, valid_batches=valid_batches, optimizer=opt, fp8=fp8_state)     # for tests / notebooks
