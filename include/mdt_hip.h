@@ -333,6 +333,20 @@ int mdt_node_ce(void* stream, int dtype, int64_t M, int nlab, const void* logits
                 const int32_t* targets, float w_neg, float w_pos, int fp16_loss, float grad_scale,
                 float* out_loss, int32_t* counters, void* dlogits);
 
+/* Label-smoothed / focal objective of the same classifier (--label-smoothing, --focal-gamma), csrc/node_objective.hip.
+ * Operands as mdt_node_ce; label_smoothing eps in [0, 1), focal_gamma >= 0, both finite.  Per labelled row, y the
+ * target and o = 1 - y: nll = -w_y lp_y, f = expf(gamma lp_o) = (1 - p_y)^gamma,
+ *   loss = (1 - eps) f nll + (eps / 2) sum_c (-w_c lp_c)
+ * (gamma = 0: F.cross_entropy(weight, label_smoothing = eps, reduction "sum"); eps = 0: the focal loss with alpha_t = w_y;
+ * the focal factor modulates the hard-target term only and is differentiated).  out f32[2] = sum loss, sum nll;
+ * counters as mdt_node_ce (equal integers on the same logits); dlogits T[M,2] = grad_scale * dL/d logits, zero for
+ * unlabelled rows (NULL: forward only).  fp16_loss: the logits and the class weights are rounded to fp16 first and the
+ * predictions use the half-rounded softmax, as in mdt_node_ce; everything else is fp32.  The sums run in a fixed order: two
+ * calls on the same operands give the same bits.  A refused call (MDT_ERR_ARG / MDT_ERR_UNSUPPORTED) writes nothing. */
+int mdt_node_objective(void* stream, int dtype, int64_t M, int nlab, const void* logits, const int32_t* rows,
+                       const int32_t* targets, float w_neg, float w_pos, int fp16_loss, float label_smoothing,
+                       float focal_gamma, float grad_scale, float* out, int32_t* counters, void* dlogits);
+
 /* ------------------------------------------------------------------ fp8 operands (BASELINE.json configs[4])
  * Per-tensor-scaled OCP fp8 for the big k-contiguous GEMMs of the encoder blocks (every nn.Linear forward and, against a
  * transposed weight copy, every input gradient): C[M,N] (bf16) = epilogue((1/scale_a)(1/scale_b) * A[M,K] B[N,K]^T), A in

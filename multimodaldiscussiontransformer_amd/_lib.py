@@ -102,6 +102,7 @@ _SIGS = {
     "mdt_tanh_fwd": ([_vp, _i, _i64, _vp, _vp], _i),
     "mdt_tanh_bwd": ([_vp, _i, _i64, _vp, _vp, _vp], _i),
     "mdt_node_ce": ([_vp, _i, _i64, _i, _vp, _vp, _vp, _f, _f, _i, _f, _vp, _vp, _vp], _i),
+    "mdt_node_objective": ([_vp, _i, _i64, _i, _vp, _vp, _vp, _f, _f, _i, _f, _f, _f, _vp, _vp, _vp], _i),
     "mdt_gemm_fp8": ([_vp, _i, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f,
                       C.c_uint64, _vp], _i),
     "mdt_gemm_fp8_q8": ([_vp, _i, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f,

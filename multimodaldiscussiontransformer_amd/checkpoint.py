@@ -287,6 +287,7 @@ def load_checkpoint(path: str, model, *, optimizer=None, reset_optimizer: bool =
         if not reset_lr_scheduler:
             out["lr_scheduler_state"] = dict(hist[-1].get("lr_scheduler_state") or {})
     extra = state.get("extra_state") or {}
+    out["cfg"] = state.get("cfg")     # the nested config of the run that wrote the file (None: a legacy checkpoint)
     out["ema"] = extra.get("ema")     # FairSeq --store-ema: the averaged weights (model state: kept whatever is reset); None: not stored
     if not reset_meters:
         out["extra_state"] = extra

@@ -19,7 +19,7 @@ __all__ = [
     "bert_embed_rows",
     "gemm", "colsum", "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "attention_mean_probs", "graph_attn_bias",
     "row_axpby", "row_scatter_add", "bert_embed_sum", "bert_embed_ln_rows", "vit_patchify", "vit_assemble", "vit_patch_embed", "graph_node_feature",
-    "tanh_fwd", "tanh_bwd", "node_ce", "contrastive_loss", "fp8_quantize", "fp8_scale_update", "gemm_fp8", "cast", "transpose2d", "dropout", "dropout_mask",
+    "tanh_fwd", "tanh_bwd", "node_ce", "node_objective", "contrastive_loss", "fp8_quantize", "fp8_scale_update", "gemm_fp8", "cast", "transpose2d", "dropout", "dropout_mask",
     "sum_slices", "gemm_splitk_ordered", "colsum_ordered", "layernorm_bwd_ordered", "segments_of", "row_segment_sum",
     "attn_bias_grad_ordered", "float_atomic_launches", "lora_down", "lora_up_add", "lora_up_add_drop", "lora_up_add_mul", "lora_up_act", "lora_wgrad",
     "lora_down_drop", "lora_wgrad_drop", "lora_up_add_mul_drop", "LORA_WGRAD_SLAB",
@@ -613,6 +613,21 @@ def node_ce(logits, rows, targets, w_neg, w_pos, *, fp16_loss=True, grad_scale=1
                           float(w_pos), int(fp16_loss), float(grad_scale), ptr(loss), ptr(counters), ptr(dlogits)),
           "mdt_node_ce")
     return loss, counters, dlogits
+
+
+def node_objective(logits, rows, targets, w_neg, w_pos, *, label_smoothing=0.0, focal_gamma=0.0, fp16_loss=True, grad_scale=1.0,
+                   want_grad=True):
+    """→ (out f32[2]: the label-smoothed / focal objective and the plain weighted NLL, counters i32[4], dlogits or None);
+    include/mdt_hip.h."""
+    M = logits.shape[0]
+    assert logits.shape[1] == 2 and logits.is_contiguous()
+    out = torch.empty(2, dtype=torch.float32, device=logits.device)
+    counters = torch.empty(4, dtype=torch.int32, device=logits.device)
+    dlogits = torch.empty_like(logits) if want_grad else None
+    check(lib.mdt_node_objective(stream(), dt(logits), M, rows.numel(), ptr(logits), ptr(rows), ptr(targets), float(w_neg),
+                                 float(w_pos), int(fp16_loss), float(label_smoothing), float(focal_gamma), float(grad_scale),
+                                 ptr(out), ptr(counters), ptr(dlogits)), "mdt_node_objective")
+    return out, counters, dlogits
 
 
 def contrastive_loss(emb, y, hard_y, scale, soft_negative_weight, adaptive, *, grad_scale=1.0, want_grad=True):

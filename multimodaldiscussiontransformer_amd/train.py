@@ -117,7 +117,9 @@ def build_parser():
             if f.type in (bool, "bool"):
                 p.add_argument(flag, type=lambda v: str(v).lower() in ("1", "true", "yes"), nargs="?", const=True, default=f.default)
             else:
-                p.add_argument(flag, type=type(f.default), default=f.default)
+                # an opt-in field (--label-smoothing, --focal-gamma) stays None until given: main() keeps it out of the
+                # checkpoint cfg of a run without it and can tell "not given" from "given as 0" when it restores
+                p.add_argument(flag, type=type(f.default), default=None if f.metadata.get("opt_in") else f.default)
     p.add_argument("--distributed-world-size", type=int, default=1)
     p.add_argument("--save-checkpoint", default="", help="write a FairSeq-layout checkpoint here at the end")
     p.add_argument("--save-dir", default="", help="FairSeq: checkpoint_last.pt (and checkpoint<epoch>.pt) are written here")
@@ -258,6 +260,32 @@ def _main(argv):
     else:
         for f in ("lora_rank", "lora_alpha", "lora_targets", "lora_dropout"):      # a run without adapters writes the checkpoint cfg it always wrote
             delattr(args, f)
+    # --label-smoothing / --focal-gamma (criterions/hatespeech_loss.py): None until given.  Left alone, a restored run takes
+    # them from its checkpoint's cfg (below, after the restore); a run without them keeps the cfg, the log keys and the
+    # six-wide scalar vectors it always had.
+    objective_names = ("label_smoothing", "focal_gamma")
+    objective_given = [f for f in objective_names if getattr(args, f) is not None]
+    if objective_given and args.criterion != "node_cross_entropy":
+        raise SystemExit("[mdt-train] " + ", ".join("--" + f.replace("_", "-") for f in objective_given) + f" with --criterion "
+                         f"{args.criterion}: only node_cross_entropy has a label-smoothed / focal objective")
+
+    def set_objective(eps, gamma):
+        """The two values into ``args`` where the objective is on, out of it where it is off; → on."""
+        from .criterions.hatespeech_loss import check_objective
+        eps, gamma = float(eps or 0.0), float(gamma or 0.0)
+        try:
+            check_objective(eps, gamma)
+        except ValueError as e:
+            raise SystemExit(f"[mdt-train] --label-smoothing must be in [0, 1) and --focal-gamma finite and >= 0 ({e})")
+        on = eps != 0.0 or gamma != 0.0
+        for f, v in zip(objective_names, (eps, gamma)):
+            if on:
+                setattr(args, f, v)
+            elif hasattr(args, f):
+                delattr(args, f)
+        return on
+
+    objective_on = set_objective(args.label_smoothing, args.focal_gamma)
     from . import engine
     was_deterministic = engine.deterministic()
     if args.deterministic:
@@ -358,6 +386,14 @@ def _main(argv):
                                     reset_lr_scheduler=args.reset_lr_scheduler, reset_meters=args.reset_meters,
                                     reset_dataloader=args.reset_dataloader, allow_missing_prefixes=("node_encoder_stack.",))
         start_update, epoch0 = info["num_updates"], info["epoch"]
+        stored = (info.get("cfg") or {}).get("model") or {}
+        if not objective_given and args.criterion == "node_cross_entropy" and any(stored.get(f) for f in objective_names):
+            # the objective the checkpoint was trained with goes on, as its cfg records it; either flag on the command line
+            # (0 included) says otherwise
+            objective_on = set_objective(stored.get("label_smoothing"), stored.get("focal_gamma"))
+            crit.label_smoothing, crit.focal_gamma = args.label_smoothing, args.focal_gamma
+            print(f"[mdt-train] {args.restore_file} was trained with --label-smoothing {args.label_smoothing:g} --focal-gamma "
+                  f"{args.focal_gamma:g}: continuing with them", file=sys.stderr)
         if rank == 0:
             print(json.dumps(dict(restored=args.restore_file, num_updates=start_update, optimizer=info["loaded_optimizer"],
                                   missing=len(info["missing"]), unexpected=len(info["unexpected"]))), flush=True)
@@ -448,7 +484,10 @@ def _main(argv):
         for _ in range(start_update * args.update_freq):        # resume the batch order where the checkpoint left it
             next(stream)
     max_update = args.max_update or (args.max_epoch * n_batches // max(1, args.update_freq)) or 50
-    scal = torch.zeros(6, dtype=torch.float32, device="cuda")
+    # loss, sample size and the criterion's four counters; with the label-smoothed / focal objective one more slot: nll_loss
+    n_scal = 7 if objective_on else 6
+    not_counters = ("loss", "sample_size", "nsentences", "ntokens", "nll_loss")
+    scal = torch.zeros(n_scal, dtype=torch.float32, device="cuda")
     history = []
     it = 0
     t0 = time.time()
@@ -499,16 +538,18 @@ def _main(argv):
         was = model.training
         rng = torch.get_rng_state() if keep_rng else None
         model.eval()
-        tot = torch.zeros(6, dtype=torch.float32, device="cuda")
+        tot = torch.zeros(n_scal, dtype=torch.float32, device="cuda")
         keys = None
         import contextlib
         with (opt.ema_weights() if validate_with_ema else contextlib.nullcontext()), torch.no_grad():
             for pb in valid_batches():
                 loss, sample_size, log = crit(model, {"nsamples": pb.B, "net_input": {"batched_data": pb.batched_data}})
-                keys = [k for k in log if k not in ("loss", "sample_size", "nsentences", "ntokens")]
+                keys = [k for k in log if k not in not_counters]
                 tot[0] += loss.detach().float()
                 tot[1] += float(sample_size)
                 tot[2:6] += torch.stack([log[k] for k in keys]).float()
+                if objective_on:
+                    tot[6] += log["nll_loss"].float()
         model.train(was)
         if rng is not None:
             torch.set_rng_state(rng)
@@ -517,7 +558,7 @@ def _main(argv):
         if keys is None:
             keys = ["ncorrect", "num_positive_correct", "total_positive", "num_pred_positive"]
         s_ = tot.tolist()
-        summed = dict(loss=s_[0], sample_size=s_[1], **dict(zip(keys, s_[2:6])))
+        summed = dict(loss=s_[0], sample_size=s_[1], **dict(zip(keys, s_[2:6])), **(dict(nll_loss=s_[6]) if objective_on else {}))
         crit_cls.reduce_metrics([summed])            # logs through fairseq.metrics when fairseq is there
         m = {("valid_" + k): v for k, v in crit_cls.compute_metrics([summed]).items()}
         m.update(valid_counters=summed, num_updates=upd, subset=args.valid_subset)
@@ -535,24 +576,28 @@ def _main(argv):
         torch.set_rng_state(info["extra_state"]["rng_state"])
     for upd in range(start_update + 1, max_update + 1):
         dp.zero_grad()
-        acc = torch.zeros(6, dtype=torch.float32, device="cuda")
+        acc = torch.zeros(n_scal, dtype=torch.float32, device="cuda")
         for micro in range(args.update_freq):
             dp.accumulate(micro == args.update_freq - 1)
             pb = next(stream)
             it += 1
             loss, sample_size, log = crit(model, {"nsamples": pb.B, "net_input": {"batched_data": pb.batched_data}})
             loss.backward()
-            counter_keys = [k for k in log if k not in ("loss", "sample_size", "nsentences", "ntokens")]   # 4 per criterion
+            counter_keys = [k for k in log if k not in not_counters]   # 4 per criterion
             acc[0] += loss.detach().float()
             acc[1] += float(sample_size)
             acc[2:6] += torch.stack([log[k] for k in counter_keys]).float()
+            if objective_on:
+                acc[6] += log["nll_loss"].float()
         scal.copy_(acc)
         gscale = dp.finish_backward(scal, fold_scale=True)     # all-reduce (world > 1); 1 / global sample size is applied by the optimiser
         opt.step(lr=lr_for(upd), grad_scale=gscale, num_updates=upd)
         if upd % args.log_interval == 0 or upd == max_update:
             s = torch.cat([scal.double(), opt.guard_log_vector()]).tolist()     # the only host sync, once per log interval
-            g = check_guard(upd, dict(gnorm=s[6], applied=int(s[7]), clipped=int(s[8]), skipped=int(s[9])))
-            m = crit_cls.compute_metrics([dict(loss=s[0], sample_size=s[1], **dict(zip(counter_keys, s[2:6])))])
+            gw = s[n_scal:]
+            g = check_guard(upd, dict(gnorm=gw[0], applied=int(gw[1]), clipped=int(gw[2]), skipped=int(gw[3])))
+            m = crit_cls.compute_metrics([dict(loss=s[0], sample_size=s[1], **dict(zip(counter_keys, s[2:6])),
+                                               **(dict(nll_loss=s[6]) if objective_on else {}))])
             # FairSeq's meters: gnorm of this update, clip = per cent of the updates since the previous line that were clipped
             m.update(num_updates=upd, lr=lr_for(upd), gnorm=g["gnorm"], clip=100.0 * (g["clipped"] - meter["clipped"]) / (upd - meter["upd"]),
                      skipped_updates=g["skipped"], wall=round(time.time() - t0, 2))
